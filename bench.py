@@ -7,7 +7,13 @@ field-structured data resident in HBM. value = nnz_train * k * steps / wall time
 timed steps for the WHOLE data set (all ranks), wall time = max over ranks.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2|multihot|tiny]
-                    [--scaling strong|weak] [--shard rows|features]
+                    [--scaling strong|weak] [--shard rows|features] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the steps and prints the result line. --full adds the CPU
+baseline (the reference's sweep on a sample of the same data, on one host core, beside the
+timed steps). --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs below); the inputs depend on the arguments alone, so two builds can be compared
+output for output.
 
 Default workload: BASELINE configs[3] / the metric's "k=100 100M rows": 1e8 rows x 40
 one-hot fields x 125000 ids (D = 5e6), nnz = 4e9, k = 100.
@@ -374,6 +380,40 @@ def host_allreduce(arr, op):
     arr[:] = t.numpy().astype(arr.dtype)
 
 
+DUMP_SAMPLE = 1 << 19        # elements kept of a larger array (4 MB as float64)
+DUMP_MAX_BYTES = 64 << 20    # of all the files together
+
+
+def dump_outputs(dirname, fml, st, rmse_trace):
+    """--dump-outputs: what the last timed step handed its caller, as <dirname>/<name>.npy in
+    float64 -- iter_stats (the step's statistics in the order of their struct's fields, times and
+    launch counts left out), test_rmse_trace (every step's, warm-up first), test_pred (the test
+    predictions) and every parameter array of get_params() (its scalars together, in the
+    dictionary's order, as param_scalars). An array of more than DUMP_SAMPLE elements is
+    written as its elements at DUMP_SAMPLE sorted indices drawn once from a fixed seed, the same
+    for every run of the same shape."""
+    import numpy as np
+    arrays = {"iter_stats": [float(v) for key, v in st.as_dict().items() if not key.startswith(("ms_", "n_"))],
+              "test_rmse_trace": rmse_trace, "test_pred": fml.predict()}
+    scalars = []
+    for key, v in fml.get_params().items():
+        if isinstance(v, np.ndarray):
+            arrays[key] = v
+        else:
+            scalars.append(float(v))
+    arrays["param_scalars"] = scalars
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64).ravel()
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(20240607).integers(0, a.size, DUMP_SAMPLE))]
+        total += a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    assert total <= DUMP_MAX_BYTES, total
+    return total
+
+
 def loaded_libs(name):
     """Distinct files named like `name` mapped into this process (one RCCL, not two)."""
     paths = set()
@@ -426,6 +466,12 @@ def main():
                     help="hand the train set over from host memory (vbfm_set_train: the copy to the device and "
                          "the device's CSR build, the drop-in CLI's path) instead of generating it in HBM; the "
                          "data is the same (generated on the device by a scratch context and copied back first)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (the reference's "
+                         "sweep on a sample of the data set, rank 0, during the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (its statistics, the test "
+                         "predictions, the parameters; large arrays as a fixed seeded sample) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-rows", type=int, default=20_000_000,
                     help="rows of the CPU baseline's sample (reported); a 2e6-row, 2-factor sample runs beside it")
@@ -574,8 +620,11 @@ def main():
             setup["s_store"], setup["s_placement"], setup["place_candidates"]))
 
     cpu_leg = None
-    run_leg, leg_reason = cpu_leg_plan(rank, world, args, mc, online, multihot)
-    leg_any = cpu_leg_plan(0, world, args, mc, online, multihot)[0]   # some rank runs it
+    if args.full:
+        run_leg, leg_reason = cpu_leg_plan(rank, world, args, mc, online, multihot)
+        leg_any = cpu_leg_plan(0, world, args, mc, online, multihot)[0]   # some rank runs it
+    else:   # a plain run times the GPU steps alone
+        run_leg, leg_reason, leg_any = False, "the CPU baseline runs with --full", False
     core = cpu_leg_core() if leg_any else None
     if leg_any:
         pin_away_from(core)     # every rank: the GPU-driving threads leave the CPU leg's core
@@ -631,6 +680,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        log("outputs of the last step: %d bytes under %s" % (
+            dump_outputs(args.dump_outputs, fml, stats[-1], rmse_trace), args.dump_outputs))
 
     if fshard or world == 1:
         nnz_total = nnz                  # the whole data set's (all ranks)

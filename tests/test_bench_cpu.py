@@ -213,6 +213,48 @@ def test_cpu_leg_core_and_pinning():
                 pass
 
 
+def test_dump_outputs_writes_sampled_float64_arrays(tmp_path):
+    """--dump-outputs: every array the last step handed back as <name>.npy in float64, a large one
+    as the same seeded sample in every run, the scalars together, times and launch counts left out,
+    all within the size limit."""
+    bench = _bench_module()
+    big = np.arange(3 * bench.DUMP_SAMPLE, dtype=np.float64)
+
+    class St:
+        def as_dict(self):
+            return {"rmse": 0.5, "num_levels": 7, "ms_total": 123.0, "n_vlevel_launches": 9, "nnz_train": 11}
+
+    class Fml:
+        def predict(self):
+            return np.array([1.0, 2.5], dtype=np.float64)
+
+        def get_params(self):
+            return {"mu_w": np.array([1, 2, 3], dtype=np.float64), "mu_v": big, "alpha": 2.0, "sigma_0": 3.0}
+
+    total = [bench.dump_outputs(str(tmp_path / d), Fml(), St(), [0.9, 0.8]) for d in ("a", "b")]
+    assert total[0] == total[1] <= bench.DUMP_MAX_BYTES
+    got = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["iter_stats.npy", "mu_v.npy", "mu_w.npy", "param_scalars.npy", "test_pred.npy",
+                           "test_rmse_trace.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) == total[0]
+    np.testing.assert_array_equal(got["iter_stats.npy"], [0.5, 7.0, 11.0])
+    np.testing.assert_array_equal(got["param_scalars.npy"], [2.0, 3.0])
+    np.testing.assert_array_equal(got["test_pred.npy"], [1.0, 2.5])
+    np.testing.assert_array_equal(got["test_rmse_trace.npy"], [0.9, 0.8])
+    np.testing.assert_array_equal(got["mu_w.npy"], [1, 2, 3])
+    s = got["mu_v.npy"]
+    assert s.size == bench.DUMP_SAMPLE and np.all(np.diff(s) >= 0) and s[-1] > 2 * bench.DUMP_SAMPLE
+    np.testing.assert_array_equal(s, np.load(tmp_path / "b" / "mu_v.npy"))
+
+
+def test_full_and_dump_outputs_options_parse():
+    """--full and --dump-outputs DIR are options of the bench; a dry run writes nothing."""
+    out = _dry(["--full", "--dump-outputs", "unused"])
+    assert out.returncode == 0, out.stderr
+    assert "--full" in subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True).stdout
+
+
 def _exchange_worker(rank, world, port, q):
     import numpy as np
     import torch.distributed as dist

@@ -72,6 +72,33 @@ def test_eight_rank_bench_matches_one_rank():
     _close(eight["free_energy"], one["free_energy"])
 
 
+def test_dump_outputs_repeat_and_plain_run_skips_the_cpu_baseline(tmp_path):
+    """A plain run (no --full) reports the CPU baseline as left out; --dump-outputs writes the
+    last step's statistics, test predictions and parameters as float64 .npy files, and a second
+    run with the same arguments writes the same values (to summation order: the level sums are
+    atomic adds) -- the test RMSE in the dump is the one in the line."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    runs = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "tiny", "--steps", "2",
+                              "--warmup", "1", "--dump-outputs", str(tmp_path / d)],
+                             env=env, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        runs.append((line, {p.name[:-4]: np.load(p) for p in (tmp_path / d).iterdir()}))
+    (line, a), (_, b) = runs
+    assert line["cpu_baseline"]["value"] is None and "--full" in line["cpu_baseline"]["skipped"]
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert {"iter_stats", "test_rmse_trace", "test_pred", "mu_w", "sigma_w", "mu_v", "sigma_v",
+            "param_scalars"} <= set(a) == set(b)
+    assert a["test_pred"].size == 2000 and a["mu_v"].size == 8 * 20001 and a["test_rmse_trace"].size == 3
+    assert a["iter_stats"][0] == line["test_rmse"]
+    for name in a:
+        assert a[name].dtype == np.float64 and np.all(np.isfinite(a[name])), name
+        assert np.max(np.abs(a[name] - b[name])) <= REL * np.max(np.abs(b[name])), name
+
+
 def test_bench_rank_fault_ends_the_run():
     """The N-rank launch with a faulting rank (VBFM_FAULT=comm on rank 2 of 4: its first exchange
     inside a sweep fails as a failed collective would): that rank exits non-zero and the launcher

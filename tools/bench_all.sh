@@ -10,7 +10,7 @@ run() {
 	local name=$1; shift
 	timeout -k 10 $1 python -u bench.py "${@:2}" > $out/$name.json 2> $out/$name.err || exit $?
 }
-run c4_vb 420 --steps 5 --warmup 1
+run c4_vb 420 --full --steps 5 --warmup 1
 run c4_mcmc 300 --method mcmc --steps 3 --warmup 1
 run c3_online 200 --config c3 --method vb_online --steps 3 --warmup 1
 run multihot 300 --config multihot --steps 3 --warmup 1 --no-launch-events
