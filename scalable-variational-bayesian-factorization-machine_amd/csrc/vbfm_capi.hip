@@ -409,6 +409,34 @@ static void build_long_segs(vbfm_ctx *c, const std::vector<uint64_t> &lcp, const
 	sync(c);
 }
 
+// x of every train entry (c->lx), unless all are 1.0f (one-hot libfm data): the level kernels
+// then read no x at all (VBFM_LX=1 keeps the array)
+static void alloc_lx(vbfm_ctx *c)
+{
+	DevData &d = c->tr;
+	uint32_t *cnt = dalloc<uint32_t>(1), h = 1;
+	HIPCHK(vbk::count_x_ne1(d.csc, d.nnz, cnt, c->s));
+	HIPCHK(d2h(c, &h, cnt, 4));
+	sync(c);
+	dfree(cnt);
+	const char *kx = getenv("VBFM_LX");
+	if (h != 0 || (kx && kx[0] == '1')) c->lx = dalloc<float>(d.nnz);
+}
+
+// the deferred kernels' payload: one 16-B record per entry {x, next position, previous entry's
+// feature index, its x}, or 8 B {next, previous} when every x (and so every previous x) is 1
+static void pack_payload(vbfm_ctx *c, const uint32_t *pidx, const float *px)
+{
+	const uint64_t nnz = c->tr.nnz;
+	if (c->lx) {
+		c->lpay = dalloc<uint4>(nnz);
+		HIPCHK(vbk::lord_pack(c->lx, c->lnext, pidx, px, c->lpay, nnz, c->s));
+	} else {
+		c->lpay2 = dalloc<uint2>(nnz);
+		HIPCHK(vbk::lord_pack2(c->lnext, pidx, c->lpay2, nnz, c->s));
+	}
+}
+
 // The entry store, for levels that miss rows (multi-hot rows without fields): one slot per
 // train entry in the field store's order (level by level, the level's columns in ascending
 // feature order, rows ascending in a column), nnz x 64 B; a row's record waits in the slot of
@@ -447,15 +475,7 @@ bool build_estore(vbfm_ctx *c, const std::vector<uint64_t> &lcp, const std::vect
 	HIPCHK(hipMemcpyAsync(c->lcp, lcp.data(), lcp.size() * 8, hipMemcpyHostToDevice, c->s));
 	uint32_t *lv = dalloc<uint32_t>(nf);
 	HIPCHK(hipMemcpyAsync(lv, lvpos.data(), (size_t)nf * 4, hipMemcpyHostToDevice, c->s));
-	{
-		uint32_t *cnt = dalloc<uint32_t>(1), h = 1;
-		HIPCHK(vbk::count_x_ne1(d.csc, d.nnz, cnt, c->s));
-		HIPCHK(d2h(c, &h, cnt, 4));
-		sync(c);
-		dfree(cnt);
-		const char *kx = getenv("VBFM_LX");
-		if (h != 0 || (kx && kx[0] == '1')) c->lx = dalloc<float>(d.nnz);
-	}
+	alloc_lx(c);
 	c->lnext = dalloc<uint32_t>(d.nnz);
 	c->lpos0 = dalloc<uint32_t>(n);
 	// slots: the entries, then one parking slot per row (used by rows without entries)
@@ -472,13 +492,7 @@ bool build_estore(vbfm_ctx *c, const std::vector<uint64_t> &lcp, const std::vect
 		uint32_t *pidx = dalloc<uint32_t>(d.nnz);
 		float *px = dalloc<float>(d.nnz);
 		HIPCHK(vbk::estore_prev(d.row_ptr, d.csr, d.col_ptr, d.csc, lv, c->lcp, n, pidx, px, c->s));
-		if (c->lx) {
-			c->lpay = dalloc<uint4>(d.nnz);
-			HIPCHK(vbk::lord_pack(c->lx, c->lnext, pidx, px, c->lpay, d.nnz, c->s));
-		} else {   // every x 1: 8 B per entry
-			c->lpay2 = dalloc<uint2>(d.nnz);
-			HIPCHK(vbk::lord_pack2(c->lnext, pidx, c->lpay2, d.nnz, c->s));
-		}
+		pack_payload(c, pidx, px);
 		c->post_tab = dalloc<PostT>(std::max(nf, 1u));
 		HIPCHK(hipMemsetAsync(c->post_tab, 0, (size_t)std::max(nf, 1u) * sizeof(PostT), c->s));
 		sync(c);
@@ -717,17 +731,7 @@ void build_lorder(vbfm_ctx *c, const std::vector<uint64_t> &cp, const std::vecto
 	c->lcp = dalloc<uint64_t>(lcp.size());
 	HIPCHK(hipMemcpyAsync(c->lcp, lcp.data(), lcp.size() * 8, hipMemcpyHostToDevice, c->s));
 	build_long_segs(c, lcp, dup, feats);
-	// x of every entry, unless all are 1.0f (one-hot libfm data): the level kernels then
-	// read no x at all (VBFM_LX=1 keeps the array)
-	{
-		uint32_t *cnt = dalloc<uint32_t>(1), h = 1;
-		HIPCHK(vbk::count_x_ne1(d.csc, d.nnz, cnt, c->s));
-		HIPCHK(d2h(c, &h, cnt, 4));
-		sync(c);
-		dfree(cnt);
-		const char *kx = getenv("VBFM_LX");
-		if (h != 0 || (kx && kx[0] == '1')) c->lx = dalloc<float>(d.nnz);
-	}
+	alloc_lx(c);
 	c->lnext = dalloc<uint32_t>(d.nnz);
 	c->lrow0 = dalloc<uint32_t>(n);
 	c->lpos0 = dalloc<uint32_t>(n);
@@ -773,16 +777,9 @@ void build_lorder(vbfm_ctx *c, const std::vector<uint64_t> &cp, const std::vecto
 		c->post_tab = dalloc<PostT>(maxlev);
 		sync(c);
 		dfree(tmpx);
-		// one 16-B record per entry for the deferred kernels; the separate arrays are not
-		// read in this mode any more
+		// the separate arrays are not read in this mode any more
 		dfree(tmp);
-		if (c->lx) {
-			c->lpay = dalloc<uint4>(d.nnz);
-			HIPCHK(vbk::lord_pack(c->lx, c->lnext, c->lpidx, c->lpx, c->lpay, d.nnz, c->s));
-		} else {   // every x (and so every previous x) is 1: 8 B per entry
-			c->lpay2 = dalloc<uint2>(d.nnz);
-			HIPCHK(vbk::lord_pack2(c->lnext, c->lpidx, c->lpay2, d.nnz, c->s));
-		}
+		pack_payload(c, c->lpidx, c->lpx);
 		sync(c);
 		dfree(c->lx); dfree(c->lnext); dfree(c->lpidx); dfree(c->lpx);
 	}

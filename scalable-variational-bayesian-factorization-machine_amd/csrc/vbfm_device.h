@@ -79,6 +79,43 @@ inline int shape_block(uint32_t avg)
 	return b;
 }
 
+// A runtime flag as a template argument: f(std::true_type) or f(std::false_type). For the
+// two-way axes that are independent of the sweep (ENT, PAY8, the online PAD).
+template <class F> inline void dispatch_bool(bool b, F &&f)
+{
+	if (b) f(std::true_type());
+	else f(std::false_type());
+}
+
+// A three-way axis (the MCMC MODE, the deferred split's PK): f(integral_constant<int, 0|1|2>);
+// the callers pass nothing but 0, 1 or 2
+template <class F> inline void dispatch_mode(int m, F &&f)
+{
+	if (m == 0) f(std::integral_constant<int, 0>());
+	else if (m == 1) f(std::integral_constant<int, 1>());
+	else f(std::integral_constant<int, 2>());
+}
+
+// The sweep variant every level kernel is specialised on: IS_W (the w sweep, or a factor's), P
+// (the q-cache slot the factor is swept from) and NEXT (the next factor's q-cache is accumulated
+// along the way). The w sweep has no q-cache of its own and always runs as P = 0, so only
+// (W,0), (V,0) and (V,1) exist -- (W,1) is never instantiated -- each with and without NEXT: six
+// variants, chosen here and nowhere else. f(W, P[, N]) is called with integral_constants, as
+// dispatch_shape's; a v-only kernel family passes is_w = false and ignores W.
+template <class F> inline void dispatch_wp(bool is_w, int slot, F &&f)
+{
+	typedef std::integral_constant<int, 0> P0;
+	typedef std::integral_constant<int, 1> P1;
+	if (is_w) f(std::true_type(), P0());
+	else if (slot == 0) f(std::false_type(), P0());
+	else f(std::false_type(), P1());
+}
+
+template <class F> inline void dispatch_sweep(bool is_w, int slot, bool next, F &&f)
+{
+	dispatch_wp(is_w, slot, [&](auto W, auto P) { dispatch_bool(next, [&](auto N) { f(W, P, N); }); });
+}
+
 struct __attribute__((aligned(64))) RowRec {
 	double e;    // cache[i].e      residual y - yhat (fm_learn_vb_simultaneous.h:42-44)
 	double q;    // cache[i].q      q-cache slot 0: sum mu x

@@ -1375,80 +1375,54 @@ __global__ __launch_bounds__(64) void k_stall(const volatile uint32_t *flag)
 
 namespace vbk {
 
-// Column-length-adaptive launch shape: threads per column and entries held per thread
-// from the level's mean column length (dispatch_shape, vbfm_device.h).
-template <int P, bool NEXT>
-hipError_t launch_v_fused(const LevelArgs &a, hipStream_t s)
-{
-	dispatch_shape(a.avg_len, [&](auto B, auto R) { k_v_level_fused<B(), R(), P, NEXT><<<a.nfeat, B(), 0, s>>>(a); });
-	return hipGetLastError();
-}
-
-template <bool NEXT>
-hipError_t launch_w_fused(const LevelArgs &a, hipStream_t s)
-{
-	dispatch_shape(a.avg_len, [&](auto B, auto R) { k_w_level_fused<B(), R(), NEXT><<<a.nfeat, B(), 0, s>>>(a); });
-	return hipGetLastError();
-}
-
 hipError_t stall(const uint32_t *flag, hipStream_t s)
 {
 	hipLaunchKernelGGL(k_stall, dim3(1), dim3(64), 0, s, flag);
 	return hipGetLastError();
 }
 
+// Column-length-adaptive launch shape: threads per column and entries held per thread
+// from the level's mean column length (dispatch_shape, vbfm_device.h); the sweep variant from
+// dispatch_sweep (the v kernels take no IS_W: they ignore it).
 hipError_t v_level_fused(const LevelArgs &a, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	const bool nx = a.ms_next != nullptr;
-	if (a.slot == 0) return nx ? launch_v_fused<0, true>(a, s) : launch_v_fused<0, false>(a, s);
-	return nx ? launch_v_fused<1, true>(a, s) : launch_v_fused<1, false>(a, s);
+	dispatch_sweep(false, a.slot, a.ms_next != nullptr, [&](auto, auto P, auto N) {
+		dispatch_shape(a.avg_len, [&](auto B, auto R) { k_v_level_fused<B(), R(), P(), N()><<<a.nfeat, B(), 0, s>>>(a); });
+	});
+	return hipGetLastError();
 }
 hipError_t w_level_fused(const LevelArgs &a, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	return a.ms_next ? launch_w_fused<true>(a, s) : launch_w_fused<false>(a, s);
+	dispatch_bool(a.ms_next != nullptr, [&](auto N) {
+		dispatch_shape(a.avg_len, [&](auto B, auto R) { k_w_level_fused<B(), R(), N()><<<a.nfeat, B(), 0, s>>>(a); });
+	});
+	return hipGetLastError();
 }
 hipError_t col_long(const LevelArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nsegs == 0) return hipSuccess;
-	const bool nx = a.ms_next != nullptr;
-	if (is_w) {
-		k_col_long_stats<true, 0><<<a.nsegs, 256, 0, s>>>(a);
-		if (nx) k_col_long_correct<true, 0, true><<<a.nsegs, 256, 0, s>>>(a);
-		else k_col_long_correct<true, 0, false><<<a.nsegs, 256, 0, s>>>(a);
-	} else if (a.slot == 0) {
-		k_col_long_stats<false, 0><<<a.nsegs, 256, 0, s>>>(a);
-		if (nx) k_col_long_correct<false, 0, true><<<a.nsegs, 256, 0, s>>>(a);
-		else k_col_long_correct<false, 0, false><<<a.nsegs, 256, 0, s>>>(a);
-	} else {
-		k_col_long_stats<false, 1><<<a.nsegs, 256, 0, s>>>(a);
-		if (nx) k_col_long_correct<false, 1, true><<<a.nsegs, 256, 0, s>>>(a);
-		else k_col_long_correct<false, 1, false><<<a.nsegs, 256, 0, s>>>(a);
-	}
+	dispatch_wp(is_w, a.slot, [&](auto W, auto P) {
+		k_col_long_stats<W(), P()><<<a.nsegs, 256, 0, s>>>(a);
+		dispatch_bool(a.ms_next != nullptr, [&](auto N) { k_col_long_correct<W(), P(), N()><<<a.nsegs, 256, 0, s>>>(a); });
+	});
 	return hipGetLastError();
 }
 hipError_t v_level_stats(const LevelArgs &a, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
 	// the fused kernel's BLOCK: the same reduction tree, so the split form equals the fused one
-	dispatch_shape(a.avg_len, [&](auto B, auto) {
-		if (a.slot == 0) k_v_level_stats<B(), 0><<<a.nfeat, B(), 0, s>>>(a);
-		else k_v_level_stats<B(), 1><<<a.nfeat, B(), 0, s>>>(a);
+	dispatch_wp(false, a.slot, [&](auto, auto P) {
+		dispatch_shape(a.avg_len, [&](auto B, auto) { k_v_level_stats<B(), P()><<<a.nfeat, B(), 0, s>>>(a); });
 	});
 	return hipGetLastError();
 }
 hipError_t v_level_correct(const LevelArgs &a, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	const bool nx = a.ms_next != nullptr;
-	if (a.slot == 0) {
-		if (nx) k_v_level_correct<256, 0, true><<<a.nfeat, 256, 0, s>>>(a);
-		else k_v_level_correct<256, 0, false><<<a.nfeat, 256, 0, s>>>(a);
-	} else {
-		if (nx) k_v_level_correct<256, 1, true><<<a.nfeat, 256, 0, s>>>(a);
-		else k_v_level_correct<256, 1, false><<<a.nfeat, 256, 0, s>>>(a);
-	}
+	dispatch_sweep(false, a.slot, a.ms_next != nullptr,
+	               [&](auto, auto P, auto N) { k_v_level_correct<256, P(), N()><<<a.nfeat, 256, 0, s>>>(a); });
 	return hipGetLastError();
 }
 hipError_t w_level_stats(const LevelArgs &a, hipStream_t s)
@@ -1460,8 +1434,7 @@ hipError_t w_level_stats(const LevelArgs &a, hipStream_t s)
 hipError_t w_level_correct(const LevelArgs &a, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	if (a.ms_next) k_w_level_correct<256, true><<<a.nfeat, 256, 0, s>>>(a);
-	else k_w_level_correct<256, false><<<a.nfeat, 256, 0, s>>>(a);
+	dispatch_bool(a.ms_next != nullptr, [&](auto N) { k_w_level_correct<256, N()><<<a.nfeat, 256, 0, s>>>(a); });
 	return hipGetLastError();
 }
 

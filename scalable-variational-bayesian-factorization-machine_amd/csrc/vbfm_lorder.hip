@@ -451,7 +451,7 @@ __global__ __launch_bounds__(LONG_BLOCK) void k_lord_long_move(LevelArgs a)
 }
 
 // split form (row-sharded multi-GPU): statistics of the local rows -> all-reduce -> move. The
-// launch shape is the fused kernel's (launch_lord): the same BLOCK gives the same reduction tree,
+// launch shape is the fused kernel's (lord_level): the same BLOCK gives the same reduction tree,
 // and a column's run takes no more LDS than it needs (with a fixed 256 x 2 shape the 100-entry
 // columns of one N = 8 rank held 33-35 KB per workgroup: 13-15 resident waves per CU, 336 + 472 us
 // per level against 341 us fused, profiles/r05_split/)
@@ -768,41 +768,6 @@ inline LordLead lord_lead(const LevelArgs &a)
 	return L;
 }
 
-template <bool IS_W, int P, bool NEXT>
-void launch_lord(const LevelArgs &a, hipStream_t s)
-{
-	const LordLead L = lord_lead(a);
-	dispatch_shape(a.avg_len, [&](auto B, auto R) {
-		if (a.ent) k_level_lord<B(), R(), IS_W, P, NEXT, true><<<a.nfeat, B(), 0, s>>>(LORD_LEAD_ARGS(L), a);
-		else k_level_lord<B(), R(), IS_W, P, NEXT, false><<<a.nfeat, B(), 0, s>>>(LORD_LEAD_ARGS(L), a);
-	});
-}
-
-template <bool IS_W, int P, bool NEXT, bool ENT>
-void launch_lord_move_shape(const LevelArgs &a, hipStream_t s)
-{
-	dispatch_shape(a.avg_len, [&](auto B, auto R) { k_level_lord_move<B(), R(), IS_W, P, NEXT, ENT><<<a.nfeat, B(), 0, s>>>(a); });
-}
-
-template <bool IS_W, int P>
-void launch_lord_move(const LevelArgs &a, hipStream_t s)
-{
-	if (a.ent) {
-		if (a.ms_next) launch_lord_move_shape<IS_W, P, true, true>(a, s);
-		else launch_lord_move_shape<IS_W, P, false, true>(a, s);
-		return;
-	}
-	if (a.ms_next) launch_lord_move_shape<IS_W, P, true, false>(a, s);
-	else launch_lord_move_shape<IS_W, P, false, false>(a, s);
-}
-
-template <bool IS_W, int P>
-void launch_lord_stats(const LevelArgs &a, hipStream_t s)
-{
-	dispatch_shape(a.avg_len, [&](auto B, auto R) { k_level_lord_stats<B(), R(), IS_W, P><<<a.nfeat, B(), 0, s>>>(a); });
-}
-
-
 // ---- deferred correction (row-sharded split) ---------------------------------------------
 // The split form above streams every level's records twice (statistics, then after the
 // all-reduce the move). Deferred: level l's kernel applies level l-1's correction to each
@@ -1041,44 +1006,6 @@ __global__ __launch_bounds__(256) void k_lord_prev_fill(const uint32_t *feats, c
 }
 
 
-template <bool IS_W, int P, bool NEXT, int PK, bool ENT>
-void launch_defer_shape(const LevelArgs &a, hipStream_t s)
-{
-	if (a.lpay2) {   // every x 1: 8-B payloads
-		dispatch_shape(a.avg_len, [&](auto B, auto R) {
-			k_lord_defer<B(), R(), IS_W, P, NEXT, PK, true, ENT><<<a.nfeat, B(), 0, s>>>(a);
-		});
-		return;
-	}
-	dispatch_shape(a.avg_len, [&](auto B, auto R) {
-		k_lord_defer<B(), R(), IS_W, P, NEXT, PK, false, ENT><<<a.nfeat, B(), 0, s>>>(a);
-	});
-}
-
-template <bool IS_W, int P, bool NEXT, int PK>
-void launch_defer_pk(const LevelArgs &a, hipStream_t s)
-{
-	if (a.ent) launch_defer_shape<IS_W, P, NEXT, PK, true>(a, s);
-	else launch_defer_shape<IS_W, P, NEXT, PK, false>(a, s);
-}
-
-template <bool IS_W, int P, bool NEXT>
-void launch_defer(const LevelArgs &a, hipStream_t s)
-{
-	if constexpr (!IS_W) {
-		if (a.pend_kind == 1) return launch_defer_pk<IS_W, P, NEXT, 1>(a, s);
-		if (a.pend_kind == 2) return launch_defer_pk<IS_W, P, NEXT, 2>(a, s);
-	}
-	launch_defer_pk<IS_W, P, NEXT, 0>(a, s);
-}
-
-template <bool IS_W, int P, bool NEXT>
-void launch_flush(const LevelArgs &a, uint32_t n, hipStream_t s)
-{
-	if (a.ent) k_lord_defer_flush_ent<IS_W, P><<<(n + 255) / 256, 256, 0, s>>>(a, n);
-	else k_lord_defer_flush<IS_W, P, NEXT><<<(n + 255) / 256, 256, 0, s>>>(a, n);
-}
-
 // ---- MCMC / ALS deferred split (row shards) ------------------------------------------------
 // As k_lord_defer for VB: level l's kernel applies level l-1's correction (fm_learn_mcmc.h
 // draw_v :826-834 / draw_w :712-717) from the table the previous post kernel wrote after its
@@ -1213,53 +1140,6 @@ __global__ __launch_bounds__(256) void k_mc_lord_defer_flush(McArgs a, uint32_t 
 	for (uint32_t t = threadIdx.x; t < m * 4; t += 256) r[t] = recs[lslot(t >> 2, t & 3)];
 }
 
-template <bool IS_W, int P, bool NEXT>
-void launch_mc_defer(const McArgs &a, hipStream_t s)
-{
-	if (a.lpay2) {   // every x 1: 8-B payloads
-		dispatch_shape(a.avg_len, [&](auto B, auto R) {
-			k_mc_lord_defer<B(), R(), IS_W, P, NEXT, true><<<a.nfeat, B(), 0, s>>>(a);
-		});
-		return;
-	}
-	dispatch_shape(a.avg_len, [&](auto B, auto R) {
-		k_mc_lord_defer<B(), R(), IS_W, P, NEXT, false><<<a.nfeat, B(), 0, s>>>(a);
-	});
-}
-
-template <int BLOCK, int R, int MODE, bool ENT>
-void launch_mc_lord_ent(const McArgs &a, int is_w, hipStream_t s)
-{
-	const bool nx = a.par_next != nullptr;
-	if (is_w) {
-		if (nx) k_mc_level_lord<BLOCK, R, true, 0, true, MODE, ENT><<<a.nfeat, BLOCK, 0, s>>>(a);
-		else k_mc_level_lord<BLOCK, R, true, 0, false, MODE, ENT><<<a.nfeat, BLOCK, 0, s>>>(a);
-	} else if (a.slot == 0) {
-		if (nx) k_mc_level_lord<BLOCK, R, false, 0, true, MODE, ENT><<<a.nfeat, BLOCK, 0, s>>>(a);
-		else k_mc_level_lord<BLOCK, R, false, 0, false, MODE, ENT><<<a.nfeat, BLOCK, 0, s>>>(a);
-	} else {
-		if (nx) k_mc_level_lord<BLOCK, R, false, 1, true, MODE, ENT><<<a.nfeat, BLOCK, 0, s>>>(a);
-		else k_mc_level_lord<BLOCK, R, false, 1, false, MODE, ENT><<<a.nfeat, BLOCK, 0, s>>>(a);
-	}
-}
-
-// every mode on both stores: the entry store's next slots carry the row's-first-entry flag in
-// bit 31 (ENT_FIRST), which only the ENT kernels strip before the move
-template <int BLOCK, int R, int MODE>
-void launch_mc_lord(const McArgs &a, int is_w, hipStream_t s)
-{
-	if (a.ent) return launch_mc_lord_ent<BLOCK, R, MODE, true>(a, is_w, s);
-	launch_mc_lord_ent<BLOCK, R, MODE, false>(a, is_w, s);
-}
-
-template <int MODE>
-void launch_mc_lord_shape(const McArgs &a, int is_w, hipStream_t s)
-{
-	// the column-gather MCMC kernel's BLOCK (vbfm_mcmc.hip launch_level), records per thread
-	// as the VB level kernel
-	dispatch_shape(a.avg_len, [&](auto B, auto R) { launch_mc_lord<B(), R(), MODE>(a, is_w, s); });
-}
-
 }  // namespace
 
 namespace vbk {
@@ -1267,115 +1147,130 @@ namespace vbk {
 hipError_t mc_lord_level(const McArgs &a, int mode, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	if (mode == 0) launch_mc_lord_shape<0>(a, is_w, s);
-	else if (mode == 1) launch_mc_lord_shape<1>(a, is_w, s);
-	else launch_mc_lord_shape<2>(a, is_w, s);
+	// the column-gather MCMC kernel's BLOCK (vbfm_mcmc.hip mc_level), records per thread as the VB
+	// level kernel. Every mode on both stores: the entry store's next slots carry the
+	// row's-first-entry flag in bit 31 (ENT_FIRST), which only the ENT kernels strip before the move
+	dispatch_sweep(is_w, a.slot, a.par_next != nullptr, [&](auto W, auto P, auto N) {
+		dispatch_mode(mode, [&](auto M) {
+			dispatch_bool(a.ent, [&](auto E) {
+				dispatch_shape(a.avg_len, [&](auto B, auto R) {
+					k_mc_level_lord<B(), R(), W(), P(), N(), M(), E()><<<a.nfeat, B(), 0, s>>>(a);
+				});
+			});
+		});
+	});
 	return hipGetLastError();
 }
 
 hipError_t mc_lord_defer_level(const McArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	const bool nx = a.par_next != nullptr;
-	if (is_w) nx ? launch_mc_defer<true, 0, true>(a, s) : launch_mc_defer<true, 0, false>(a, s);
-	else if (a.slot == 0) nx ? launch_mc_defer<false, 0, true>(a, s) : launch_mc_defer<false, 0, false>(a, s);
-	else nx ? launch_mc_defer<false, 1, true>(a, s) : launch_mc_defer<false, 1, false>(a, s);
+	dispatch_sweep(is_w, a.slot, a.par_next != nullptr, [&](auto W, auto P, auto N) {
+		dispatch_bool(a.lpay2 != nullptr, [&](auto PAY8) {   // every x 1: 8-B payloads
+			dispatch_shape(a.avg_len, [&](auto B, auto R) {
+				k_mc_lord_defer<B(), R(), W(), P(), N(), PAY8()><<<a.nfeat, B(), 0, s>>>(a);
+			});
+		});
+	});
 	return hipGetLastError();
 }
 
 hipError_t mc_lord_defer_post(const McArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	const unsigned g = (a.nfeat + 255) / 256;
-	if (is_w) k_mc_lord_defer_post<true><<<g, 256, 0, s>>>(a);
-	else k_mc_lord_defer_post<false><<<g, 256, 0, s>>>(a);
+	dispatch_bool(is_w, [&](auto W) { k_mc_lord_defer_post<W()><<<(a.nfeat + 255) / 256, 256, 0, s>>>(a); });
 	return hipGetLastError();
 }
 
 hipError_t mc_lord_defer_flush(const McArgs &a, int is_w, uint32_t n, hipStream_t s)
 {
 	if (n == 0) return hipSuccess;
-	const unsigned g = (n + 255) / 256;
-	if (is_w) k_mc_lord_defer_flush<true, 0><<<g, 256, 0, s>>>(a, n);
-	else if (a.slot == 0) k_mc_lord_defer_flush<false, 0><<<g, 256, 0, s>>>(a, n);
-	else k_mc_lord_defer_flush<false, 1><<<g, 256, 0, s>>>(a, n);
+	dispatch_wp(is_w, a.slot, [&](auto W, auto P) { k_mc_lord_defer_flush<W(), P()><<<(n + 255) / 256, 256, 0, s>>>(a, n); });
 	return hipGetLastError();
 }
 
 hipError_t lord_level(const LevelArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	const bool nx = a.ms_next != nullptr;
-	if (is_w) nx ? launch_lord<true, 0, true>(a, s) : launch_lord<true, 0, false>(a, s);
-	else if (a.slot == 0) nx ? launch_lord<false, 0, true>(a, s) : launch_lord<false, 0, false>(a, s);
-	else nx ? launch_lord<false, 1, true>(a, s) : launch_lord<false, 1, false>(a, s);
+	const LordLead L = lord_lead(a);
+	dispatch_sweep(is_w, a.slot, a.ms_next != nullptr, [&](auto W, auto P, auto N) {
+		dispatch_bool(a.ent, [&](auto E) {
+			dispatch_shape(a.avg_len, [&](auto B, auto R) {
+				k_level_lord<B(), R(), W(), P(), N(), E()><<<a.nfeat, B(), 0, s>>>(LORD_LEAD_ARGS(L), a);
+			});
+		});
+	});
 	return hipGetLastError();
 }
 
 hipError_t lord_long(const LevelArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nsegs == 0) return hipSuccess;
-	const bool nx = a.ms_next != nullptr;
-	if (is_w) k_lord_long_stats<true, 0><<<a.nsegs, LONG_BLOCK, 0, s>>>(a);
-	else if (a.slot == 0) k_lord_long_stats<false, 0><<<a.nsegs, LONG_BLOCK, 0, s>>>(a);
-	else k_lord_long_stats<false, 1><<<a.nsegs, LONG_BLOCK, 0, s>>>(a);
-	if (is_w) {
-		if (nx) k_lord_long_move<true, 0, true><<<a.nsegs, LONG_BLOCK, 0, s>>>(a);
-		else k_lord_long_move<true, 0, false><<<a.nsegs, LONG_BLOCK, 0, s>>>(a);
-	} else if (a.slot == 0) {
-		if (nx) k_lord_long_move<false, 0, true><<<a.nsegs, LONG_BLOCK, 0, s>>>(a);
-		else k_lord_long_move<false, 0, false><<<a.nsegs, LONG_BLOCK, 0, s>>>(a);
-	} else {
-		if (nx) k_lord_long_move<false, 1, true><<<a.nsegs, LONG_BLOCK, 0, s>>>(a);
-		else k_lord_long_move<false, 1, false><<<a.nsegs, LONG_BLOCK, 0, s>>>(a);
-	}
+	dispatch_wp(is_w, a.slot, [&](auto W, auto P) {
+		k_lord_long_stats<W(), P()><<<a.nsegs, LONG_BLOCK, 0, s>>>(a);
+		dispatch_bool(a.ms_next != nullptr, [&](auto N) { k_lord_long_move<W(), P(), N()><<<a.nsegs, LONG_BLOCK, 0, s>>>(a); });
+	});
 	return hipGetLastError();
 }
 
 hipError_t lord_level_stats(const LevelArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	if (is_w) launch_lord_stats<true, 0>(a, s);
-	else if (a.slot == 0) launch_lord_stats<false, 0>(a, s);
-	else launch_lord_stats<false, 1>(a, s);
+	dispatch_wp(is_w, a.slot, [&](auto W, auto P) {
+		dispatch_shape(a.avg_len, [&](auto B, auto R) { k_level_lord_stats<B(), R(), W(), P()><<<a.nfeat, B(), 0, s>>>(a); });
+	});
 	return hipGetLastError();
 }
 
 hipError_t lord_level_move(const LevelArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	if (is_w) launch_lord_move<true, 0>(a, s);
-	else if (a.slot == 0) launch_lord_move<false, 0>(a, s);
-	else launch_lord_move<false, 1>(a, s);
+	dispatch_sweep(is_w, a.slot, a.ms_next != nullptr, [&](auto W, auto P, auto N) {
+		dispatch_bool(a.ent, [&](auto E) {
+			dispatch_shape(a.avg_len, [&](auto B, auto R) {
+				k_level_lord_move<B(), R(), W(), P(), N(), E()><<<a.nfeat, B(), 0, s>>>(a);
+			});
+		});
+	});
 	return hipGetLastError();
 }
 
 hipError_t lord_defer_level(const LevelArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	const bool nx = a.ms_next != nullptr;
-	if (is_w) nx ? launch_defer<true, 0, true>(a, s) : launch_defer<true, 0, false>(a, s);
-	else if (a.slot == 0) nx ? launch_defer<false, 0, true>(a, s) : launch_defer<false, 0, false>(a, s);
-	else nx ? launch_defer<false, 1, true>(a, s) : launch_defer<false, 1, false>(a, s);
+	const auto launch = [&](auto W, auto P, auto N, auto PK) {
+		dispatch_bool(a.ent, [&](auto E) {
+			dispatch_bool(a.lpay2 != nullptr, [&](auto PAY8) {   // every x 1: 8-B payloads
+				dispatch_shape(a.avg_len, [&](auto B, auto R) {
+					k_lord_defer<B(), R(), W(), P(), N(), PK(), PAY8(), E()><<<a.nfeat, B(), 0, s>>>(a);
+				});
+			});
+		});
+	};
+	dispatch_sweep(is_w, a.slot, a.ms_next != nullptr, [&](auto W, auto P, auto N) {
+		// only a v sweep can carry the previous sweep's last correction (pend_kind 1 or 2)
+		if constexpr (W()) launch(W, P, N, std::integral_constant<int, 0>());
+		else dispatch_mode(a.pend_kind, [&](auto PK) { launch(W, P, N, PK); });
+	});
 	return hipGetLastError();
 }
 
 hipError_t lord_defer_post(const LevelArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	const unsigned g = (a.nfeat + 255) / 256;
-	if (is_w) { if (a.ms_next) k_lord_defer_post<true, true><<<g, 256, 0, s>>>(a); else k_lord_defer_post<true, false><<<g, 256, 0, s>>>(a); }
-	else { if (a.ms_next) k_lord_defer_post<false, true><<<g, 256, 0, s>>>(a); else k_lord_defer_post<false, false><<<g, 256, 0, s>>>(a); }
+	dispatch_bool(is_w, [&](auto W) {
+		dispatch_bool(a.ms_next != nullptr, [&](auto N) { k_lord_defer_post<W(), N()><<<(a.nfeat + 255) / 256, 256, 0, s>>>(a); });
+	});
 	return hipGetLastError();
 }
 
 hipError_t lord_defer_flush(const LevelArgs &a, int is_w, uint32_t n, hipStream_t s)
 {
 	if (n == 0) return hipSuccess;
-	const bool nx = a.ms_next != nullptr;
-	if (is_w) nx ? launch_flush<true, 0, true>(a, n, s) : launch_flush<true, 0, false>(a, n, s);
-	else if (a.slot == 0) nx ? launch_flush<false, 0, true>(a, n, s) : launch_flush<false, 0, false>(a, n, s);
-	else nx ? launch_flush<false, 1, true>(a, n, s) : launch_flush<false, 1, false>(a, n, s);
+	dispatch_sweep(is_w, a.slot, a.ms_next != nullptr, [&](auto W, auto P, auto N) {
+		if (a.ent) k_lord_defer_flush_ent<W(), P()><<<(n + 255) / 256, 256, 0, s>>>(a, n);
+		else k_lord_defer_flush<W(), P(), N()><<<(n + 255) / 256, 256, 0, s>>>(a, n);
+	});
 	return hipGetLastError();
 }
 

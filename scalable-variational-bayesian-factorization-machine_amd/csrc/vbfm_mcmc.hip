@@ -373,43 +373,19 @@ inline unsigned grid_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
 namespace vbk {
 
-template <int BLOCK, int MODE>
-static void launch_v(const McArgs &a, hipStream_t s)
-{
-	const bool nx = a.par_next != nullptr;
-	if (a.slot == 0) {
-		if (nx) k_mc_v_level<BLOCK, 0, true, MODE><<<a.nfeat, BLOCK, 0, s>>>(a);
-		else k_mc_v_level<BLOCK, 0, false, MODE><<<a.nfeat, BLOCK, 0, s>>>(a);
-	} else {
-		if (nx) k_mc_v_level<BLOCK, 1, true, MODE><<<a.nfeat, BLOCK, 0, s>>>(a);
-		else k_mc_v_level<BLOCK, 1, false, MODE><<<a.nfeat, BLOCK, 0, s>>>(a);
-	}
-}
-
-template <int BLOCK, int MODE>
-static void launch_w(const McArgs &a, hipStream_t s)
-{
-	if (a.par_next) k_mc_w_level<BLOCK, true, MODE><<<a.nfeat, BLOCK, 0, s>>>(a);
-	else k_mc_w_level<BLOCK, false, MODE><<<a.nfeat, BLOCK, 0, s>>>(a);
-}
-
 // threads per column from the level's mean column length (the VB kernels' shapes; the
 // level-ordered MCMC kernel uses the same BLOCK, so both reduce a column in one order)
-template <int MODE>
-static void launch_level(const McArgs &a, bool is_w, hipStream_t s)
-{
-	dispatch_shape(a.avg_len, [&](auto B, auto) {
-		if (is_w) launch_w<B(), MODE>(a, s);
-		else launch_v<B(), MODE>(a, s);
-	});
-}
-
 static hipError_t mc_level(const McArgs &a, int mode, bool is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	if (mode == 0) launch_level<0>(a, is_w, s);
-	else if (mode == 1) launch_level<1>(a, is_w, s);
-	else launch_level<2>(a, is_w, s);
+	dispatch_sweep(is_w, a.slot, a.par_next != nullptr, [&](auto W, auto P, auto N) {
+		dispatch_mode(mode, [&](auto M) {
+			dispatch_shape(a.avg_len, [&](auto B, auto) {
+				if constexpr (W()) k_mc_w_level<B(), N(), M()><<<a.nfeat, B(), 0, s>>>(a);
+				else k_mc_v_level<B(), P(), N(), M()><<<a.nfeat, B(), 0, s>>>(a);
+			});
+		});
+	});
 	return hipGetLastError();
 }
 

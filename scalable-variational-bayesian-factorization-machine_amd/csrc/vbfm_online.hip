@@ -777,37 +777,11 @@ template <int G>
 hipError_t launch_ov(const LevelArgs &a, int is_w, hipStream_t s)
 {
 	const unsigned grid = G <= 64 ? (a.nfeat + 256 / G - 1) / (256 / G) : a.nfeat;
-	const bool nx = a.ms_next != nullptr;
-	if (is_w) {
-		if (nx) k_ov_w_level<G, true><<<grid, 256, 0, s>>>(a);
-		else k_ov_w_level<G, false><<<grid, 256, 0, s>>>(a);
-	} else if (a.slot == 0) {
-		if (nx) k_ov_v_level<G, 0, true><<<grid, 256, 0, s>>>(a);
-		else k_ov_v_level<G, 0, false><<<grid, 256, 0, s>>>(a);
-	} else {
-		if (nx) k_ov_v_level<G, 1, true><<<grid, 256, 0, s>>>(a);
-		else k_ov_v_level<G, 1, false><<<grid, 256, 0, s>>>(a);
-	}
+	dispatch_sweep(is_w, a.slot, a.ms_next != nullptr, [&](auto W, auto P, auto N) {
+		if constexpr (W()) k_ov_w_level<G, N()><<<grid, 256, 0, s>>>(a);
+		else k_ov_v_level<G, P(), N()><<<grid, 256, 0, s>>>(a);
+	});
 	return hipGetLastError();
-}
-
-template <int G, bool PAD>
-void launch_ov_lord_pad(const LevelArgs &a, int is_w, hipStream_t s)
-{
-	const unsigned grid = (a.nfeat + 256 / G - 1) / (256 / G);
-	const bool nx = a.ms_next != nullptr;
-#define OV_LORD_ARGS a.col_ptr, a.src, a.lnext, a.ms, a.nat, a.rho, a.ccount, a.nfeat, a
-	if (is_w) {
-		if (nx) k_ov_lord<G, true, 0, true, PAD, false><<<grid, 256, 0, s>>>(OV_LORD_ARGS);
-		else k_ov_lord<G, true, 0, false, PAD, false><<<grid, 256, 0, s>>>(OV_LORD_ARGS);
-	} else if (a.slot == 0) {
-		if (nx) k_ov_lord<G, false, 0, true, PAD, false><<<grid, 256, 0, s>>>(OV_LORD_ARGS);
-		else k_ov_lord<G, false, 0, false, PAD, false><<<grid, 256, 0, s>>>(OV_LORD_ARGS);
-	} else {
-		if (nx) k_ov_lord<G, false, 1, true, PAD, false><<<grid, 256, 0, s>>>(OV_LORD_ARGS);
-		else k_ov_lord<G, false, 1, false, PAD, false><<<grid, 256, 0, s>>>(OV_LORD_ARGS);
-	}
-#undef OV_LORD_ARGS
 }
 
 // the tagged-argument form of a v sweep's padded level (k_ov_lord FAST): field data (the level's
@@ -832,26 +806,24 @@ bool launch_ov_lord_fast(const LevelArgs &a, int is_w, hipStream_t s)
 	double *rho = a.rho + a.feat_base;
 	const uint32_t *cc = a.ccount + a.feat_base;
 	const unsigned grid = (a.nfeat + 256 / G - 1) / (256 / G);
-#define OV_FAST_ARGS cp, sr, ln, ms, nat, rho, cc, a.nfeat, a
-	if (a.slot == 0) {
-		if (a.ms_next) k_ov_lord<G, false, 0, true, true, true><<<grid, 256, 0, s>>>(OV_FAST_ARGS);
-		else k_ov_lord<G, false, 0, false, true, true><<<grid, 256, 0, s>>>(OV_FAST_ARGS);
-	} else {
-		if (a.ms_next) k_ov_lord<G, false, 1, true, true, true><<<grid, 256, 0, s>>>(OV_FAST_ARGS);
-		else k_ov_lord<G, false, 1, false, true, true><<<grid, 256, 0, s>>>(OV_FAST_ARGS);
-	}
-#undef OV_FAST_ARGS
+	dispatch_sweep(false, a.slot, a.ms_next != nullptr, [&](auto, auto P, auto N) {
+		k_ov_lord<G, false, P(), N(), true, true><<<grid, 256, 0, s>>>(cp, sr, ln, ms, nat, rho, cc, a.nfeat, a);
+	});
 	return true;
 }
 
+// the padded level in its tagged form where that applies, else the plain form (padded or not)
 template <int G>
 hipError_t launch_ov_lord(const LevelArgs &a, int is_w, hipStream_t s)
 {
-	if (a.pad_cap) {
-		if (!launch_ov_lord_fast<G>(a, is_w, s)) launch_ov_lord_pad<G, true>(a, is_w, s);
-	} else {
-		launch_ov_lord_pad<G, false>(a, is_w, s);
-	}
+	if (launch_ov_lord_fast<G>(a, is_w, s)) return hipGetLastError();
+	const unsigned grid = (a.nfeat + 256 / G - 1) / (256 / G);
+	dispatch_sweep(is_w, a.slot, a.ms_next != nullptr, [&](auto W, auto P, auto N) {
+		dispatch_bool(a.pad_cap != 0, [&](auto PAD) {
+			k_ov_lord<G, W(), P(), N(), PAD(), false><<<grid, 256, 0, s>>>(a.col_ptr, a.src, a.lnext, a.ms, a.nat, a.rho,
+			                                                               a.ccount, a.nfeat, a);
+		});
+	});
 	return hipGetLastError();
 }
 

@@ -10,12 +10,17 @@ column's statistics are reduced in a fixed tree order on the device and sequenti
 reference; the q-cache a factor's sweep starts from is a per-row sum in the reference's order
 and stays bit-exact. tests/test_oracle_golden.py checks that the reference's level-by-level
 sweep ends bit for bit where its ascending sweep ends.
+
+The few-factor tests run whole iterations with k = 0..3 against the CPU oracle
+(tests/oracle_ctypes.py) at the same tolerance: the kernel variants "no next factor" and "slot 1
+without a next factor" are launched only when k < 3.
 """
 import os
 
 import numpy as np
 import pytest
 
+import oracle_ctypes as oc
 import synth
 import vbfm
 from conftest import GOLDEN, load_case
@@ -149,6 +154,110 @@ def test_level_stores_mid_sweep_equal_column_layout(layout):
     for i, (a, b) in enumerate(zip(res["column"], res[layout])):
         for key in a:
             np.testing.assert_array_equal(a[key], b[key], err_msg="%d %s" % (i, key))
+
+
+# ---- few factors: every sweep variant the launch layer can choose ---------------------------
+# With k = 3 a run never sweeps w without a next factor, slot 0 without a next factor as the only
+# factor, or slot 1 without a next factor (k = 0, 1, 2). Small field data, two iterations.
+FEW_N, FEW_F, FEW_S, FEW_NT, FEW_ITERS = 2000, 5, 150, 200, 2
+FEW_KEYS = ("e", "t", "q", "tq", "tz", "mu_w", "mu_v", "free_energy")
+_few_cache = {}
+
+
+def _few_data(long_column):
+    """synth.generate(2000, 5, 150) with a 200-row test set; long_column: every third row takes
+    the same id of field 2, a column of ~670 entries among columns of ~13."""
+    key = ("data", long_column)
+    if key not in _few_cache:
+        rp, f, v, y = synth.generate(FEW_N, FEW_F, FEW_S, 71, 1)
+        te = synth.generate(FEW_NT, FEW_F, FEW_S, 72, 1)
+        if long_column:
+            f = f.copy()
+            f[2::3 * FEW_F] = 2 * FEW_S + 7
+            assert np.bincount(f).max() > 2 * 256
+        _few_cache[key] = ((rp, f, v, y), te)
+    return _few_cache[key]
+
+
+def _few_oracle(k, long_column=False):
+    """The CPU oracle's state after FEW_ITERS iterations, computed once per k."""
+    key = ("oracle", k, long_column)
+    if key not in _few_cache:
+        (rp, f, v, y), (rpt, ft, vt, yt) = _few_data(long_column)
+        o = oc.VB(1, 1, k, FEW_F * FEW_S + 1)
+        o.init_params(5, 0.1)
+        o.attach(oc.Data(csr=(FEW_N, rp, f, v, y)), oc.Data(csr=(FEW_NT, rpt, ft, vt, yt)))
+        o.init_caches()
+        fe = []
+        for _ in range(FEW_ITERS):
+            o.iterate()
+            fe.append(o.s.last_free_energy)
+        r, p = o.rows(), o.params()
+        _few_cache[key] = dict(r, mu_w=p["mu_w"], mu_v=p["mu_v"], free_energy=np.asarray(fe))
+    return _few_cache[key]
+
+
+def _few_run(k, layout, env, monkeypatch, long_column=False):
+    for name in ("VBFM_FORCE_SPLIT", "VBFM_DEFER", "VBFM_SEG_MIN", "VBFM_SEG_LEN"):
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    (rp, f, v, y), (rpt, ft, vt, yt) = _few_data(long_column)
+    nf = FEW_F * FEW_S
+    g = vbfm.FMLearnVB(1, 1, k, nf + 1, min_target=float(y.min()), max_target=float(y.max()), layout=layout)
+    g.init(5, 0.1)
+    g.set_data(vbfm.DataSubset.from_csr(rp, f, v, y, nf), vbfm.DataSubset.from_csr(rpt, ft, vt, yt, nf))
+    g.init_caches()
+    assert g.layout() == layout
+    fe = [g.iterate().free_energy for _ in range(FEW_ITERS)]
+    r, p = g.rows(), g.get_params()
+    g.close()
+    return dict(r, mu_w=np.asarray(p["mu_w"]), mu_v=np.asarray(p["mu_v"]), free_energy=np.asarray(fe))
+
+
+def _few_close(res, ref, k, what):
+    for key in FEW_KEYS:
+        if k == 0 and key in ("q", "tq", "tz"):
+            continue   # no factor: no q-cache
+        print(what, key, rel_err(res[key], ref[key]))
+        close(res[key], ref[key], (what, key))
+
+
+def _few_forms(layout):
+    """The sweep's three forms on one rank. The deferred split is the field store's default under
+    row shards and opt-in (VBFM_DEFER=1) on the entry store."""
+    deferred = {"VBFM_FORCE_SPLIT": "1", "VBFM_DEFER": "1"} if layout == "entry" else {"VBFM_FORCE_SPLIT": "1"}
+    return (("fused", {"VBFM_FORCE_SPLIT": "0"}), ("two-pass", {"VBFM_FORCE_SPLIT": "1", "VBFM_DEFER": "0"}),
+            ("deferred", deferred))
+
+
+@pytest.mark.parametrize("layout", ["level", "column", "entry"])
+@pytest.mark.parametrize("k", [0, 1, 2, 3])
+def test_few_factors_vs_oracle(k, layout, monkeypatch):
+    """VB with k = 0 (the w sweep without a next factor), 1 (slot 0 without next), 2 (slot 1 without
+    next) and 3, on every layout, fused and in both split forms: e, t, the last factor's q-cache,
+    mu_w, mu_v and the free energy of two iterations against the CPU oracle (1e-12: tree against
+    sequential column sums). On the field store the three forms are bit-identical."""
+    ref = _few_oracle(k)
+    res = {}
+    for form, env in _few_forms(layout):
+        res[form] = _few_run(k, layout, env, monkeypatch)
+        _few_close(res[form], ref, k, (k, layout, form))
+    if layout == "level":
+        for form in ("two-pass", "deferred"):
+            for key in FEW_KEYS:
+                np.testing.assert_array_equal(res[form][key], res["fused"][key], err_msg="%s %s" % (form, key))
+
+
+@pytest.mark.parametrize("layout", ["level", "column"])
+@pytest.mark.parametrize("k", [1, 2])
+def test_few_factors_long_column(k, layout, monkeypatch):
+    """One column cut into segments (VBFM_SEG_MIN / VBFM_SEG_LEN of 256: three segments, the last
+    one partial): the segment kernels of both layouts without a next factor (k = 1) and on slot 1
+    (k = 2), against the CPU oracle."""
+    env = {"VBFM_FORCE_SPLIT": "0", "VBFM_SEG_MIN": "256", "VBFM_SEG_LEN": "256"}
+    res = _few_run(k, layout, env, monkeypatch, long_column=True)
+    _few_close(res, _few_oracle(k, long_column=True), k, (k, layout, "segments"))
 
 
 def test_per_level_steps_refuse_misuse(monkeypatch):

@@ -45,9 +45,9 @@ def case_files(case, synth_files, sa_split):
     return os.path.join(d, "train.libfm"), os.path.join(d, "test.libfm")
 
 
-def make_learner(case, synth_files, sa_split, replay=False, batch=None):
+def make_learner(case, synth_files, sa_split, replay=False, batch=None, dim=None):
     t, a = load_case(case)
-    m = t["meta"]
+    m = dict(t["meta"], dim=dim) if dim else t["meta"]
     trp, tep = case_files(case, synth_files, sa_split)
     train, test = vbfm.DataSubset.load(trp), vbfm.DataSubset.load(tep)
     k0, k1, k = [int(x) for x in m["dim"].split(",")]
@@ -97,9 +97,13 @@ def test_online_trace_vs_reference(case, layout, synth_files, sa_split, monkeypa
         close(st.rmse, ref["rmse"], what=("rmse", it))
         fe = [st.free_energy_first] if m["batch"] == 1 else [st.free_energy_first, st.free_energy_last]
         close(fe, ref["free_energy"], what=("free energy", it))
-    p, s = fml.get_params(), fml.online_state()
     o, _, keep = oracle_run(trp, tep, groups, D, m, len(t["trace"]))
-    op = o.params()
+    check_final(fml, a, o.params())
+
+
+def check_final(fml, a, op):
+    """The learner's final state against the reference's dumps (a) where they exist, else the oracle's."""
+    p, s = fml.get_params(), fml.online_state()
     for key in ("mu_w", "sigma_w", "mu_v", "sigma_v", "hyp_sigma_w", "hyp_sigma_v"):
         ref = a["final_" + key] if "final_" + key in a else op[key]
         close(p[key], ref, what=key)
@@ -109,6 +113,35 @@ def test_online_trace_vs_reference(case, layout, synth_files, sa_split, monkeypa
     close(np.concatenate([s["new_wj"], s["new_vj"]]), a.get("final_steps", op["steps"]), what="steps")
     close(s["scalars"], a.get("final_scalars", op["scalars"]), what="scalars")
     close(fml.predict(), a.get("final_pred", op["pred"]), what="pred")
+
+
+_few_oracle = {}
+
+
+@pytest.mark.parametrize("layout", ["auto", "column"])
+@pytest.mark.parametrize("k", [1, 2, 3])
+@pytest.mark.parametrize("case", ["tiny/online_b3", "synth_online"])
+def test_online_few_factors_vs_oracle(case, k, layout, synth_files, sa_split, monkeypatch):
+    """k = 1 (slot 0 without a next factor), 2 (slot 1 without next) and 3 with the per-batch store
+    on (auto; synth_online's batches always take it) and off (column): every epoch's test RMSE and
+    free energies and the final state against the oracle, which is computed once per case and k."""
+    monkeypatch.setenv("VBFM_LAYOUT", layout)
+    t, _, fml, (trp, tep, groups, D) = make_learner(case, synth_files, sa_split, dim="1,1,%d" % k)
+    m = dict(t["meta"], dim="1,1,%d" % k)
+    if (case, k) not in _few_oracle:
+        o, out, keep = oracle_run(trp, tep, groups, D, m, len(t["trace"]))
+        _few_oracle[case, k] = (out, o.params())
+    out, op = _few_oracle[case, k]
+    for it, (rmse, _, fe_first, fe_last) in enumerate(out):
+        st = fml.epoch()
+        if layout == "column":
+            assert st.n_lord_batches == 0
+        elif case in COMPLETE:
+            assert st.n_lord_batches == st.num_batch, st.n_lord_batches
+        close(st.rmse, rmse, what=("rmse", it))
+        close([st.free_energy_first, st.free_energy_last], [fe_first, fe_last], what=("free energy", it))
+    check_final(fml, {}, op)
+    fml.close()
 
 
 def test_online_replay_init_is_host_init(synth_files, sa_split):
