@@ -1,6 +1,8 @@
 // vbfm_ctx.h -- the learner context behind include/vbfm.h and the host-side helpers its
-// two front ends share: the VB learner (vbfm_capi.hip) and the MCMC / ALS learner
-// (vbfm_mcmc_capi.hip). Internal to libvbfm; not part of the ABI.
+// front ends share: the VB learner (vbfm_capi.hip), the MCMC / ALS learner (vbfm_mcmc_capi.hip)
+// and the online learner (vbfm_online.hip), over the exchange (vbfm_comm.hip), the schedule
+// (vbfm_schedule.hip), the row stores (vbfm_store.hip), checkpoints (vbfm_ckpt.hip) and the
+// synthetic data (vbfm_synth.hip). Internal to libvbfm; not part of the ABI.
 #pragma once
 #include "vbfm_device.h"
 #include "../../include/vbfm.h"
@@ -46,12 +48,6 @@ struct HipError {
 		if (_e != hipSuccess) throw HipError{_e, #x};               \
 	} while (0)
 
-#define NCCLCHK(x)                                                  \
-	do {                                                            \
-		ncclResult_t _r = (x);                                      \
-		if (_r != ncclSuccess) throw std::string("RCCL: ") + ncclGetErrorString(_r) + " in " #x; \
-	} while (0)
-
 template <class T> inline T *dalloc(size_t n)
 {
 	void *p = nullptr;
@@ -65,11 +61,14 @@ template <class T> inline void dfree(T *&p)
 	p = nullptr;
 }
 
-// a device buffer freed when its scope ends, normally or by an exception (dfree(buf.p) frees it early)
+// a device buffer freed when its scope ends, normally or by an exception (dfree(buf.p) frees it
+// early; a default-constructed one adopts whatever is put into p); it passes for its pointer
 template <class T> struct DevScratch {
 	T *p = nullptr;
+	DevScratch() = default;
 	explicit DevScratch(size_t n) : p(dalloc<T>(n)) {}
 	~DevScratch() { dfree(p); }
+	operator T *() const { return p; }
 	DevScratch(const DevScratch &) = delete;
 	DevScratch &operator=(const DevScratch &) = delete;
 };
@@ -82,12 +81,16 @@ inline double wall_s()
 	return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-// the deferred MCMC / ALS split kernel's record stores non-temporal (VBFM_DEFER_NT bit 1, default
-// on; its loads always are), as the VB one's (vbfm_capi.hip defer_nt)
-inline bool defer_nt_stores()
+// Non-temporal record traffic of the deferred split kernels: VBFM_DEFER_NT=0..3 (bit 0 loads, bit 1
+// stores; LevelArgs::pending carries them as 2 and 4). Default both: the moved records then leave
+// more of L2 to the posterior table the next level gathers from (one N = 8 rank's shape, 1.25e7
+// rows: 426-427 -> 415-417 us per split level, profiles/r05_split/; alone, either half gained
+// 0-1.5 %, profiles/probes/ab_defer_loads.txt, ab_defer_nt_store.txt). The MCMC / ALS kernel takes
+// the store bit only (its loads always are non-temporal)
+inline int defer_nt_bits()
 {
 	const char *e = getenv("VBFM_DEFER_NT");
-	return ((e ? atoi(e) : 3) & 2) != 0;
+	return (e ? atoi(e) : 3) & 3;
 }
 
 // test hook: VBFM_FAULT=<where> makes the named step throw as a failed HIP call would (the error
@@ -120,12 +123,6 @@ struct vbfm_ctx {
 	int dev = 0;
 	hipStream_t s = nullptr;
 	hipStream_t s_test = nullptr;   // the test prediction, overlapping the hyper-parameter step
-	// row shards over RCCL: the per-level all-reduce of chunk i of a level's statistics runs on
-	// s_comm while chunk i+1 computes on s (stats_exchange); events order the two
-	hipStream_t s_comm = nullptr;
-	static constexpr int AR_MAX_CHUNKS = 8;
-	hipEvent_t ev_ar[AR_MAX_CHUNKS] = {};
-	hipEvent_t ev_arj = nullptr;
 	int k0 = 1, k1 = 1, k = 0;
 	uint32_t D = 0, G = 1;
 	std::vector<uint32_t> group_h, per_group;
@@ -148,16 +145,19 @@ struct vbfm_ctx {
 	// a sweep driven level by level (vbfm_step_w_level / vbfm_step_v_level): kind -1 none, 0 the
 	// w sweep, 1 the v sweep of factor part_f; part_next = the level expected next
 	int part_kind = -1, part_f = 0;
-	std::vector<float> place_ms;    // tune_placement: each candidate buffer's score (ms), [0], [1] = the first pair
-	int place_pick[2] = {-1, -1};   // ... and the two kept (records, alternate)
-	std::vector<float> place_pair_ms;   // ... the best few scored as pairs (a < b in score order)
+	uint32_t part_next = 0;
+	// the placement search of the store's record buffers (tune_placement, vbfm_store.hip)
+	struct Place {
+		std::vector<float> ms;       // each candidate buffer's score (ms), [0], [1] = the first pair
+		int pick[2] = {-1, -1};      // ... and the two kept (records, alternate)
+		std::vector<float> pair_ms;  // ... the best few scored as pairs (a < b in score order)
+		int cands_cfg = 0;           // vbfm_config::place_candidates / place_budget_bytes (0: defaults)
+		uint64_t budget_cfg = 0;
+		uint64_t bytes = 0;          // device memory the last search held at its peak
+	} place;
 	int prefetch = -1;              // the level kernels touch the next level's column bounds (VBFM_PREFETCH; -1: not read yet)
-	int place_cands_cfg = 0;        // vbfm_config::place_candidates / place_budget_bytes (0: defaults)
-	uint64_t place_budget_cfg = 0;
-	uint64_t place_bytes = 0;       // device memory the last search held at its peak
 	// host wall seconds of the set-up steps (vbfm_setup_info)
 	double t_set_train = 0, t_schedule = 0, t_store = 0, t_place = 0;
-	uint32_t part_next = 0;
 	uint32_t *level_feats = nullptr;
 	uint8_t *dup = nullptr;
 	bool sched_ready = false;
@@ -175,84 +175,101 @@ struct vbfm_ctx {
 	double *vpart_d = nullptr;          // [chunks * k] factor partials
 	double *vseg_d = nullptr;           // [k * G] factor sums (inside chunk_out_d)
 	uint32_t *counters = nullptr;
-	// row-sharded multi-GPU
-	int nranks = 1, rank = 0;
 	bool force_split = false;      // VBFM_FORCE_SPLIT=1: the multi-rank kernels on one rank
 	int debug_skew = 0;            // VBFM_DEBUG_SKEW=1: late waves in the split forms' posterior kernels
-	ncclComm_t comm = nullptr;
-	// communicator health: RCCL runs non-blocking (its errors surface through
-	// ncclCommGetAsyncError), polled against a deadline wherever the host waits on work that holds a
-	// collective (comm_wait); a failure or a missed deadline aborts the communicator, and every
-	// later exchange refuses with the first message (comm_err)
-	double comm_timeout_s = 300.0;   // VBFM_COMM_TIMEOUT_S
-	bool comm_failed = false;
-	std::string comm_err;
-	// where the path is when it exchanges (the messages name it): a phase, the factor (-1: none)
-	// and the level (-1: not in a sweep)
-	const char *x_phase = "set-up";
-	int x_f = -1, x_l = -1;
-	std::string x_pending;           // the first exchange issued since the last completed wait (x_where)
-	vbfm_exchange_stats xs = {};     // this iteration's exchanges (vbfm_exchange_info)
-	uint32_t *stall_flag = nullptr;  // VBFM_FAULT=comm_stall: host flag that releases the stall kernel
-	bool stall_done = false;
+	static constexpr int AR_MAX_CHUNKS = 8;
+	// the exchange between ranks (vbfm_comm.hip; released by comm_free)
+	struct Net {
+		// row-sharded multi-GPU
+		int nranks = 1, rank = 0;
+		ncclComm_t comm = nullptr;
+		// row shards over RCCL: the per-level all-reduce of chunk i of a level's statistics runs on
+		// s_comm while chunk i+1 computes on s (stats_exchange); events order the two
+		hipStream_t s_comm = nullptr;
+		hipEvent_t ev_ar[AR_MAX_CHUNKS] = {};
+		hipEvent_t ev_arj = nullptr;
+		// communicator health: RCCL runs non-blocking (its errors surface through
+		// ncclCommGetAsyncError), polled against a deadline wherever the host waits on work that holds a
+		// collective (comm_wait); a failure or a missed deadline aborts the communicator, and every
+		// later exchange refuses with the first message (err)
+		double timeout_s = 300.0;   // VBFM_COMM_TIMEOUT_S
+		bool failed = false;
+		std::string err;
+		// where the path is when it exchanges (the messages name it): a phase, the factor (-1: none)
+		// and the level (-1: not in a sweep)
+		const char *x_phase = "set-up";
+		int x_f = -1, x_l = -1;
+		std::string x_pending;           // the first exchange issued since the last completed wait (x_where)
+		vbfm_exchange_stats xs = {};     // this iteration's exchanges (vbfm_exchange_info)
+		uint32_t *stall_flag = nullptr;  // VBFM_FAULT=comm_stall: host flag that releases the stall kernel
+		bool stall_done = false;
+		vbfm_exchange_fn xfn = nullptr; // vbfm_comm_init_host: all-reduces through the caller
+		void *xuser = nullptr;
+		std::vector<uint8_t> xbuf;      // host staging of a host-exchange all-reduce
+	} net;
 	double2 *stats = nullptr;
 	uint32_t stats_cap = 0;
 	uint64_t n_global = 0;
 	uint32_t test_n_global = 0;
 	hipEvent_t ev[vbi::EV_N] = {};
-	// per-launch profiling (vbfm_set_profiling)
-	bool profiling = false;
-	int prof_stride = 1;             // event pair around every prof_stride-th launch of a kind
-	uint64_t prof_tick[4] = {0, 0, 0, 0};
-	std::vector<hipEvent_t> pev;
-	size_t pev_used = 0;
-	struct Span { size_t a; int kind; };   // kind 0 = v level, 1 = w level, 2 = qcache, 3 = exchange
-	std::vector<Span> spans;
-	// level-ordered row store (vbfm_lorder.hip)
-	int layout_req = VBFM_LAYOUT_AUTO;
-	bool lord = false;             // built for the current train set and in use
-	bool estore = false;           // ... as the entry store (levels that miss rows: build_estore);
-	                               // lpos0 then holds each row's slot between sweeps, lrow0 is unused
-	bool rows_lorder = false;      // rows currently hold level-0 order (else row order)
-	RowRec *rows_alt = nullptr;    // second record buffer (each level moves rows -> rows_alt)
-	uint64_t *lcp = nullptr;       // [nf+1] global position of each level feature's run
-	float *lx = nullptr;           // [nnz] x per level-ordered entry
-	uint32_t *lnext = nullptr;     // [nnz] position of the entry's row in the next level
-	uint32_t *lrow0 = nullptr;     // [n] row at each level-0 position
-	uint32_t *lpos0 = nullptr;     // [n] level-0 position of each row
-	uint32_t *lpidx = nullptr;     // [nnz] split form: the row's previous-level feature (index in its level)
-	float *lpx = nullptr;          // [nnz] ... and its x (deferred correction)
-	uint2 *lpay2 = nullptr;        // [nnz] ... {lnext, lpidx} instead when every x is 1 (no lx)
-	uint4 *lpay = nullptr;         // [nnz] deferred split: {x, lnext, lpidx, lpx} of every entry in one
-	                               // 16-B load (lx / lnext / lpidx / lpx are freed once packed)
-	PostT *post_tab = nullptr;     // [max level width] posteriors of the last level swept
-	// long columns of the level store (fused single-rank sweep): segments of every level
-	uint32_t long_min = 0;         // nonzero: some level has long columns split into segments
-	std::vector<uint32_t> long_min_l;  // [L] each level's threshold (0: no segments in the level)
-	std::vector<uint32_t> seg_ptr; // [L+1] each level's segments in long_segs
-	LongSeg *long_segs = nullptr;
-	double2 *seg_part = nullptr;   // [2 * max segments of a level]
+	// per-launch profiling (vbfm_set_profiling; released by prof_free)
+	struct Prof {
+		bool on = false;
+		int stride = 1;                  // event pair around every stride-th launch of a kind
+		uint64_t tick[4] = {0, 0, 0, 0};
+		std::vector<hipEvent_t> pev;
+		size_t pev_used = 0;
+		struct Span { size_t a; int kind; };   // kind 0 = v level, 1 = w level, 2 = qcache, 3 = exchange
+		std::vector<Span> spans;
+	} prof;
+	// level-ordered row store (vbfm_store.hip, kernels in vbfm_lorder.hip; released by store_release)
+	struct Store {
+		int layout_req = VBFM_LAYOUT_AUTO;   // a request, not a build product: kept across a release
+		bool lord = false;             // built for the current train set and in use
+		bool estore = false;           // ... as the entry store (levels that miss rows: build_estore);
+		                               // lpos0 then holds each row's slot between sweeps, lrow0 is unused
+		bool rows_lorder = false;      // rows currently hold level-0 order (else row order)
+		RowRec *rows_alt = nullptr;    // second record buffer (each level moves rows -> rows_alt)
+		uint64_t *lcp = nullptr;       // [nf+1] global position of each level feature's run
+		float *lx = nullptr;           // [nnz] x per level-ordered entry
+		uint32_t *lnext = nullptr;     // [nnz] position of the entry's row in the next level
+		uint32_t *lrow0 = nullptr;     // [n] row at each level-0 position
+		uint32_t *lpos0 = nullptr;     // [n] level-0 position of each row
+		uint32_t *lpidx = nullptr;     // [nnz] split form: the row's previous-level feature (index in its level)
+		float *lpx = nullptr;          // [nnz] ... and its x (deferred correction)
+		uint2 *lpay2 = nullptr;        // [nnz] ... {lnext, lpidx} instead when every x is 1 (no lx)
+		uint4 *lpay = nullptr;         // [nnz] deferred split: {x, lnext, lpidx, lpx} of every entry in one
+		                               // 16-B load (lx / lnext / lpidx / lpx are freed once packed)
+		PostT *post_tab = nullptr;     // [max level width] posteriors of the last level swept
+		// long columns of the level store (fused single-rank sweep): segments of every level
+		uint32_t long_min = 0;         // nonzero: some level has long columns split into segments
+		std::vector<uint32_t> long_min_l;  // [L] each level's threshold (0: no segments in the level)
+		std::vector<uint32_t> seg_ptr; // [L+1] each level's segments in long_segs
+		LongSeg *long_segs = nullptr;
+		double2 *seg_part = nullptr;   // [2 * max segments of a level]
+	} store;
 	// deferred split across sweeps (vbfm_iterate only): the last level's correction of a sweep is
 	// left to level 0 of the next one instead of a flush pass. carry: 0 none, 1 / 2 = v sweep of
 	// q-cache slot 0 / 1, 3 = w sweep
 	int carry_ok = 0, carry = 0;
 	// feature-sharded mode (vbfm_set_shard_mode): shards own column chunks of every level
-	int shard_mode = VBFM_SHARD_ROWS;
-	int fs_req = 1;                // shards requested (no communicator: run one after another here)
-	int fs_n = 1;                  // shards in use
-	std::vector<uint32_t> fs_lo;   // [L * (fs_n + 1)] chunk bounds of each level in level_feats
-	uint32_t *fs_own = nullptr;    // this rank's features (all levels) for the parameter exchange
-	uint32_t fs_own_n = 0;
-	double *fs_base = nullptr;     // [2n] e, t at the start of a pass
-	double *fs_buf = nullptr;      // [5n] summed changes / partial q-caches
-	double2 *fs_pbuf = nullptr;    // [nf] parameter exchange
-	RowRec *fs_rows0 = nullptr;    // in-process shards: the rows at the start of a pass
-	vbfm_exchange_fn xfn = nullptr; // vbfm_comm_init_host: all-reduces through the caller
-	void *xuser = nullptr;
-	std::vector<uint8_t> xbuf;      // host staging of a host-exchange all-reduce
-	bool deferred() const { return lpay || lpay2; }
-	bool multi() const { return comm || xfn || comm_failed; }
-	bool row_comm() const { return multi() && shard_mode == VBFM_SHARD_ROWS; }
+	// (vbfm_schedule.hip; released by fs_free)
+	struct FeatShards {
+		int mode = VBFM_SHARD_ROWS;
+		int req = 1;                   // shards requested (no communicator: run one after another here)
+		int n = 1;                     // shards in use
+		std::vector<uint32_t> lo;      // [L * (n + 1)] chunk bounds of each level in level_feats
+		uint32_t *own = nullptr;       // this rank's features (all levels) for the parameter exchange
+		uint32_t own_n = 0;
+		double *base = nullptr;        // [2n] e, t at the start of a pass
+		double *buf = nullptr;         // [5n] summed changes / partial q-caches
+		double2 *pbuf = nullptr;       // [nf] parameter exchange
+		RowRec *rows0 = nullptr;       // in-process shards: the rows at the start of a pass
+	} fs;
+	bool deferred() const { return store.lpay || store.lpay2; }
+	bool multi() const { return net.comm || net.xfn || net.failed; }
+	bool row_comm() const { return multi() && fs.mode == VBFM_SHARD_ROWS; }
+	bool split() const { return row_comm() || force_split; }   // the sweeps run their split (multi-rank) forms
 	McState *mc = nullptr;         // set by vbfm_mcmc_init: the context runs the MCMC / ALS learner
 	OvState *ov = nullptr;         // set by vbfm_online_init: the context runs the online VB learner
 	// vbfm_init_params_replay: the draws' seed and the glibc outputs they consumed (after the
@@ -261,10 +278,9 @@ struct vbfm_ctx {
 	uint64_t init_stream_end = ~0ull;
 };
 
-
 namespace vbi {
 
-int fail(vbfm_ctx *c, const std::string &m);
+int fail(vbfm_ctx *c, const std::string &m);   // vbfm_capi.hip
 
 template <class F> int guarded(vbfm_ctx *c, F &&fn)
 {
@@ -283,6 +299,7 @@ template <class F> int guarded(vbfm_ctx *c, F &&fn)
 	}
 }
 
+// ---- vbfm_comm.hip: the exchange between ranks ---------------------------------------------
 void sync(vbfm_ctx *c);
 // a copy from the device into host memory, queued on the context's stream. A copy into pageable
 // memory holds the calling thread until the stream reaches it, so with an RCCL communicator the
@@ -290,23 +307,22 @@ void sync(vbfm_ctx *c);
 hipError_t d2h(vbfm_ctx *c, void *dst, const void *src, size_t bytes);
 // the phase the next exchanges belong to (restored on scope exit), for comm_fail's message
 struct XPhase {
-	vbfm_ctx *c;
+	vbfm_ctx::Net &x;
 	const char *p;
 	int f, l;
-	XPhase(vbfm_ctx *c_, const char *phase, int f_ = -1, int l_ = -1) : c(c_), p(c_->x_phase), f(c_->x_f), l(c_->x_l)
+	XPhase(vbfm_ctx *c, const char *phase, int f_ = -1, int l_ = -1) : x(c->net), p(x.x_phase), f(x.x_f), l(x.x_l)
 	{
-		c->x_phase = phase; c->x_f = f_; c->x_l = l_;
+		x.x_phase = phase; x.x_f = f_; x.x_l = l_;
 	}
-	~XPhase() { c->x_phase = p; c->x_f = f; c->x_l = l; }
+	~XPhase() { x.x_phase = p; x.x_f = f; x.x_l = l; }
 };
 // a new iteration's exchange accounting (vbfm_exchange_info)
 void xs_reset(vbfm_ctx *c);
-// fold the timed exchange spans of the iteration into c->xs (vbfm_iterate / vbfm_mcmc_iterate)
+// fold the timed exchange spans of the iteration into c->net.xs (vbfm_iterate / vbfm_mcmc_iterate)
 void xs_span(vbfm_ctx *c, float ms);
 void allreduce_host(vbfm_ctx *c, double *v, int n);
 // in-place all-reduce of a device buffer over the ranks (RCCL on c->s, or the host exchange)
 void allreduce_dev(vbfm_ctx *c, void *buf, size_t n, ncclDataType_t t, ncclRedOp_t op);
-double finish_sum(vbfm_ctx *c, uint32_t nblocks);
 // chunks the per-level exchange is cut into (1: one all-reduce after the level's statistics)
 uint32_t ar_chunks(vbfm_ctx *c, uint32_t nfeat);
 // in-place fp64 sum over the ranks of n doubles of chunk i (< ar_chunks) of a level, issued after
@@ -314,6 +330,7 @@ uint32_t ar_chunks(vbfm_ctx *c, uint32_t nfeat);
 void allreduce_chunk(vbfm_ctx *c, double2 *buf, size_t n, uint32_t i);
 // c->s waits for every chunk's all-reduce issued since the last join
 void allreduce_join(vbfm_ctx *c);
+void comm_free(vbfm_ctx *c);   // the communicator, its stream and events, the stall flag
 
 // chunk [c0, c1) of a level's features as a launch of its own (LevelArgs / McArgs): the
 // kernels index their columns, runs and statistics by the launch's feature index
@@ -349,20 +366,51 @@ void stats_exchange(vbfm_ctx *c, const A &a, F launch)
 	}
 	allreduce_join(c);
 }
+
+// ---- vbfm_schedule.hip: dependency levels, feature shards -------------------------------------
+void build_schedule(vbfm_ctx *c);
+void fs_free(vbfm_ctx *c);
+
+// ---- vbfm_store.hip: the level-ordered row stores ---------------------------------------------
+// the store for the new schedule (cp: the train col_ptr, feats: level_feats, both on the host)
+void build_lorder(vbfm_ctx *c, const std::vector<uint64_t> &cp, const std::vector<uint32_t> &feats);
+void store_release(vbfm_ctx *c);                  // every buffer of the store; the group starts over
+void lord_release(vbfm_ctx *c, bool keep_rows);   // rows back to row order (keep_rows), sync, store_release
+void rows_level_order(vbfm_ctx *c);   // records in level-0 order before a sweep (no-op without the store)
+void rows_dense(vbfm_ctx *c);         // records N-dense for the data-set sums (row order from the entry store)
+void rows_row_order(vbfm_ctx *c);     // records back in row order (row-indexed kernels, readback)
+std::vector<RowRec> rows_mid_sweep(vbfm_ctx *c);
+// the store's part of a level launch (LevelArgs / McArgs): level l's runs, and where its records
+// move -- the other buffer in the next level's order, or (entry store: one store, global slots)
+// each row's next slot in place
+template <class A> void store_args(vbfm_ctx *c, A &a, uint32_t l)
+{
+	const vbfm_ctx::Store &st = c->store;
+	a.lcp = st.lcp + c->level_ptr[l];
+	a.lx = st.lx;
+	a.lnext = st.lnext;
+	a.lbase = st.estore ? 0 : (uint64_t)l * c->tr.n;
+	a.src = c->rows;
+	a.dst = st.estore ? c->rows : st.rows_alt;
+	a.first_level = l == 0;
+	if (st.estore) a.ent = 1;
+}
+
+// ---- vbfm_capi.hip: the context's life and the VB sweep driver --------------------------------
+void free_data(DevData &d);
+void alloc_rows(vbfm_ctx *c);                     // the records of a new train set
+uint32_t global_nf(vbfm_ctx *c, uint32_t nf);     // the train feature count every shard pads to
+double finish_sum(vbfm_ctx *c, uint32_t nblocks);
 void require_train(vbfm_ctx *c);
+void no_partial(vbfm_ctx *c);
 uint32_t nlevels(vbfm_ctx *c);
 constexpr size_t NO_SPAN = ~(size_t)0;   // prof_begin: this launch is not timed
 size_t prof_begin(vbfm_ctx *c, int kind, hipStream_t st = nullptr);
 void prof_end(vbfm_ctx *c, size_t a, hipStream_t st = nullptr);
+void prof_free(vbfm_ctx *c);
 int blocked_predict(const vbfm_ctx *c, const DevData &d);
 float ev_ms(vbfm_ctx *c, int a, int b);
-void mc_free(vbfm_ctx *c);   // vbfm_mcmc_capi.hip
-void ov_free(vbfm_ctx *c);   // vbfm_online.hip
-void glibc_state_at(uint32_t seed, uint64_t pos, uint32_t st[31]);   // vbfm_replay.hip
-// online VB: the per-feature fields of LevelArgs for the w sweep or factor f (vbfm_online.hip)
-void ov_level_args(vbfm_ctx *c, LevelArgs &a, bool is_w, int f);
-void ov_launch_level(vbfm_ctx *c, LevelArgs &a, uint32_t l, bool is_w);
-// steps of update_all shared with the online learner (vbfm_capi.hip)
+// steps of update_all shared with the online learner
 void step_w(vbfm_ctx *c);
 void step_qcache(vbfm_ctx *c, int f);
 void step_v(vbfm_ctx *c, int f);
@@ -377,13 +425,10 @@ double free_energy(vbfm_ctx *c, double energy);
 void test_predict(vbfm_ctx *c, hipStream_t s);
 void read_counters(vbfm_ctx *c, vbfm_iter_stats *o);
 void upload_hyp(vbfm_ctx *c);
-void lord_release(vbfm_ctx *c, bool keep_rows);
-void rows_level_order(vbfm_ctx *c);   // records in level-0 order before a sweep (no-op without the store)
-void rows_dense(vbfm_ctx *c);         // records N-dense for the data-set sums (row order from the entry store)
-void rows_row_order(vbfm_ctx *c);     // records back in row order (row-indexed kernels, readback)   // level-ordered store freed (rows back to row order)
 
-// checkpoint files (vbfm_save_state / vbfm_load_state, vbfm_capi.hip): whole-buffer I/O that
-// throws on a short read or write, device buffers staged through the host in 64 MB pieces
+// ---- vbfm_ckpt.hip: checkpoint files (vbfm_save_state / vbfm_load_state) ----------------------
+// whole-buffer I/O that throws on a short read or write, device buffers staged through the host
+// in 64 MB pieces
 struct CkptFile {
 	FILE *f;
 	std::string path;
@@ -403,16 +448,27 @@ struct CkptFile {
 };
 void dev_to_file(vbfm_ctx *c, CkptFile &f, const void *d, size_t bytes);
 void file_to_dev(vbfm_ctx *c, CkptFile &f, void *d, size_t bytes);
-// the MCMC / ALS learner's part of a checkpoint (vbfm_mcmc_capi.hip): its payload size, and the
-// payload written / read behind the common header (the caller has put the records in row order)
+
+// ---- vbfm_mcmc_capi.hip: the MCMC / ALS learner -----------------------------------------------
+void mc_free(vbfm_ctx *c);
+// its part of a checkpoint: its payload size, and the payload written / read behind the common
+// header (the caller has put the records in row order)
 uint64_t mc_state_payload(vbfm_ctx *c);
 void mc_state_write(vbfm_ctx *c, CkptFile &f);
 void mc_state_read(vbfm_ctx *c, CkptFile &f);
-// ... and the online learner's (vbfm_online.hip)
+
+// ---- vbfm_online.hip: the online VB learner ---------------------------------------------------
+void ov_free(vbfm_ctx *c);
+// the per-feature fields of LevelArgs for the w sweep or factor f
+void ov_level_args(vbfm_ctx *c, LevelArgs &a, bool is_w, int f);
+void ov_launch_level(vbfm_ctx *c, LevelArgs &a, uint32_t l, bool is_w);
 uint64_t ov_state_payload(vbfm_ctx *c);
 // the online learner sweeps its batches on the per-batch level-ordered store (k_ov_lord)
 bool ov_store_on(vbfm_ctx *c);
 void ov_state_write(vbfm_ctx *c, CkptFile &f);
 void ov_state_read(vbfm_ctx *c, CkptFile &f);
+
+// ---- vbfm_replay.hip --------------------------------------------------------------------------
+void glibc_state_at(uint32_t seed, uint64_t pos, uint32_t st[31]);
 
 }  // namespace vbi

@@ -320,19 +320,10 @@ void mc_sweep(vbfm_ctx *c, bool is_w, int f)
 		if (a.nfeat == 0) continue;
 		XPhase ph(c, is_w ? "draw_w sweep" : "draw_v sweep", is_w ? -1 : f, (int)l);
 		const size_t p = prof_begin(c, is_w ? 1 : 0);
-		if (c->lord) {   // level-ordered store: stream the runs, move the records to level l+1
-			a.lcp = c->lcp + c->level_ptr[l];
-			a.lx = c->lx;
-			a.lnext = c->lnext;
-			a.lbase = (uint64_t)l * c->tr.n;
-			a.src = c->rows;
-			a.dst = c->rows_alt;
-			a.first_level = l == 0;
-			if (c->estore) {   // one store, global slots: each record to its row's next slot
-				a.lbase = 0;
-				a.dst = c->rows;
-				a.ent = 1;
-				if (!c->row_comm() && !c->force_split) {
+		if (c->store.lord) {   // level-ordered store: stream the runs, move the records to level l+1
+			store_args(c, a, l);
+			if (c->store.estore) {   // one store, global slots: each record to its row's next slot
+				if (!c->split()) {
 					HIPCHK(vbk::mc_lord_level(a, 0, is_w, c->s));
 				} else {   // row shards: the two-pass split (statistics, all-reduce, draw + move)
 					stats_exchange(c, a, [&](const McArgs &b) { HIPCHK(vbk::mc_lord_level(b, 1, is_w, c->s)); });
@@ -341,30 +332,30 @@ void mc_sweep(vbfm_ctx *c, bool is_w, int f)
 				prof_end(c, p);
 				continue;
 			}
-			if (!c->row_comm() && !c->force_split) {
+			if (!c->split()) {
 				HIPCHK(vbk::mc_lord_level(a, 0, is_w, c->s));
 			} else if (c->deferred()) {
 				// deferred: level l-1's correction, level l's statistics and the move in one pass;
 				// the draws after the all-reduce, applied by level l+1 (or the flush)
-				a.lpay = c->lpay;
-				a.lpay2 = c->lpay2;
-				a.tab = c->post_tab;
-				a.pending = (l > 0 ? 3 : 0) | (defer_nt_stores() ? 4 : 0);
+				a.lpay = c->store.lpay;
+				a.lpay2 = c->store.lpay2;
+				a.tab = c->store.post_tab;
+				a.pending = (l > 0 ? 3 : 0) | ((defer_nt_bits() & 2) ? 4 : 0);
 				stats_exchange(c, a, [&](const McArgs &b) { HIPCHK(vbk::mc_lord_defer_level(b, is_w, c->s)); });
 				HIPCHK(vbk::mc_lord_defer_post(a, is_w, c->s));
 				if (l + 1 == nlevels(c)) {   // the sweep's last correction, on level-0-ordered records
-					a.dst = c->rows_alt;      // (swapped below)
+					a.dst = c->store.rows_alt;      // (swapped below)
 					HIPCHK(vbk::mc_lord_defer_flush(a, is_w, c->tr.n, c->s));
 				}
 			} else {
 				stats_exchange(c, a, [&](const McArgs &b) { HIPCHK(vbk::mc_lord_level(b, 1, is_w, c->s)); });
 				HIPCHK(vbk::mc_lord_level(a, 2, is_w, c->s));
 			}
-			std::swap(c->rows, c->rows_alt);
+			std::swap(c->rows, c->store.rows_alt);
 			prof_end(c, p);
 			continue;
 		}
-		if (!c->row_comm() && !c->force_split) {
+		if (!c->split()) {
 			HIPCHK(is_w ? vbk::mc_w_level(a, 0, c->s) : vbk::mc_v_level(a, 0, c->s));
 		} else {   // row-sharded: statistics of this shard, summed over shards, identical draws
 			stats_exchange(c, a, [&](const McArgs &b) {
@@ -395,7 +386,7 @@ void mc_step_v(vbfm_ctx *c, int f)
 		const size_t p = prof_begin(c, 2);
 		rows_level_order(c);
 		HIPCHK(vbk::mc_qcache(c->tr.row_ptr, c->tr.csr, c->ms_v + f, (uint32_t)c->k, c->rows, c->tr.n, slot,
-		                      c->rows_lorder ? c->lpos0 : nullptr, c->s));
+		                      c->store.rows_lorder ? c->store.lpos0 : nullptr, c->s));
 		prof_end(c, p);
 	}
 	fill_normals(c, c->mc->v_lambda.data() + f, (size_t)c->k);
@@ -446,12 +437,11 @@ void scan_columns(vbfm_ctx *c)
 	m.col_nonempty.assign(nf, 0);
 	for (uint32_t j = 0; j < nf; j++) m.col_nonempty[j] = cp[j + 1] > cp[j];
 	if (c->multi() && nf) {
-		uint8_t *d = dalloc<uint8_t>(nf);
+		DevScratch<uint8_t> d(nf);
 		HIPCHK(hipMemcpyAsync(d, m.col_nonempty.data(), nf, hipMemcpyHostToDevice, c->s));
 		allreduce_dev(c, d, nf, ncclUint8, ncclMax);
 		HIPCHK(d2h(c, m.col_nonempty.data(), d, nf));
 		sync(c);
-		dfree(d);
 	}
 }
 
@@ -465,7 +455,7 @@ int vbfm_mcmc_init(vbfm_ctx *c, const vbfm_mcmc_config *cfg)
 	if (!c || !cfg) return fail(c, "vbfm_mcmc_init: null argument");
 	return guarded(c, [&] {
 		if (cfg->rng != VBFM_RNG_REFERENCE && cfg->rng != VBFM_RNG_DEVICE) throw std::string("unknown rng mode");
-		if (c->shard_mode == VBFM_SHARD_FEATURES)
+		if (c->fs.mode == VBFM_SHARD_FEATURES)
 			throw std::string("feature shards are implemented for the VB learner only");
 		mc_free(c);
 		c->mc = new McState();
@@ -494,7 +484,7 @@ int vbfm_mcmc_init(vbfm_ctx *c, const vbfm_mcmc_config *cfg)
 			std::vector<double> v(kd), w(c->D), zero(std::max(kd, (size_t)c->D), 0.0);
 			for (double &x : v) x = m.stream.gaussian(0.0, cfg->init_stdev);
 			for (double &x : w) x = m.stream.gaussian(0.0, cfg->init_stdev);
-			double *tmp = dalloc<double>(2 * std::max(kd, (size_t)c->D));
+			DevScratch<double> tmp(2 * std::max(kd, (size_t)c->D));
 			const size_t half = std::max(kd, (size_t)c->D);
 			HIPCHK(hipMemcpyAsync(tmp + half, zero.data(), half * 8, hipMemcpyHostToDevice, c->s));
 			if (kd) {
@@ -507,7 +497,6 @@ int vbfm_mcmc_init(vbfm_ctx *c, const vbfm_mcmc_config *cfg)
 				HIPCHK(vbk::pack_pairs(tmp, tmp + half, c->ms_w, 1, c->D, c->s));
 			}
 			sync(c);
-			dfree(tmp);
 		} else {
 			HIPCHK(vbk::init_normal_pairs(c->ms_v, kd, cfg->seed, 21, cfg->init_stdev, 0.0, c->s));
 			HIPCHK(vbk::init_normal_pairs(c->ms_w, c->D, cfg->seed, 22, cfg->init_stdev, 0.0, c->s));
@@ -524,7 +513,7 @@ int vbfm_mcmc_set_params(vbfm_ctx *c, const vbfm_mcmc_params *p)
 		McState &m = mc(c);
 		const size_t kd = (size_t)c->k * c->D, half = std::max(kd, (size_t)c->D);
 		if (!p->w || (kd && !p->v)) throw std::string("vbfm_mcmc_set_params: parameter arrays missing");
-		double *tmp = dalloc<double>(2 * half);
+		DevScratch<double> tmp(2 * half);
 		HIPCHK(hipMemsetAsync(tmp + half, 0, half * 8, c->s));
 		HIPCHK(hipMemcpyAsync(tmp, p->w, (size_t)c->D * 8, hipMemcpyHostToDevice, c->s));
 		HIPCHK(vbk::pack_pairs(tmp, tmp + half, c->ms_w, 1, c->D, c->s));
@@ -534,7 +523,6 @@ int vbfm_mcmc_set_params(vbfm_ctx *c, const vbfm_mcmc_params *p)
 			HIPCHK(vbk::pack_pairs(tmp, tmp + half, c->ms_v, (uint32_t)c->k, c->D, c->s));
 			sync(c);
 		}
-		dfree(tmp);
 		if (p->w_mu) std::copy(p->w_mu, p->w_mu + G_(c), m.w_mu.begin());
 		if (p->w_lambda) std::copy(p->w_lambda, p->w_lambda + G_(c), m.w_lambda.begin());
 		if (p->v_mu) std::copy(p->v_mu, p->v_mu + GK(c), m.v_mu.begin());
@@ -553,7 +541,7 @@ int vbfm_mcmc_get_params(vbfm_ctx *c, vbfm_mcmc_params *p)
 	return guarded(c, [&] {
 		McState &m = mc(c);
 		const size_t kd = (size_t)c->k * c->D, half = std::max(kd, (size_t)c->D);
-		double *tmp = dalloc<double>(2 * half);
+		DevScratch<double> tmp(2 * half);
 		HIPCHK(vbk::unpack_pairs(c->ms_w, tmp, tmp + half, 1, c->D, c->s));
 		if (p->w) HIPCHK(d2h(c, p->w, tmp, (size_t)c->D * 8));
 		sync(c);
@@ -562,7 +550,6 @@ int vbfm_mcmc_get_params(vbfm_ctx *c, vbfm_mcmc_params *p)
 			HIPCHK(d2h(c, p->v, tmp, kd * 8));
 			sync(c);
 		}
-		dfree(tmp);
 		if (p->w_mu) std::copy(m.w_mu.begin(), m.w_mu.end(), p->w_mu);
 		if (p->w_lambda) std::copy(m.w_lambda.begin(), m.w_lambda.end(), p->w_lambda);
 		if (p->v_mu) std::copy(m.v_mu.begin(), m.v_mu.end(), p->v_mu);
@@ -584,7 +571,7 @@ int vbfm_mcmc_init_caches(vbfm_ctx *c)
 		// fm_learn_mcmc_simultaneous.h:71-80: predict train and test, e = yhat - y
 		mc_predict(c);
 		HIPCHK(vbk::mc_train_update(c->rows, c->scratch_n, c->tr.target, c->tr.n, c->min_target, c->max_target,
-		                            m.red_d, MC_RED_BLOCKS, c->rows_lorder ? c->lpos0 : nullptr, c->s));
+		                            m.red_d, MC_RED_BLOCKS, c->store.rows_lorder ? c->store.lpos0 : nullptr, c->s));
 		sync(c);
 		m.iter = 0;
 		m.caches = true;
@@ -603,8 +590,8 @@ int vbfm_mcmc_iterate(vbfm_ctx *c, vbfm_mcmc_stats *o)
 		memset(&st, 0, sizeof(st));
 		memset(m.hc, 0, sizeof(m.hc));
 		HIPCHK(hipMemsetAsync(c->counters, 0, CNT_N * 4, c->s));
-		c->pev_used = 0;
-		c->spans.clear();
+		c->prof.pev_used = 0;
+		c->prof.spans.clear();
 		xs_reset(c);
 		c->q_ready[0] = c->q_ready[1] = -1;
 		HIPCHK(hipEventRecord(m.ev[MEV_BEGIN], c->s));
@@ -638,11 +625,11 @@ int vbfm_mcmc_iterate(vbfm_ctx *c, vbfm_mcmc_stats *o)
 		if (fused) {   // yhat of train from the sweeps' accumulators + the last factor and w
 			if (!m.pc) m.pc = dalloc<double>(2 * (size_t)c->D);
 			HIPCHK(vbk::mc_pred_final(c->tr.row_ptr, c->tr.csr, c->ms_v, c->ms_w, c->k, c->k1, c->k0, m.w0, c->k >= 2,
-			                          c->rows, c->rows_lorder ? c->lpos0 : nullptr, c->tr.n, c->D, m.pc, c->scratch_n,
+			                          c->rows, c->store.rows_lorder ? c->store.lpos0 : nullptr, c->tr.n, c->D, m.pc, c->scratch_n,
 			                          c->s));
 		}
 		HIPCHK(vbk::mc_train_update(c->rows, c->scratch_n, c->tr.target, c->tr.n, mn, mx, c->red_d, c->RED_BLOCKS,
-		                            c->rows_lorder ? c->lpos0 : nullptr, c->s));
+		                            c->store.rows_lorder ? c->store.lpos0 : nullptr, c->s));
 		tm[4] = finish_sum(c, c->RED_BLOCKS);
 		allreduce_host(c, tm, 5);
 		HIPCHK(hipEventRecord(m.ev[MEV_PRED], c->s));
@@ -678,10 +665,10 @@ int vbfm_mcmc_iterate(vbfm_ctx *c, vbfm_mcmc_stats *o)
 		st.ms_v = ms(MEV_W, MEV_V);
 		st.ms_predict = ms(MEV_V, MEV_PRED);
 		st.ms_total = ms(MEV_BEGIN, MEV_PRED);
-		for (const auto &sp : c->spans) {
+		for (const auto &sp : c->prof.spans) {
 			if (sp.kind != 0 && sp.kind != 3) continue;
 			float t = 0.f;
-			HIPCHK(hipEventElapsedTime(&t, c->pev[sp.a], c->pev[sp.a + 1]));
+			HIPCHK(hipEventElapsedTime(&t, c->prof.pev[sp.a], c->prof.pev[sp.a + 1]));
 			if (sp.kind == 3) {
 				xs_span(c, t);
 				continue;

@@ -1273,7 +1273,7 @@ int vbfm_online_init(vbfm_ctx *c, const vbfm_online_config *cfg)
 	if (!c || !cfg) return fail(c, "vbfm_online_init: null argument");
 	return guarded(c, [&] {
 		if (c->mc) throw std::string("an MCMC / ALS context cannot run the online VB learner");
-		if (c->multi() || c->shard_mode == VBFM_SHARD_FEATURES)
+		if (c->multi() || c->fs.mode == VBFM_SHARD_FEATURES)
 			throw std::string("the online VB learner runs on one GPU (no communicator, no feature shards)");
 		if (!c->rows) throw std::string("no train data set (vbfm_set_train)");
 		if (!c->e_test) throw std::string("no test data set (vbfm_set_test)");
@@ -1366,7 +1366,7 @@ int vbfm_online_init(vbfm_ctx *c, const vbfm_online_config *cfg)
 			// vbfm_set_layout(VBFM_LAYOUT_COLUMN) keep the column kernels
 			{
 				const char *lay = getenv("VBFM_LAYOUT");
-				bool want = c->layout_req != VBFM_LAYOUT_COLUMN && !(lay && !strcmp(lay, "column")) &&
+				bool want = c->store.layout_req != VBFM_LAYOUT_COLUMN && !(lay && !strcmp(lay, "column")) &&
 				            (c->k1 || c->k == 0) && nlevels(c) > 0;
 				if (want && nf) {
 					std::vector<uint8_t> dup(nf);
@@ -1447,8 +1447,8 @@ int vbfm_online_epoch(vbfm_ctx *c, vbfm_online_stats *out)
 		Range r_ep("vbfm_online_epoch");
 		HIPCHK(hipEventRecord(o.ev[0], c->s));
 		o.launches_v = 0;
-		c->pev_used = 0;   // vbfm_set_profiling: the spans of this epoch only
-		c->spans.clear();
+		c->prof.pev_used = 0;   // vbfm_set_profiling: the spans of this epoch only
+		c->prof.spans.clear();
 		ov_regroup(c);
 		HIPCHK(hipEventRecord(o.ev[1], c->s));
 		const uint32_t nb = o.num_batch, nf = c->tr.nf;

@@ -1,5 +1,5 @@
 """Dependency levels and the feature-shard assignment of libvbfm's VBFM_SHARD_FEATURES mode,
-restated in numpy for the tests (vbfm_capi.hip: build_schedule, build_fshards)."""
+restated in numpy for the tests (vbfm_schedule.hip: build_schedule, build_fshards)."""
 import numpy as np
 
 

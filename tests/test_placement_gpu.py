@@ -1,4 +1,4 @@
-"""Record-buffer placement tuning of the level store (tune_placement, csrc/vbfm_capi.hip; DESIGN
+"""Record-buffer placement tuning of the level store (tune_placement, csrc/vbfm_store.hip; DESIGN
 §5b): which physical buffers hold the records changes the level kernel's speed only, so a learner
 that tuned its placement must match one that did not, bit for bit, and the report
 (vbfm_placement_info) must name the kept pair: the best pair among the best-scored candidates

@@ -1,4 +1,4 @@
-"""Dependency levels of the train features (vbfm_capi.hip build_schedule): the relaxation's fixed
+"""Dependency levels of the train features (vbfm_schedule.hip build_schedule): the relaxation's fixed
 point (k_level_relax, one round per row switch on the longest path) and Kahn's order (k_kahn_*,
 one pass over the edges, the default once three relaxation rounds have not converged) give the
 same levels, equal to the numpy restatement (tests/shards.py levels): on multi-hot rows

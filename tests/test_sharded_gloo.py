@@ -2,8 +2,8 @@
 
 libvbfm's multi-rank mode splits the train rows over ranks and, per dependency level,
 all-reduces each feature's sufficient statistics (and every whole-data-set sum) so that all
-ranks compute identical posteriors (vbfm_capi.hip: sweep_level / allreduce_host). Here the
-same decomposition runs through the oracle's sharded update_all
+ranks compute identical posteriors (vbfm_capi.hip: sweep_level; vbfm_comm.hip: allreduce_host).
+Here the same decomposition runs through the oracle's sharded update_all
 (or_vb_update_all_sharded) with a torch.distributed gloo all-reduce as the exchange, and
 must reproduce the single-process update_all to summation-order accuracy.
 """

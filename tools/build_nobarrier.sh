@@ -19,8 +19,8 @@ F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unuse
 # the sources include ../../include/vbfm.h: src/csrc -> include/ one level above src
 rm -f $O/build/*.o $O/lib/libvbfm.so
 pids=()
-for s in vbfm_online vbfm_replay vbfm_lorder vbfm_kernels vbfm_mcmc vbfm_capi vbfm_mcmc_capi; do
-  /opt/rocm/bin/hipcc $F -c $O/src/csrc/$s.hip -o $O/build/$s.o &
+for src in $O/src/csrc/*.hip; do   # every translation unit, as the Makefile's wildcard
+  /opt/rocm/bin/hipcc $F -c $src -o $O/build/$(basename $src .hip).o &
   pids+=($!)
 done
 g++ -O2 -std=c++17 -fPIC -ffp-contract=off -Wall -pthread -c $O/src/csrc/vbfm_host.cpp -o $O/build/vbfm_host.o

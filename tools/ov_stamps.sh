@@ -8,8 +8,8 @@ P=scalable-variational-bayesian-factorization-machine_amd
 O=tools/ab_stamp
 mkdir -p $O/build $O/lib
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -I/opt/rocm/include -mllvm -amdgpu-kernarg-preload-count=16 -DVBFM_OV_STAMPS"
-for s in vbfm_online vbfm_replay vbfm_lorder vbfm_kernels vbfm_mcmc vbfm_capi vbfm_mcmc_capi; do
-  /opt/rocm/bin/hipcc $F -c $P/csrc/$s.hip -o $O/build/$s.o &
+for src in $P/csrc/*.hip; do   # every translation unit, as the Makefile's wildcard
+  /opt/rocm/bin/hipcc $F -c $src -o $O/build/$(basename $src .hip).o &
 done
 g++ -O2 -std=c++17 -fPIC -ffp-contract=off -Wall -pthread -c $P/csrc/vbfm_host.cpp -o $O/build/vbfm_host.o
 wait
