@@ -331,7 +331,7 @@ void sweep_level(vbfm_ctx *c, uint32_t l, bool is_w, int f)
 	}
 	if (!c->split()) {
 		long_args(c, a, l);
-		HIPCHK(is_w ? vbk::w_level_fused(a, c->s) : vbk::v_level_fused(a, c->s));
+		HIPCHK(vbk::level_fused(a, is_w, c->s));
 		HIPCHK(vbk::col_long(a, is_w, c->s));
 		prof_end(c, p);
 		return;
@@ -339,9 +339,9 @@ void sweep_level(vbfm_ctx *c, uint32_t l, bool is_w, int f)
 	// row-sharded form: per-feature sufficient statistics of this shard's rows, summed over
 	// the shards, then every shard applies the identical posterior to its own rows
 	stats_exchange(c, a, [&](const LevelArgs &b) {
-		HIPCHK(is_w ? vbk::w_level_stats(b, c->s) : vbk::v_level_stats(b, c->s));
+		HIPCHK(vbk::level_stats(b, is_w, c->s));
 	});
-	HIPCHK(is_w ? vbk::w_level_correct(a, c->s) : vbk::v_level_correct(a, c->s));
+	HIPCHK(vbk::level_correct(a, is_w, c->s));
 	prof_end(c, p);
 }
 
@@ -362,7 +362,7 @@ void sweep_level_shard(vbfm_ctx *c, uint32_t l, bool is_w, int f, int s)
 	a.first_mask = 0;
 	if (a.nfeat == 0) return;
 	const size_t p = prof_begin(c, is_w ? 1 : 0);
-	HIPCHK(is_w ? vbk::w_level_fused(a, c->s) : vbk::v_level_fused(a, c->s));
+	HIPCHK(vbk::level_fused(a, is_w, c->s));
 	prof_end(c, p);
 }
 

@@ -301,12 +301,10 @@ namespace vbk {
 // test hook of the exchange's deadline (VBFM_FAULT=comm_stall): one wave that spins until *flag
 // (coherent host memory) turns non-zero, at most ~100 s
 hipError_t stall(const uint32_t *flag, hipStream_t s);
-hipError_t v_level_fused(const LevelArgs &a, hipStream_t s);
-hipError_t w_level_fused(const LevelArgs &a, hipStream_t s);
-hipError_t v_level_stats(const LevelArgs &a, hipStream_t s);
-hipError_t v_level_correct(const LevelArgs &a, hipStream_t s);
-hipError_t w_level_stats(const LevelArgs &a, hipStream_t s);
-hipError_t w_level_correct(const LevelArgs &a, hipStream_t s);
+// column-gather layout (vbfm_kernels.hip): fused level, or split stats -> (all-reduce) -> correct
+hipError_t level_fused(const LevelArgs &a, int is_w, hipStream_t s);
+hipError_t level_stats(const LevelArgs &a, int is_w, hipStream_t s);
+hipError_t level_correct(const LevelArgs &a, int is_w, hipStream_t s);
 // pos: nullptr, or the record index of each row (level-ordered store: level-0 position)
 hipError_t qcache(const uint64_t *row_ptr, const uint2 *csr, const double2 *ms_f, uint32_t stride, RowRec *rows,
                   uint32_t n, int slot, const uint32_t *pos, hipStream_t s);
@@ -462,12 +460,11 @@ uint32_t ov_lord_g(uint32_t m);
 uint32_t ov_pad_cap();
 // MCMC / ALS (vbfm_mcmc.hip); mode 0: fused, 1: statistics only (into a.stats),
 // 2: draw + correction from the (all-reduced) a.stats
-hipError_t mc_v_level(const McArgs &a, int mode, hipStream_t s);
-hipError_t mc_w_level(const McArgs &a, int mode, hipStream_t s);
+hipError_t mc_level(const McArgs &a, int mode, int is_w, hipStream_t s);
 hipError_t mc_prior(const McArgs &a, uint32_t j0, uint32_t j1, int is_v, hipStream_t s);
 hipError_t mc_qcache(const uint64_t *row_ptr, const uint2 *csr, const double2 *par_f, uint32_t stride, RowRec *rows,
                      uint32_t n, int slot, const uint32_t *pos, hipStream_t s);
-// MCMC / ALS level on the level-ordered store; mode as mc_v_level (2 = draw + move)
+// MCMC / ALS level on the level-ordered store; mode as mc_level (2 = draw + move)
 hipError_t mc_lord_level(const McArgs &a, int mode, int is_w, hipStream_t s);
 // MCMC / ALS deferred split on the level-ordered store: level l-1's correction, level l's
 // statistics and the move in one pass; the draws after the all-reduce; the sweep's last correction

@@ -15,6 +15,10 @@
 // row); all features of one level are updated concurrently, one workgroup per feature
 // column, which reproduces the sequential result exactly (each row is touched by at most
 // one feature per level, in the same relative order as the reference).
+//
+// The column-gather level kernels have one body per family over IS_W (level_fused_body,
+// level_stats_body, level_correct_body; the per-entry arithmetic is vbfm_math.h's); the
+// __global__ templates k_v_level_* / k_w_level_* are shells that keep the kernels' names.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -22,26 +26,33 @@
 
 namespace {
 
-template <int P, bool NEXT>
-DEVI void v_apply_serial(const uint2 *col, uint32_t n, RowRec *rows, bool go, double mo, double so, double mu,
-                         double sig, double2 nx, uint32_t fm)
+// a column listing some row twice: the reference corrects entry after entry, a repeated
+// row seeing its own earlier update
+template <bool IS_W, int P, bool NEXT>
+DEVI void apply_serial(const uint2 *col, uint32_t n, RowRec *rows, bool go, double mo, double so, double mu, double sig,
+                       double2 nx, uint32_t fm)
 {
-	// a column listing some row twice: the reference corrects entry after entry, a repeated
-	// row seeing its own earlier update
 	for (uint32_t i = 0; i < n; ++i) {
 		const uint2 ent = col[i];
 		Rec v;
 		load_rec(rows, ent.x & ROW_MASK, v);
-		v_apply<P, NEXT>(v, ent_x(ent), (ent.x & fm) != 0, go, mo, so, mu, sig, nx);
+		vb_apply<IS_W, P, NEXT>(v, ent_x(ent), (ent.x & fm) != 0, go, mo, so, mu, sig, nx);
 		store_rec(rows, ent.x & ROW_MASK, v);
 	}
 }
 
-// One workgroup per feature column of the level. Entries i = tid + u*BLOCK for u < R are
-// gathered once (one 64-B record each) and kept in registers from the stats pass to the
-// write-back; longer columns re-gather the overflow entries.
-template <int BLOCK, int R, int P, bool NEXT>
-__global__ __launch_bounds__(BLOCK) void k_v_level_fused(LevelArgs a)
+DEVI double level_hyp(const LevelArgs &a, uint32_t j)
+{
+	return a.hyp_uniform ? a.hyp0 : a.hyp[(size_t)a.attr_group[j] * a.hyp_stride];
+}
+
+// The fused level of either sweep (update_v, fm_learn_vb.h:577-644; update_w, :527-574; with
+// NEXT also the q-cache of the next factor, add_main_q :354-381). One workgroup per feature
+// column of the level. Entries i = tid + u*BLOCK for u < R are gathered once (one 64-B record
+// each) and kept in registers from the stats pass to the write-back; longer columns re-gather
+// the overflow entries.
+template <int BLOCK, int R, bool IS_W, int P, bool NEXT>
+DEVI void level_fused_body(LevelArgs a)
 {
 	__shared__ double lds[2 * (BLOCK / 64)];
 	const uint32_t j = level_feat(a, blockIdx.x);
@@ -69,41 +80,52 @@ __global__ __launch_bounds__(BLOCK) void k_v_level_fused(LevelArgs a)
 	}
 #pragma unroll
 	for (int u = 0; u < R; ++u) load_rec(a.rows, row[u] & ROW_MASK, rec[u]);
-	double vm = 0.0, vs = 0.0;
+	double s1 = 0.0, s2 = 0.0;
 #pragma unroll
 	for (int u = 0; u < R; ++u)
-		if (threadIdx.x + u * BLOCK < n) v_stat(xv[u], E(rec[u]), Q<P>(rec[u]), TQ<P>(rec[u]), mo, so, vm, vs);
+		if (threadIdx.x + u * BLOCK < n) vb_stat<IS_W, P>(rec[u], xv[u], mo, so, s1, s2);
 	for (uint32_t i = threadIdx.x + R * BLOCK; i < n; i += BLOCK) {
 		const uint2 ent = col[i];
 		Rec v;
 		load_rec(a.rows, ent.x & ROW_MASK, v);
-		v_stat(ent_x(ent), E(v), Q<P>(v), TQ<P>(v), mo, so, vm, vs);
+		vb_stat<IS_W, P>(v, ent_x(ent), mo, so, s1, s2);
 	}
-	block_sum2<BLOCK>(vm, vs, lds);
+	block_sum2<BLOCK>(s1, s2, lds);
 
 	double mu, sig;
-	const double sv_g = (a.hyp_uniform ? a.hyp0 : a.hyp[(size_t)a.attr_group[j] * a.hyp_stride]);
-	const bool go = v_post(vm, vs, sv_g, a.alpha, mo, so, mu, sig, a.counters, threadIdx.x == 0);
+	const bool go = vb_post<IS_W>(s1, s2, level_hyp(a, j), a.alpha, mo, so, mu, sig, a.counters, threadIdx.x == 0);
 	if (threadIdx.x == 0) a.ms[(size_t)j * a.ms_stride] = make_double2(mu, sig);
 	if (!go && !NEXT) return;
 	if (a.dup[j]) {
 		__syncthreads();
-		if (threadIdx.x == 0) v_apply_serial<P, NEXT>(col, n, a.rows, go, mo, so, mu, sig, nx, a.first_mask);
+		if (threadIdx.x == 0) apply_serial<IS_W, P, NEXT>(col, n, a.rows, go, mo, so, mu, sig, nx, a.first_mask);
 		return;
 	}
 #pragma unroll
 	for (int u = 0; u < R; ++u)
 		if (threadIdx.x + u * BLOCK < n) {
-			v_apply<P, NEXT>(rec[u], xv[u], (row[u] & a.first_mask) != 0, go, mo, so, mu, sig, nx);
+			vb_apply<IS_W, P, NEXT>(rec[u], xv[u], (row[u] & a.first_mask) != 0, go, mo, so, mu, sig, nx);
 			store_rec(a.rows, row[u] & ROW_MASK, rec[u]);
 		}
 	for (uint32_t i = threadIdx.x + R * BLOCK; i < n; i += BLOCK) {
 		const uint2 ent = col[i];
 		Rec v;
 		load_rec(a.rows, ent.x & ROW_MASK, v);
-		v_apply<P, NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
+		vb_apply<IS_W, P, NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
 		store_rec(a.rows, ent.x & ROW_MASK, v);
 	}
+}
+
+template <int BLOCK, int R, int P, bool NEXT>
+__global__ __launch_bounds__(BLOCK) void k_v_level_fused(LevelArgs a)
+{
+	level_fused_body<BLOCK, R, false, P, NEXT>(a);
+}
+
+template <int BLOCK, int R, bool NEXT>
+__global__ __launch_bounds__(BLOCK) void k_w_level_fused(LevelArgs a)
+{
+	level_fused_body<BLOCK, R, true, 0, NEXT>(a);
 }
 
 // Long columns on the column-gather layout (as lord_long on the level store): the fused
@@ -124,8 +146,7 @@ __global__ __launch_bounds__(256) void k_col_long_stats(LevelArgs a)
 		const uint2 ent = col[i];
 		Rec v;
 		load_rec(a.rows, ent.x & ROW_MASK, v);
-		if constexpr (IS_W) w_stat(ent_x(ent), E(v), msj.x, s1, s2);
-		else v_stat(ent_x(ent), E(v), Q<P>(v), TQ<P>(v), msj.x, msj.y, s1, s2);
+		vb_stat<IS_W, P>(v, ent_x(ent), msj.x, msj.y, s1, s2);
 	}
 	block_sum2<256>(s1, s2, lds);
 	if (threadIdx.x == 0) {
@@ -149,26 +170,23 @@ __global__ __launch_bounds__(256) void k_col_long_correct(LevelArgs a)
 	const double2 msj = a.seg_part[2 * g.seg0 + 1];
 	const double mo = msj.x, so = msj.y;
 	const double2 nx = NEXT ? a.ms_next[(size_t)j * a.ms_stride_next] : make_double2(0.0, 0.0);
-	const double hyp = (a.hyp_uniform ? a.hyp0 : a.hyp[(size_t)a.attr_group[j] * a.hyp_stride]);
 	const bool lead = threadIdx.x == 0 && blockIdx.x == g.seg0;
 	double mu, sig;
-	const bool go = IS_W ? w_post(s1, s2, hyp, a.alpha, mo, so, mu, sig, a.counters, lead)
-	                     : v_post(s1, s2, hyp, a.alpha, mo, so, mu, sig, a.counters, lead);
+	const bool go = vb_post<IS_W>(s1, s2, level_hyp(a, j), a.alpha, mo, so, mu, sig, a.counters, lead);
 	if (lead) a.ms[(size_t)j * a.ms_stride] = make_double2(mu, sig);
 	if (!go && !NEXT) return;
 	for (uint32_t i = threadIdx.x; i < g.len; i += 256) {
 		const uint2 ent = col[i];
 		Rec v;
 		load_rec(a.rows, ent.x & ROW_MASK, v);
-		if constexpr (IS_W) w_apply<NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
-		else v_apply<P, NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
+		vb_apply<IS_W, P, NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
 		store_rec(a.rows, ent.x & ROW_MASK, v);
 	}
 }
 
 // split form for the row-sharded multi-GPU mode: stats -> (all-reduce) -> correction
-template <int BLOCK, int P>
-__global__ __launch_bounds__(BLOCK) void k_v_level_stats(LevelArgs a)
+template <int BLOCK, bool IS_W, int P>
+DEVI void level_stats_body(LevelArgs a)
 {
 	__shared__ double lds[2 * (BLOCK / 64)];
 	const uint32_t j = level_feat(a, blockIdx.x);
@@ -176,19 +194,19 @@ __global__ __launch_bounds__(BLOCK) void k_v_level_stats(LevelArgs a)
 	const uint32_t n = (uint32_t)(a.col_ptr[j + 1] - cb);
 	const uint2 *col = a.csc + cb;
 	const double2 msj = a.ms[(size_t)j * a.ms_stride];
-	double vm = 0.0, vs = 0.0;
+	double s1 = 0.0, s2 = 0.0;
 	for (uint32_t i = threadIdx.x; i < n; i += BLOCK) {
 		const uint2 ent = col[i];
 		Rec v;
 		load_rec(a.rows, ent.x & ROW_MASK, v);
-		v_stat(ent_x(ent), E(v), Q<P>(v), TQ<P>(v), msj.x, msj.y, vm, vs);
+		vb_stat<IS_W, P>(v, ent_x(ent), msj.x, msj.y, s1, s2);
 	}
-	block_sum2<BLOCK>(vm, vs, lds);
-	if (threadIdx.x == 0) a.stats[blockIdx.x] = make_double2(vm, vs);
+	block_sum2<BLOCK>(s1, s2, lds);
+	if (threadIdx.x == 0) a.stats[blockIdx.x] = make_double2(s1, s2);
 }
 
-template <int BLOCK, int P, bool NEXT>
-__global__ __launch_bounds__(BLOCK) void k_v_level_correct(LevelArgs a)
+template <int BLOCK, bool IS_W, int P, bool NEXT>
+DEVI void level_correct_body(LevelArgs a)
 {
 	const uint32_t j = level_feat(a, blockIdx.x);
 	const uint64_t cb = a.col_ptr[j];
@@ -200,153 +218,47 @@ __global__ __launch_bounds__(BLOCK) void k_v_level_correct(LevelArgs a)
 	double2 nx = make_double2(0.0, 0.0);
 	if constexpr (NEXT) nx = a.ms_next[(size_t)j * a.ms_stride_next];
 	double mu, sig;
-	const double sv_g = (a.hyp_uniform ? a.hyp0 : a.hyp[(size_t)a.attr_group[j] * a.hyp_stride]);
-	const bool go = v_post(st.x, st.y, sv_g, a.alpha, msj.x, msj.y, mu, sig, a.counters, threadIdx.x == 0);
-	// every wave has used the old value (v_post above) before it is overwritten: without the
+	const bool go = vb_post<IS_W>(st.x, st.y, level_hyp(a, j), a.alpha, msj.x, msj.y, mu, sig, a.counters, threadIdx.x == 0);
+	// every wave has used the old value (vb_post above) before it is overwritten: without the
 	// barrier a wave of this workgroup could still read the new one as its "old"
 	__syncthreads();   // [raw-barrier]
 	if (threadIdx.x == 0) a.ms[(size_t)j * a.ms_stride] = make_double2(mu, sig);
 	if (!go && !NEXT) return;
 	if (a.dup[j]) {
-		if (threadIdx.x == 0) v_apply_serial<P, NEXT>(col, n, a.rows, go, msj.x, msj.y, mu, sig, nx, a.first_mask);
+		if (threadIdx.x == 0) apply_serial<IS_W, P, NEXT>(col, n, a.rows, go, msj.x, msj.y, mu, sig, nx, a.first_mask);
 		return;
 	}
 	for (uint32_t i = threadIdx.x; i < n; i += BLOCK) {
 		const uint2 ent = col[i];
 		Rec v;
 		load_rec(a.rows, ent.x & ROW_MASK, v);
-		v_apply<P, NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, msj.x, msj.y, mu, sig, nx);
+		vb_apply<IS_W, P, NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, msj.x, msj.y, mu, sig, nx);
 		store_rec(a.rows, ent.x & ROW_MASK, v);
 	}
 }
 
-// ------------------------------------------------------------------------------------
-// w sweep: update_w (fm_learn_vb.h:527-574). With NEXT the sweep also accumulates the
-// q-cache of factor 0 into slot 0 (add_main_q(train, 0), fm_learn_vb.h:354-381).
-template <bool NEXT>
-DEVI void w_apply_serial(const uint2 *col, uint32_t n, RowRec *rows, bool go, double mo, double so, double mu,
-                         double sig, double2 nx, uint32_t fm)
+template <int BLOCK, int P>
+__global__ __launch_bounds__(BLOCK) void k_v_level_stats(LevelArgs a)
 {
-	for (uint32_t i = 0; i < n; ++i) {
-		const uint2 ent = col[i];
-		Rec v;
-		load_rec(rows, ent.x & ROW_MASK, v);
-		w_apply<NEXT>(v, ent_x(ent), (ent.x & fm) != 0, go, mo, so, mu, sig, nx);
-		store_rec(rows, ent.x & ROW_MASK, v);
-	}
-}
-
-template <int BLOCK, int R, bool NEXT>
-__global__ __launch_bounds__(BLOCK) void k_w_level_fused(LevelArgs a)
-{
-	__shared__ double lds[2 * (BLOCK / 64)];
-	const uint32_t j = level_feat(a, blockIdx.x);
-	const uint64_t cb = a.col_ptr[j];
-	const uint32_t n = (uint32_t)(a.col_ptr[j + 1] - cb);
-	if (a.long_min && n > a.long_min && !a.dup[j]) return;   // segment kernels (col_long)
-	const uint2 *col = a.csc + cb;
-	const double2 msj = a.ms[(size_t)j * a.ms_stride];
-	const double mo = msj.x, so = msj.y;
-	double2 nx = make_double2(0.0, 0.0);
-	if constexpr (NEXT) nx = a.ms_next[(size_t)j * a.ms_stride_next];
-	uint32_t row[R];
-	float xv[R];
-	Rec rec[R];
-#pragma unroll
-	for (int u = 0; u < R; ++u) {
-		const uint32_t i = threadIdx.x + u * BLOCK;
-		// unconditional, index clamped (entries and records past the column are never used;
-		// an empty column reads row 0): a guarded load is sunk into its branch and waited on
-		// there, so the entries and then the records would arrive one after the other
-		const uint2 ent = n ? col[min(i, n - 1)] : make_uint2(0u, 0u);
-		row[u] = ent.x;
-		xv[u] = ent_x(ent);
-	}
-#pragma unroll
-	for (int u = 0; u < R; ++u) load_rec(a.rows, row[u] & ROW_MASK, rec[u]);
-	double wm = 0.0, ws = 0.0;
-#pragma unroll
-	for (int u = 0; u < R; ++u)
-		if (threadIdx.x + u * BLOCK < n) w_stat(xv[u], E(rec[u]), mo, wm, ws);
-	for (uint32_t i = threadIdx.x + R * BLOCK; i < n; i += BLOCK) {
-		const uint2 ent = col[i];
-		w_stat(ent_x(ent), a.rows[ent.x & ROW_MASK].e, mo, wm, ws);
-	}
-	block_sum2<BLOCK>(wm, ws, lds);
-	double mu, sig;
-	const double sw_g = (a.hyp_uniform ? a.hyp0 : a.hyp[(size_t)a.attr_group[j] * a.hyp_stride]);
-	const bool go = w_post(wm, ws, sw_g, a.alpha, mo, so, mu, sig, a.counters, threadIdx.x == 0);
-	if (threadIdx.x == 0) a.ms[(size_t)j * a.ms_stride] = make_double2(mu, sig);
-	if (!go && !NEXT) return;
-	if (a.dup[j]) {
-		__syncthreads();
-		if (threadIdx.x == 0) w_apply_serial<NEXT>(col, n, a.rows, go, mo, so, mu, sig, nx, a.first_mask);
-		return;
-	}
-#pragma unroll
-	for (int u = 0; u < R; ++u)
-		if (threadIdx.x + u * BLOCK < n) {
-			w_apply<NEXT>(rec[u], xv[u], (row[u] & a.first_mask) != 0, go, mo, so, mu, sig, nx);
-			store_rec(a.rows, row[u] & ROW_MASK, rec[u]);
-		}
-	for (uint32_t i = threadIdx.x + R * BLOCK; i < n; i += BLOCK) {
-		const uint2 ent = col[i];
-		Rec v;
-		load_rec(a.rows, ent.x & ROW_MASK, v);
-		w_apply<NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
-		store_rec(a.rows, ent.x & ROW_MASK, v);
-	}
+	level_stats_body<BLOCK, false, P>(a);
 }
 
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_w_level_stats(LevelArgs a)
 {
-	__shared__ double lds[2 * (BLOCK / 64)];
-	const uint32_t j = level_feat(a, blockIdx.x);
-	const uint64_t cb = a.col_ptr[j];
-	const uint32_t n = (uint32_t)(a.col_ptr[j + 1] - cb);
-	const uint2 *col = a.csc + cb;
-	const double mo = a.ms[(size_t)j * a.ms_stride].x;
-	double wm = 0.0, ws = 0.0;
-	for (uint32_t i = threadIdx.x; i < n; i += BLOCK) {
-		const uint2 ent = col[i];
-		w_stat(ent_x(ent), a.rows[ent.x & ROW_MASK].e, mo, wm, ws);
-	}
-	block_sum2<BLOCK>(wm, ws, lds);
-	if (threadIdx.x == 0) a.stats[blockIdx.x] = make_double2(wm, ws);
+	level_stats_body<BLOCK, true, 0>(a);
+}
+
+template <int BLOCK, int P, bool NEXT>
+__global__ __launch_bounds__(BLOCK) void k_v_level_correct(LevelArgs a)
+{
+	level_correct_body<BLOCK, false, P, NEXT>(a);
 }
 
 template <int BLOCK, bool NEXT>
 __global__ __launch_bounds__(BLOCK) void k_w_level_correct(LevelArgs a)
 {
-	const uint32_t j = level_feat(a, blockIdx.x);
-	const uint64_t cb = a.col_ptr[j];
-	const uint32_t n = (uint32_t)(a.col_ptr[j + 1] - cb);
-	const uint2 *col = a.csc + cb;
-	debug_skew(a.skew);
-	const double2 msj = a.ms[(size_t)j * a.ms_stride];
-	const double2 st = a.stats[blockIdx.x];
-	double2 nx = make_double2(0.0, 0.0);
-	if constexpr (NEXT) nx = a.ms_next[(size_t)j * a.ms_stride_next];
-	double mu, sig;
-	const double sw_g = (a.hyp_uniform ? a.hyp0 : a.hyp[(size_t)a.attr_group[j] * a.hyp_stride]);
-	const bool go = w_post(st.x, st.y, sw_g, a.alpha, msj.x, msj.y, mu, sig, a.counters, threadIdx.x == 0);
-	// every wave has used the old value (w_post above) before it is overwritten: without the
-	// barrier a wave of this workgroup could still read the new one as its "old"
-	__syncthreads();   // [raw-barrier]
-	if (threadIdx.x == 0) a.ms[(size_t)j * a.ms_stride] = make_double2(mu, sig);
-	if (!go && !NEXT) return;
-	if (a.dup[j]) {
-		if (threadIdx.x == 0) w_apply_serial<NEXT>(col, n, a.rows, go, msj.x, msj.y, mu, sig, nx, a.first_mask);
-		return;
-	}
-	for (uint32_t i = threadIdx.x; i < n; i += BLOCK) {
-		const uint2 ent = col[i];
-		Rec v;
-		load_rec(a.rows, ent.x & ROW_MASK, v);
-		w_apply<NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, msj.x, msj.y, mu, sig, nx);
-		store_rec(a.rows, ent.x & ROW_MASK, v);
-	}
+	level_correct_body<BLOCK, true, 0, NEXT>(a);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1383,20 +1295,15 @@ hipError_t stall(const uint32_t *flag, hipStream_t s)
 
 // Column-length-adaptive launch shape: threads per column and entries held per thread
 // from the level's mean column length (dispatch_shape, vbfm_device.h); the sweep variant from
-// dispatch_sweep (the v kernels take no IS_W: they ignore it).
-hipError_t v_level_fused(const LevelArgs &a, hipStream_t s)
+// dispatch_sweep (the w shells take no P: the w sweep always runs as slot 0).
+hipError_t level_fused(const LevelArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	dispatch_sweep(false, a.slot, a.ms_next != nullptr, [&](auto, auto P, auto N) {
-		dispatch_shape(a.avg_len, [&](auto B, auto R) { k_v_level_fused<B(), R(), P(), N()><<<a.nfeat, B(), 0, s>>>(a); });
-	});
-	return hipGetLastError();
-}
-hipError_t w_level_fused(const LevelArgs &a, hipStream_t s)
-{
-	if (a.nfeat == 0) return hipSuccess;
-	dispatch_bool(a.ms_next != nullptr, [&](auto N) {
-		dispatch_shape(a.avg_len, [&](auto B, auto R) { k_w_level_fused<B(), R(), N()><<<a.nfeat, B(), 0, s>>>(a); });
+	dispatch_sweep(is_w, a.slot, a.ms_next != nullptr, [&](auto W, auto P, auto N) {
+		dispatch_shape(a.avg_len, [&](auto B, auto R) {
+			if constexpr (W()) k_w_level_fused<B(), R(), N()><<<a.nfeat, B(), 0, s>>>(a);
+			else k_v_level_fused<B(), R(), P(), N()><<<a.nfeat, B(), 0, s>>>(a);
+		});
 	});
 	return hipGetLastError();
 }
@@ -1409,32 +1316,25 @@ hipError_t col_long(const LevelArgs &a, int is_w, hipStream_t s)
 	});
 	return hipGetLastError();
 }
-hipError_t v_level_stats(const LevelArgs &a, hipStream_t s)
+hipError_t level_stats(const LevelArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
 	// the fused kernel's BLOCK: the same reduction tree, so the split form equals the fused one
-	dispatch_wp(false, a.slot, [&](auto, auto P) {
-		dispatch_shape(a.avg_len, [&](auto B, auto) { k_v_level_stats<B(), P()><<<a.nfeat, B(), 0, s>>>(a); });
+	dispatch_wp(is_w, a.slot, [&](auto W, auto P) {
+		dispatch_shape(a.avg_len, [&](auto B, auto) {
+			if constexpr (W()) k_w_level_stats<B()><<<a.nfeat, B(), 0, s>>>(a);
+			else k_v_level_stats<B(), P()><<<a.nfeat, B(), 0, s>>>(a);
+		});
 	});
 	return hipGetLastError();
 }
-hipError_t v_level_correct(const LevelArgs &a, hipStream_t s)
+hipError_t level_correct(const LevelArgs &a, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
-	dispatch_sweep(false, a.slot, a.ms_next != nullptr,
-	               [&](auto, auto P, auto N) { k_v_level_correct<256, P(), N()><<<a.nfeat, 256, 0, s>>>(a); });
-	return hipGetLastError();
-}
-hipError_t w_level_stats(const LevelArgs &a, hipStream_t s)
-{
-	if (a.nfeat == 0) return hipSuccess;
-	dispatch_shape(a.avg_len, [&](auto B, auto) { k_w_level_stats<B()><<<a.nfeat, B(), 0, s>>>(a); });
-	return hipGetLastError();
-}
-hipError_t w_level_correct(const LevelArgs &a, hipStream_t s)
-{
-	if (a.nfeat == 0) return hipSuccess;
-	dispatch_bool(a.ms_next != nullptr, [&](auto N) { k_w_level_correct<256, N()><<<a.nfeat, 256, 0, s>>>(a); });
+	dispatch_sweep(is_w, a.slot, a.ms_next != nullptr, [&](auto W, auto P, auto N) {
+		if constexpr (W()) k_w_level_correct<256, N()><<<a.nfeat, 256, 0, s>>>(a);
+		else k_v_level_correct<256, P(), N()><<<a.nfeat, 256, 0, s>>>(a);
+	});
 	return hipGetLastError();
 }
 

@@ -28,76 +28,6 @@
 
 namespace {
 
-// What one level does to one record, as a policy of the staging loops below.
-// VB (update_v :587-596/:623-643, update_w :534-539/:567-573): statistics, then the
-// correction with the new posterior; NEXT adds the q-cache term of the next factor.
-template <bool IS_W, int P, bool NEXT>
-struct VbOp {
-	double mo, so, mu, sig;
-	double2 nx;
-	bool go;
-	DEVI void stat(Rec &v, float x, double &s1, double &s2) const
-	{
-		if constexpr (IS_W) w_stat(x, E(v), mo, s1, s2);
-		else v_stat(x, E(v), Q<P>(v), TQ<P>(v), mo, so, s1, s2);
-	}
-	DEVI void apply(Rec &v, float x, bool first) const
-	{
-		if constexpr (IS_W) w_apply<NEXT>(v, x, first, go, mo, so, mu, sig, nx);
-		else v_apply<P, NEXT>(v, x, first, go, mo, so, mu, sig, nx);
-	}
-};
-
-template <bool IS_W>
-DEVI bool vb_post(double s1, double s2, double hyp, double alpha, double mo, double so, double &mu, double &sig,
-                  uint32_t *counters, bool leader)
-{
-	if constexpr (IS_W) return w_post(s1, s2, hyp, alpha, mo, so, mu, sig, counters, leader);
-	else return v_post(s1, s2, hyp, alpha, mo, so, mu, sig, counters, leader);
-}
-
-// MCMC / ALS (draw_v :785-792/:826-834, draw_w :674-679/:712-717); row caches e (= yhat - y)
-// and the q-cache of factor f in slot P, of factor f+1 (or 0 after draw_w) in the other
-template <bool IS_W, int P, bool NEXT>
-struct McOp {
-	double vo, v, vn;
-	bool go;
-	double vp = 0.0;   // v_{f-1}[j] for the fused train re-prediction (McArgs::pk), pk 0: off
-	int pk = 0;
-	DEVI void stat(Rec &r, float x, double &s1, double &s2) const
-	{
-		if constexpr (IS_W) {
-			s1 += x * (E(r) - vo * x);
-			s2 += x * x;                                       // fp32 product
-		} else {
-			const double h = x * (Q<P>(r) - x * vo);
-			s1 += h * E(r);
-			s2 += h * h;
-		}
-	}
-	DEVI void apply(Rec &r, float x, bool first) const
-	{
-		if (go) {
-			if constexpr (IS_W) {
-				const double h = x;
-				E(r) -= h * (vo - v);
-			} else {
-				const double h = x * (Q<P>(r) - x * vo);
-				Q<P>(r) -= x * (vo - v);
-				E(r) -= h * (vo - v);
-			}
-		}
-		if constexpr (NEXT) {
-			const double a = vn * x;
-			double &q = IS_W ? Q<0>(r) : Q<1 - P>(r);
-			q = first ? 0.0 + a : q + a;
-		}
-		if constexpr (!IS_W) {
-			if (pk) mc_pred_acc(TQ<0>(r), TZ<0>(r), T(r), x, first, vp, pk);   // MCMC leaves tq, tz, t free
-		}
-	}
-};
-
 // ---- LDS staging -------------------------------------------------------------------------
 // A run of records moves between HBM and LDS four lanes per 64-B record (one 16-B piece
 // each), so that every wave instruction reads or writes whole records: the scattered writes
@@ -1025,9 +955,7 @@ DEVI void mc_apply_pending(Rec &r, const PostT &t, float x)
 template <bool IS_W, int P>
 DEVI void mc_add_next_q(Rec &r, float x, bool first, double vn)
 {
-	const double aq = vn * x;
-	double &q = IS_W ? Q<0>(r) : Q<1 - P>(r);
-	q = first ? 0.0 + aq : q + aq;
+	mc_qacc<IS_W ? 0 : 1 - P>(r, x, first, vn);
 }
 
 template <int BLOCK, int R, bool IS_W, int P, bool NEXT, bool PAY8>

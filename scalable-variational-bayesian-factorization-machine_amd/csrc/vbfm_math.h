@@ -1,8 +1,10 @@
-// vbfm_math.h -- device arithmetic shared by the sweep kernels of both row layouts
-// (vbfm_kernels.hip: column-gather; vbfm_lorder.hip: level-ordered row store): deterministic
-// wave / block reductions, the 64-B row record accessors, and the per-entry statistics,
-// posterior + guards and correction of update_v / update_w restated expression by
-// expression from the reference (citations relative to /root/reference).
+// vbfm_math.h -- device arithmetic shared by the sweep kernels of both row layouts and both
+// learners (vbfm_kernels.hip, vbfm_mcmc.hip: column-gather; vbfm_lorder.hip: level-ordered row
+// store; vbfm_online.hip): deterministic wave / block reductions, the 64-B row record accessors
+// (a loaded Rec, or the RowRec in memory), and the per-entry statistics, posterior + guards and
+// correction of update_v / update_w restated expression by expression from the reference
+// (citations relative to the reference's root). Each formula is written once: v_* / w_* below, then
+// vb_stat / vb_apply / vb_post and VbOp, which pick the sweep by IS_W for every kernel body.
 #pragma once
 #include "vbfm_device.h"
 
@@ -91,6 +93,13 @@ template <int S> DEVI double &TQ(Rec &v) { return S == 0 ? v[1].x : v[3].x; }
 template <int S> DEVI double &TZ(Rec &v) { return S == 0 ? v[1].y : v[3].y; }
 DEVI double &E(Rec &v) { return v[0].x; }
 DEVI double &T(Rec &v) { return v[2].x; }
+
+// the same fields of a record in memory (a kernel that updates single fields in place)
+template <int S> DEVI double &Q(RowRec &r) { return S == 0 ? r.q : r.q1; }
+template <int S> DEVI double &TQ(RowRec &r) { return S == 0 ? r.tq : r.tq1; }
+template <int S> DEVI double &TZ(RowRec &r) { return S == 0 ? r.tz : r.tz1; }
+DEVI double &E(RowRec &r) { return r.e; }
+DEVI double &T(RowRec &r) { return r.t; }
 
 // add_main_q term of one entry into slot S (fm_learn_vb.h:374-376); `first` marks the
 // row's smallest feature, where the reference's zeroed cache (:411-415) starts the sum
@@ -203,6 +212,96 @@ DEVI void w_apply(Rec &v, float x, bool first, bool go, double mo, double so, do
 		T(v) += h * h * (sig - so);
 	}
 	if constexpr (NEXT) qacc<0>(v, x, first, nx);
+}
+
+// ------------------------------------------------------------------------------------
+// What one level does to one record, as a policy of the kernel bodies of both layouts.
+// VB (update_v :587-596/:623-643, update_w :534-539/:567-573): statistics, then the
+// correction with the new posterior; NEXT adds the q-cache term of the next factor.
+template <bool IS_W, int P>
+DEVI void vb_stat(Rec &v, float x, double mo, double so, double &s1, double &s2)
+{
+	if constexpr (IS_W) w_stat(x, E(v), mo, s1, s2);
+	else v_stat(x, E(v), Q<P>(v), TQ<P>(v), mo, so, s1, s2);
+}
+
+template <bool IS_W, int P, bool NEXT>
+DEVI void vb_apply(Rec &v, float x, bool first, bool go, double mo, double so, double mu, double sig, double2 nx)
+{
+	if constexpr (IS_W) w_apply<NEXT>(v, x, first, go, mo, so, mu, sig, nx);
+	else v_apply<P, NEXT>(v, x, first, go, mo, so, mu, sig, nx);
+}
+
+template <bool IS_W, int P, bool NEXT>
+struct VbOp {
+	double mo, so, mu, sig;
+	double2 nx;
+	bool go;
+	DEVI void stat(Rec &v, float x, double &s1, double &s2) const { vb_stat<IS_W, P>(v, x, mo, so, s1, s2); }
+	DEVI void apply(Rec &v, float x, bool first) const
+	{
+		vb_apply<IS_W, P, NEXT>(v, x, first, go, mo, so, mu, sig, nx);
+	}
+};
+
+template <bool IS_W>
+DEVI bool vb_post(double s1, double s2, double hyp, double alpha, double mo, double so, double &mu, double &sig,
+                  uint32_t *counters, bool leader)
+{
+	if constexpr (IS_W) return w_post(s1, s2, hyp, alpha, mo, so, mu, sig, counters, leader);
+	else return v_post(s1, s2, hyp, alpha, mo, so, mu, sig, counters, leader);
+}
+
+// ------------------------------------------------------------------------------------
+// online VB (fm_learn_vb_online.h update_w :499-556, update_v :558-627): one entry's statistics
+// are VB's; each becomes the natural-parameter terms
+//   (1 - new_j) * sigma_old + new_j * (sigma_g + alpha * col_count * sigma_sqr)
+//   (1 - new_j) * mu_old    + new_j * col_count * alpha * mean
+// with keep = (1 - rho) * nat_old, acc = alpha * col_count, rca = rho * col_count * alpha
+template <bool IS_W, int P>
+DEVI void ov_stat(Rec &r, float x, double mo, double so, double hyp, double rho, double keep_m, double keep_s,
+                  double acc, double rca, double &eta1, double &eta2)
+{
+	if constexpr (IS_W) {
+		const double w_mean = x * (E(r) + x * mo);
+		const double w_sigma_sqr = x * x;   // fp32 product
+		eta2 += keep_s + rho * (hyp + acc * w_sigma_sqr);
+		eta1 += keep_m + rca * w_mean;
+	} else {
+		double vm = 0.0, vs = 0.0;
+		v_stat(x, E(r), Q<P>(r), TQ<P>(r), mo, so, vm, vs);
+		eta2 += keep_s + rho * (hyp + acc * vs);
+		eta1 += keep_m + rca * vm;
+	}
+}
+
+// the new natural parameter = the terms' mean over the column's n batch entries, the posterior
+// from it and the guards with their counters; returns false when the correction is skipped
+template <bool IS_W>
+DEVI bool ov_post(double eta1, double eta2, uint32_t n, double mo, double so, double &nmu, double &nsig, double &mu,
+                  double &sig, uint32_t *counters, bool leader)
+{
+	nmu = eta1 / n;
+	nsig = eta2 / n;
+	mu = nmu / nsig;
+	sig = 1 / nsig;
+	bool go = true;
+	const int c_sig = IS_W ? CNT_NAN_SIGMA_W : CNT_NAN_SIGMA_V, c_nan = IS_W ? CNT_NAN_MU_W : CNT_NAN_MU_V,
+	          c_inf = IS_W ? CNT_INF_MU_W : CNT_INF_MU_V;
+	if (dnan(sig) || dinf(sig)) {
+		sig = so;
+		if (leader) atomicAdd(&counters[c_sig], 1u);
+	}
+	if (dnan(mu)) {
+		if (leader) atomicAdd(&counters[c_nan], 1u);
+		mu = mo;
+		go = false;
+	} else if (dinf(mu)) {
+		if (leader) atomicAdd(&counters[c_inf], 1u);
+		mu = mo;
+		go = false;
+	}
+	return go;
 }
 
 }  // namespace

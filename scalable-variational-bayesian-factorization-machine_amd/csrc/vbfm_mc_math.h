@@ -1,12 +1,9 @@
 // vbfm_mc_math.h -- device arithmetic of the MCMC / ALS draws shared by the column-gather
 // kernels (vbfm_mcmc.hip) and the level-ordered store (vbfm_lorder.hip): the counter-based
-// normals of device-RNG mode and the conditional draw of one parameter (fm_learn_mcmc.h).
+// normals of device-RNG mode, the conditional draw of one parameter (fm_learn_mcmc.h) and McOp,
+// the per-entry statistics and correction of draw_v / draw_w for either kind of record.
 #pragma once
-#include "vbfm_device.h"
-
-#ifndef DEVI
-#define DEVI __device__ __forceinline__
-#endif
+#include "vbfm_math.h"
 
 namespace {
 
@@ -98,5 +95,54 @@ DEVI void mc_pred_acc(double &s1, double &ev, double &q2, float x, bool first, d
 		q2 = q2 - b;
 	}
 }
+
+// q-cache term of the next factor into slot S: cache[i].q += v_if * x_li (fm_learn_mcmc.h:404),
+// restarted at the row's first entry
+template <int S, class R> DEVI void mc_qacc(R &r, float x, bool first, double vn)
+{
+	const double a = vn * x;
+	double &q = Q<S>(r);
+	q = first ? 0.0 + a : q + a;
+}
+
+// What one level of a draw sweep does to one record, as VbOp (vbfm_math.h) generic over the
+// record: a loaded Rec (level store) or a RowRec updated in place, field by field (column-gather).
+// MCMC / ALS (draw_v :785-792/:826-834, draw_w :674-679/:712-717); row caches e (= yhat - y)
+// and the q-cache of factor f in slot P, of factor f+1 (or 0 after draw_w) in the other
+template <bool IS_W, int P, bool NEXT>
+struct McOp {
+	double vo, v, vn;
+	bool go;
+	double vp = 0.0;   // v_{f-1}[j] for the fused train re-prediction (McArgs::pk), pk 0: off
+	int pk = 0;
+	template <class R> DEVI void stat(R &r, float x, double &s1, double &s2) const
+	{
+		if constexpr (IS_W) {
+			s1 += x * (E(r) - vo * x);
+			s2 += x * x;                                       // fp32 product
+		} else {
+			const double h = x * (Q<P>(r) - x * vo);
+			s1 += h * E(r);
+			s2 += h * h;
+		}
+	}
+	template <class R> DEVI void apply(R &r, float x, bool first) const
+	{
+		if (go) {
+			if constexpr (IS_W) {
+				const double h = x;
+				E(r) -= h * (vo - v);
+			} else {
+				const double h = x * (Q<P>(r) - x * vo);
+				Q<P>(r) -= x * (vo - v);
+				E(r) -= h * (vo - v);
+			}
+		}
+		if constexpr (NEXT) mc_qacc<IS_W ? 0 : 1 - P>(r, x, first, vn);
+		if constexpr (!IS_W) {
+			if (pk) mc_pred_acc(TQ<0>(r), TZ<0>(r), T(r), x, first, vp, pk);   // MCMC leaves tq, tz, t free
+		}
+	}
+};
 
 }  // namespace

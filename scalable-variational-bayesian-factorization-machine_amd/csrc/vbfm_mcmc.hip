@@ -1,75 +1,25 @@
 // vbfm_mcmc.hip -- CDNA4 kernels of the MCMC / ALS learner (fm_learn_mcmc, -method mcmc|als).
 //
 // Same structure as the VB sweep (vbfm_kernels.hip): dependency levels, one workgroup per
-// feature column, deterministic block reductions, the q-cache of factor f+1 accumulated
-// while factor f is swept (slot f%2 / (f+1)%2 of the row record), bit-exact per-row sums.
+// feature column (mc_level_body, one body for draw_v and draw_w over McOp of vbfm_mc_math.h;
+// k_mc_v_level / k_mc_w_level are its shells), deterministic block reductions (vbfm_math.h),
+// the q-cache of factor f+1 accumulated while factor f is swept (slot f%2 / (f+1)%2 of the row
+// record), bit-exact per-row sums.
 // Row cache convention of the MCMC learner: e = yhat - y (fm_learn_mcmc_simultaneous.h:76-80),
 // kept in RowRec::e; the q-cache is RowRec::q (slot 0) / RowRec::q1 (slot 1).
 // Random numbers: z[j] holds the standard normal the reference's stream supplies for
 // feature j (host replay of glibc rand(), see vbfm_rng.h), or -- in device-RNG mode -- a
 // counter-based normal keyed by (seed, iteration, factor, feature), the same on every shard.
-#include "vbfm_device.h"
-
-#define DEVI __device__ __forceinline__
 #include "vbfm_mc_math.h"
 
 namespace {
 
-DEVI double wave_sum(double v)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-	return v;
-}
-
-template <int BLOCK>
-DEVI void block_sum2(double &a, double &b, double *lds)
-{
-	a = wave_sum(a);
-	b = wave_sum(b);
-	if constexpr (BLOCK > 64) {
-		const int w = threadIdx.x >> 6;
-		if ((threadIdx.x & 63) == 0) { lds[2 * w] = a; lds[2 * w + 1] = b; }
-		__syncthreads();
-		a = lds[0]; b = lds[1];
-#pragma unroll
-		for (int i = 1; i < BLOCK / 64; ++i) { a += lds[2 * i]; b += lds[2 * i + 1]; }
-	}
-}
-
-template <int BLOCK>
-DEVI double block_sum1(double a, double *lds)
-{
-	a = wave_sum(a);
-	if constexpr (BLOCK > 64) {
-		const int w = threadIdx.x >> 6;
-		__syncthreads();
-		if ((threadIdx.x & 63) == 0) lds[w] = a;
-		__syncthreads();
-		a = lds[0];
-#pragma unroll
-		for (int i = 1; i < BLOCK / 64; ++i) a += lds[i];
-	}
-	return a;
-}
-
-DEVI float ent_x(uint2 ent) { return __uint_as_float(ent.y); }
-// q-cache term of the next factor: cache[i].q += v_if * x_li (fm_learn_mcmc.h:404)
-template <int S> DEVI void mc_qacc(RowRec &r, float x, bool first, double vn)
-{
-	const double a = vn * x;
-	double &q = S == 0 ? r.q : r.q1;
-	q = first ? 0.0 + a : q + a;
-}
-
-template <int S> DEVI double mc_q(const RowRec &r) { return S == 0 ? r.q : r.q1; }
-template <int S> DEVI double &mc_qref(RowRec &r) { return S == 0 ? r.q : r.q1; }
-
-// ---- draw_v over one level -------------------------------------------------------------
+// ---- draw_v / draw_w over one level (draw_w: + q-cache of factor 0 into slot 0) -----------
 // MODE 0: fused; 1: per-feature statistics of this shard's rows into a.stats; 2: draw and
-// correction from the all-reduced a.stats (row-sharded multi-GPU form)
-template <int BLOCK, int P, bool NEXT, int MODE>
-__global__ __launch_bounds__(BLOCK) void k_mc_v_level(McArgs a)
+// correction from the all-reduced a.stats (row-sharded multi-GPU form). The records are
+// updated in place, field by field (McOp on a RowRec).
+template <int BLOCK, bool IS_W, int P, bool NEXT, int MODE>
+DEVI void mc_level_body(McArgs a)
 {
 	__shared__ double lds[2 * (BLOCK / 64)];
 	const uint32_t j = level_feat(a, blockIdx.x);
@@ -77,16 +27,13 @@ __global__ __launch_bounds__(BLOCK) void k_mc_v_level(McArgs a)
 	const uint32_t n = (uint32_t)(a.col_ptr[j + 1] - cb);
 	const uint2 *col = a.csc + cb;
 	if constexpr (MODE == 2) debug_skew(a.skew);
-	const double vo = a.par[(size_t)j * a.stride].x;
+	McOp<IS_W, P, NEXT> op;
+	op.vo = a.par[(size_t)j * a.stride].x;
 	double sm = 0.0, ss = 0.0;
 	if constexpr (MODE != 2) {
-		for (uint32_t i = threadIdx.x; i < n; i += BLOCK) {    // :785-792
+		for (uint32_t i = threadIdx.x; i < n; i += BLOCK) {    // :785-792 / :674-679
 			const uint2 ent = col[i];
-			const RowRec &r = a.rows[ent.x & ROW_MASK];
-			const float x = ent_x(ent);
-			const double h = x * (mc_q<P>(r) - x * vo);
-			sm += h * r.e;
-			ss += h * h;
+			op.stat(a.rows[ent.x & ROW_MASK], ent_x(ent), sm, ss);
 		}
 		block_sum2<BLOCK>(sm, ss, lds);
 		if constexpr (MODE == 1) {
@@ -98,94 +45,36 @@ __global__ __launch_bounds__(BLOCK) void k_mc_v_level(McArgs a)
 		sm = st.x;
 		ss = st.y;
 	}
-	const double vn = NEXT ? a.par_next[(size_t)j * a.next_stride].x : 0.0;
-	const double vp = a.pk ? a.par_prev[(size_t)j * a.next_stride].x : 0.0;   // fused re-prediction
+	op.vn = NEXT ? a.par_next[(size_t)j * a.next_stride].x : 0.0;
+	op.pk = IS_W ? 0 : a.pk;                                                // fused re-prediction
+	op.vp = op.pk ? a.par_prev[(size_t)j * a.next_stride].x : 0.0;
 	const uint32_t g = mc_group(a, j);
-	double v;
-	const bool go = mc_draw(sm, ss, vo, mc_lambda(a, g), mc_mu(a, g), a.alpha,
-	                        mc_z(a, j), a.z != nullptr, a.sample, true, v, a.counters, threadIdx.x == 0);
+	op.go = mc_draw(sm, ss, op.vo, mc_lambda(a, g), mc_mu(a, g), a.alpha,
+	                mc_z(a, j), a.z != nullptr, a.sample, !IS_W, op.v, a.counters, threadIdx.x == 0);
 	// MODE 2: every wave has used the old value (the draw) before it is overwritten
 	if constexpr (MODE == 2) __syncthreads();   // [raw-barrier]
-	if (threadIdx.x == 0) a.par[(size_t)j * a.stride].x = v;
-	if (!go && !NEXT && !a.pk) return;
-	auto entry = [&](uint2 ent) {
-		RowRec &r = a.rows[ent.x & ROW_MASK];
-		const float x = ent_x(ent);
-		const bool first = (ent.x & ROW_FIRST) != 0;
-		if (go) {
-			const double h = x * (mc_q<P>(r) - x * vo);
-			mc_qref<P>(r) -= x * (vo - v);
-			r.e -= h * (vo - v);
-		}
-		if constexpr (NEXT) mc_qacc<1 - P>(r, x, first, vn);
-		if (a.pk) mc_pred_acc(r.tq, r.tz, r.t, x, first, vp, a.pk);   // MCMC leaves tq, tz, t free
-	};
+	if (threadIdx.x == 0) a.par[(size_t)j * a.stride].x = op.v;
+	if (!op.go && !NEXT && !op.pk) return;
+	auto entry = [&](uint2 ent) { op.apply(a.rows[ent.x & ROW_MASK], ent_x(ent), (ent.x & ROW_FIRST) != 0); };
 	if (a.dup[j]) {   // a column listing a row twice: sequential, as the reference
 		__syncthreads();
 		if (threadIdx.x == 0)
 			for (uint32_t i = 0; i < n; ++i) entry(col[i]);
 		return;
 	}
-	for (uint32_t i = threadIdx.x; i < n; i += BLOCK) entry(col[i]);   // :826-834
+	for (uint32_t i = threadIdx.x; i < n; i += BLOCK) entry(col[i]);   // :826-834 / :712-717
 }
 
-// ---- draw_w over one level (+ q-cache of factor 0 into slot 0) ---------------------------
+template <int BLOCK, int P, bool NEXT, int MODE>
+__global__ __launch_bounds__(BLOCK) void k_mc_v_level(McArgs a)
+{
+	mc_level_body<BLOCK, false, P, NEXT, MODE>(a);
+}
+
 template <int BLOCK, bool NEXT, int MODE>
 __global__ __launch_bounds__(BLOCK) void k_mc_w_level(McArgs a)
 {
-	__shared__ double lds[2 * (BLOCK / 64)];
-	const uint32_t j = level_feat(a, blockIdx.x);
-	const uint64_t cb = a.col_ptr[j];
-	const uint32_t n = (uint32_t)(a.col_ptr[j + 1] - cb);
-	const uint2 *col = a.csc + cb;
-	if constexpr (MODE == 2) debug_skew(a.skew);
-	const double wo = a.par[(size_t)j * a.stride].x;
-	double sm = 0.0, ss = 0.0;
-	if constexpr (MODE != 2) {
-		for (uint32_t i = threadIdx.x; i < n; i += BLOCK) {    // :674-679
-			const uint2 ent = col[i];
-			const float x = ent_x(ent);
-			sm += x * (a.rows[ent.x & ROW_MASK].e - wo * x);
-			ss += x * x;                                       // fp32 product
-		}
-		block_sum2<BLOCK>(sm, ss, lds);
-		if constexpr (MODE == 1) {
-			if (threadIdx.x == 0) a.stats[blockIdx.x] = make_double2(sm, ss);
-			return;
-		}
-	} else {
-		const double2 st = a.stats[blockIdx.x];
-		sm = st.x;
-		ss = st.y;
-	}
-	const double vn = NEXT ? a.par_next[(size_t)j * a.next_stride].x : 0.0;
-	const uint32_t g = mc_group(a, j);
-	double w;
-	const bool go = mc_draw(sm, ss, wo, mc_lambda(a, g), mc_mu(a, g), a.alpha,
-	                        mc_z(a, j), a.z != nullptr, a.sample, false, w, a.counters, threadIdx.x == 0);
-	// MODE 2: every wave has used the old value (the draw) before it is overwritten
-	if constexpr (MODE == 2) __syncthreads();   // [raw-barrier]
-	if (threadIdx.x == 0) a.par[(size_t)j * a.stride].x = w;
-	if (!go && !NEXT) return;
-	if (a.dup[j]) {
-		__syncthreads();
-		if (threadIdx.x == 0)
-			for (uint32_t i = 0; i < n; ++i) {
-				const uint2 ent = col[i];
-				RowRec &r = a.rows[ent.x & ROW_MASK];
-				const float x = ent_x(ent);
-				if (go) { const double h = x; r.e -= h * (wo - w); }
-				if constexpr (NEXT) mc_qacc<0>(r, x, (ent.x & ROW_FIRST) != 0, vn);
-			}
-		return;
-	}
-	for (uint32_t i = threadIdx.x; i < n; i += BLOCK) {        // :712-717
-		const uint2 ent = col[i];
-		RowRec &r = a.rows[ent.x & ROW_MASK];
-		const float x = ent_x(ent);
-		if (go) { const double h = x; r.e -= h * (wo - w); }
-		if constexpr (NEXT) mc_qacc<0>(r, x, (ent.x & ROW_FIRST) != 0, vn);
-	}
+	mc_level_body<BLOCK, true, 0, NEXT, MODE>(a);
 }
 
 // parameters of attributes without train rows (j in [nf_train, D)): drawn from the prior,
@@ -375,7 +264,7 @@ namespace vbk {
 
 // threads per column from the level's mean column length (the VB kernels' shapes; the
 // level-ordered MCMC kernel uses the same BLOCK, so both reduce a column in one order)
-static hipError_t mc_level(const McArgs &a, int mode, bool is_w, hipStream_t s)
+hipError_t mc_level(const McArgs &a, int mode, int is_w, hipStream_t s)
 {
 	if (a.nfeat == 0) return hipSuccess;
 	dispatch_sweep(is_w, a.slot, a.par_next != nullptr, [&](auto W, auto P, auto N) {
@@ -388,9 +277,6 @@ static hipError_t mc_level(const McArgs &a, int mode, bool is_w, hipStream_t s)
 	});
 	return hipGetLastError();
 }
-
-hipError_t mc_v_level(const McArgs &a, int mode, hipStream_t s) { return mc_level(a, mode, false, s); }
-hipError_t mc_w_level(const McArgs &a, int mode, hipStream_t s) { return mc_level(a, mode, true, s); }
 
 hipError_t mc_prior(const McArgs &a, uint32_t j0, uint32_t j1, int is_v, hipStream_t s)
 {

@@ -356,12 +356,12 @@ void mc_sweep(vbfm_ctx *c, bool is_w, int f)
 			continue;
 		}
 		if (!c->split()) {
-			HIPCHK(is_w ? vbk::mc_w_level(a, 0, c->s) : vbk::mc_v_level(a, 0, c->s));
+			HIPCHK(vbk::mc_level(a, 0, is_w, c->s));
 		} else {   // row-sharded: statistics of this shard, summed over shards, identical draws
 			stats_exchange(c, a, [&](const McArgs &b) {
-				HIPCHK(is_w ? vbk::mc_w_level(b, 1, c->s) : vbk::mc_v_level(b, 1, c->s));
+				HIPCHK(vbk::mc_level(b, 1, is_w, c->s));
 			});
-			HIPCHK(is_w ? vbk::mc_w_level(a, 2, c->s) : vbk::mc_v_level(a, 2, c->s));
+			HIPCHK(vbk::mc_level(a, 2, is_w, c->s));
 		}
 		prof_end(c, p);
 	}

@@ -184,13 +184,28 @@ DEVI void group_sum2(double &a, double &b, double *lds)
 	}
 }
 
-// update_v (fm_learn_vb_online.h:558-627) for the batch's entries of one column per lane group.
-// The per-entry statistics are VB's (v_stat); each becomes the natural-parameter terms
-//   (1 - new_vj) * sigma_old + new_vj * (sigma_v_g + alpha * col_count * v_sigma_sqr)
-//   (1 - new_vj) * mu_old    + new_vj * col_count * alpha * v_mean
-// whose mean over the entries is the new natural parameter; the correction is VB's (v_apply).
-template <int G, int P, bool NEXT>
-__global__ __launch_bounds__(256) void k_ov_v_level(LevelArgs a)
+// what the column's leader writes after ov_post: the natural parameter, {mu, sigma}, and the
+// counts behind the step size -- t_wj / new_wj are advanced by the w column itself (:519-520),
+// t_vj by factor 0's sweep (tcount set, :396-399); tc = the count before this batch
+template <bool IS_W>
+DEVI void ov_commit(double2 *natp, double2 *msp, uint32_t *tcp, double *rhop, uint32_t tc, uint32_t n, double nmu,
+                    double nsig, double mu, double sig)
+{
+	*natp = make_double2(nmu, nsig);
+	*msp = make_double2(mu, sig);
+	if constexpr (IS_W) {
+		const uint32_t t = tc + n;
+		*tcp = t;
+		*rhop = pow((double)(T0 + t), -LAMDA);
+	} else {
+		if (tcp) *tcp = tc + n;
+	}
+}
+
+// update_v (fm_learn_vb_online.h:558-627) / update_w (:499-556) for the batch's entries of one
+// column per lane group: ov_stat per entry, ov_post, the leader's ov_commit, then VB's correction.
+template <int G, bool IS_W, int P, bool NEXT>
+DEVI void ov_level_body(LevelArgs a)
 {
 	__shared__ double lds[2 * (256 / 64)];
 	const uint32_t col_i = G <= 64 ? blockIdx.x * (256 / G) + threadIdx.x / G : blockIdx.x;
@@ -202,7 +217,7 @@ __global__ __launch_bounds__(256) void k_ov_v_level(LevelArgs a)
 	const uint32_t j = level_feat(a, col_i);
 	const uint64_t cb = a.col_ptr[col_i];
 	const uint32_t n = (uint32_t)(a.col_ptr[col_i + 1] - cb);
-	if (n == 0) return;   // columns without entries in the batch are skipped (:389-394)
+	if (n == 0) return;   // columns without entries in the batch are skipped (:389-394 / :364-368)
 	const uint2 *col = a.csc + cb;
 	// the lane's first two entries stay in registers from the statistics to the correction
 	// (named, not an array: an array of records gets demoted to LDS / scratch)
@@ -222,18 +237,15 @@ __global__ __launch_bounds__(256) void k_ov_v_level(LevelArgs a)
 	const double mo = msj.x, so = msj.y;
 	const double rho = a.rho[j];
 	const uint32_t cc = a.ccount[j];
-	const double sv_g = a.hyp[(size_t)a.attr_group[j] * a.hyp_stride];
+	const double hyp = a.hyp[(size_t)a.attr_group[j] * a.hyp_stride];
 	const double keep_m = (1 - rho) * natj.x, keep_s = (1 - rho) * natj.y;
 	const double acc = a.alpha * cc;          // alpha * col_count(col)
-	const double rca = rho * cc * a.alpha;    // new_vj(col) * col_count(col) * alpha
+	const double rca = rho * cc * a.alpha;    // new_j(col) * col_count(col) * alpha
 	double2 nx = make_double2(0.0, 0.0);
 	if constexpr (NEXT) nx = a.ms_next[(size_t)j * a.ms_stride_next];
 	double eta1 = 0.0, eta2 = 0.0;
 	auto stat = [&](uint2 e, Rec &r) {
-		double vm = 0.0, vs = 0.0;
-		v_stat(ent_x(e), E(r), Q<P>(r), TQ<P>(r), mo, so, vm, vs);
-		eta2 += keep_s + rho * (sv_g + acc * vs);
-		eta1 += keep_m + rca * vm;
+		ov_stat<IS_W, P>(r, ent_x(e), mo, so, hyp, rho, keep_m, keep_s, acc, rca, eta1, eta2);
 	};
 	if (h0) stat(ent0, v0);
 	if (h1) stat(ent1, v1);
@@ -244,138 +256,50 @@ __global__ __launch_bounds__(256) void k_ov_v_level(LevelArgs a)
 		stat(e, r);
 	}
 	group_sum2<G>(eta1, eta2, lds);
-	const double nmu = eta1 / n, nsig = eta2 / n;
-	double mu = nmu / nsig, sig = 1 / nsig;
-	bool go = true;
+	double nmu, nsig, mu, sig;
 	const bool leader = lane == 0;
-	if (dnan(sig) || dinf(sig)) {
-		sig = so;
-		if (leader) atomicAdd(&a.counters[CNT_NAN_SIGMA_V], 1u);
-	}
-	if (dnan(mu)) {
-		if (leader) atomicAdd(&a.counters[CNT_NAN_MU_V], 1u);
-		mu = mo;
-		go = false;
-	} else if (dinf(mu)) {
-		if (leader) atomicAdd(&a.counters[CNT_INF_MU_V], 1u);
-		mu = mo;
-		go = false;
-	}
+	const bool go = ov_post<IS_W>(eta1, eta2, n, mo, so, nmu, nsig, mu, sig, a.counters, leader);
 	if (leader) {
-		a.nat[(size_t)j * a.nat_stride] = make_double2(nmu, nsig);
-		a.ms[pi] = make_double2(mu, sig);
-		if (a.tcount) a.tcount[j] += n;   // t_vj(i) += size at factor 0 (:396-399)
+		uint32_t *tcp = a.tcount ? a.tcount + j : nullptr;
+		ov_commit<IS_W>(a.nat + (size_t)j * a.nat_stride, a.ms + pi, tcp, a.rho + j, tcp ? *tcp : 0u, n, nmu, nsig, mu, sig);
 	}
 	if (!go && !NEXT) return;
+	auto apply = [&](uint2 e, Rec &r) {
+		vb_apply<IS_W, P, NEXT>(r, ent_x(e), (e.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
+		store_rec(a.rows, e.x & ROW_MASK, r);
+	};
 	if (a.dup[j]) {
 		// a row listed twice: the reference corrects entry after entry
 		if constexpr (G > 64) __syncthreads();
 		if (leader)
 			for (uint32_t i = 0; i < n; ++i) {
-				const uint2 ent = col[i];
-				Rec v;
-				load_rec(a.rows, ent.x & ROW_MASK, v);
-				v_apply<P, NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
-				store_rec(a.rows, ent.x & ROW_MASK, v);
+				const uint2 e = col[i];
+				Rec r;
+				load_rec(a.rows, e.x & ROW_MASK, r);
+				apply(e, r);
 			}
 		return;
 	}
-	if (h0) {
-		v_apply<P, NEXT>(v0, ent_x(ent0), (ent0.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
-		store_rec(a.rows, ent0.x & ROW_MASK, v0);
-	}
-	if (h1) {
-		v_apply<P, NEXT>(v1, ent_x(ent1), (ent1.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
-		store_rec(a.rows, ent1.x & ROW_MASK, v1);
-	}
+	if (h0) apply(ent0, v0);
+	if (h1) apply(ent1, v1);
 	for (uint32_t i = lane + 2 * G; i < n; i += G) {
 		const uint2 e = col[i];
 		Rec r;
 		load_rec(a.rows, e.x & ROW_MASK, r);
-		v_apply<P, NEXT>(r, ent_x(e), (e.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
-		store_rec(a.rows, e.x & ROW_MASK, r);
+		apply(e, r);
 	}
 }
 
-// update_w (fm_learn_vb_online.h:499-556): as above with VB's w statistics; t_wj / new_wj are
-// advanced by the column itself (:519-520)
+template <int G, int P, bool NEXT>
+__global__ __launch_bounds__(256) void k_ov_v_level(LevelArgs a)
+{
+	ov_level_body<G, false, P, NEXT>(a);
+}
+
 template <int G, bool NEXT>
 __global__ __launch_bounds__(256) void k_ov_w_level(LevelArgs a)
 {
-	__shared__ double lds[2 * (256 / 64)];
-	const uint32_t col_i = G <= 64 ? blockIdx.x * (256 / G) + threadIdx.x / G : blockIdx.x;
-	const uint32_t lane = G <= 64 ? threadIdx.x % G : threadIdx.x;
-	if (col_i >= a.nfeat) return;
-	const uint64_t cb = a.col_ptr[col_i];
-	const uint32_t n = (uint32_t)(a.col_ptr[col_i + 1] - cb);
-	if (n == 0) return;   // (:364-368)
-	const uint32_t j = level_feat(a, col_i);
-	const uint2 *col = a.csc + cb;
-	const size_t pi = (size_t)j * a.ms_stride;
-	const double2 msj = a.ms[pi], natj = a.nat[(size_t)j * a.nat_stride];
-	const double mo = msj.x, so = msj.y;
-	const double rho = a.rho[j];
-	const uint32_t cc = a.ccount[j];
-	const double sw_g = a.hyp[(size_t)a.attr_group[j] * a.hyp_stride];
-	const double keep_m = (1 - rho) * natj.x, keep_s = (1 - rho) * natj.y;
-	const double acc = a.alpha * cc;
-	const double rca = rho * cc * a.alpha;
-	double2 nx = make_double2(0.0, 0.0);
-	if constexpr (NEXT) nx = a.ms_next[(size_t)j * a.ms_stride_next];
-	double eta1 = 0.0, eta2 = 0.0;
-	for (uint32_t i = lane; i < n; i += G) {
-		const uint2 ent = col[i];
-		const float x = ent_x(ent);
-		const double w_mean = x * (a.rows[ent.x & ROW_MASK].e + x * mo);
-		const double w_sigma_sqr = x * x;   // fp32 product
-		eta2 += keep_s + rho * (sw_g + acc * w_sigma_sqr);
-		eta1 += keep_m + rca * w_mean;
-	}
-	group_sum2<G>(eta1, eta2, lds);
-	const double nmu = eta1 / n, nsig = eta2 / n;
-	double mu = nmu / nsig, sig = 1 / nsig;
-	bool go = true;
-	const bool leader = lane == 0;
-	if (dnan(sig) || dinf(sig)) {
-		if (leader) atomicAdd(&a.counters[CNT_NAN_SIGMA_W], 1u);
-		sig = so;
-	}
-	if (dnan(mu)) {
-		if (leader) atomicAdd(&a.counters[CNT_NAN_MU_W], 1u);
-		mu = mo;
-		go = false;
-	} else if (dinf(mu)) {
-		if (leader) atomicAdd(&a.counters[CNT_INF_MU_W], 1u);
-		mu = mo;
-		go = false;
-	}
-	if (leader) {
-		a.nat[(size_t)j * a.nat_stride] = make_double2(nmu, nsig);
-		a.ms[pi] = make_double2(mu, sig);
-		const uint32_t t = a.tcount[j] + n;
-		a.tcount[j] = t;
-		a.rho[j] = pow((double)(T0 + t), -LAMDA);
-	}
-	if (!go && !NEXT) return;
-	if (a.dup[j]) {
-		if constexpr (G > 64) __syncthreads();
-		if (leader)
-			for (uint32_t i = 0; i < n; ++i) {
-				const uint2 ent = col[i];
-				Rec v;
-				load_rec(a.rows, ent.x & ROW_MASK, v);
-				w_apply<NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
-				store_rec(a.rows, ent.x & ROW_MASK, v);
-			}
-		return;
-	}
-	for (uint32_t i = lane; i < n; i += G) {
-		const uint2 ent = col[i];
-		Rec v;
-		load_rec(a.rows, ent.x & ROW_MASK, v);
-		w_apply<NEXT>(v, ent_x(ent), (ent.x & a.first_mask) != 0, go, mo, so, mu, sig, nx);
-		store_rec(a.rows, ent.x & ROW_MASK, v);
-	}
+	ov_level_body<G, true, 0, NEXT>(a);
 }
 
 // ---- the per-batch level-ordered store --------------------------------------------------------
@@ -687,22 +611,14 @@ __global__ __launch_bounds__(256) void k_ov_lord(const uint64_t *__restrict__ co
 		Rec r;
 		get(i, r);
 		const float x = xof(i, it);
-		if constexpr (IS_W) {
-			const double w_mean = x * (E(r) + x * mo);
-			const double w_sigma_sqr = x * x;   // fp32 product
-			eta2 += keep_s + rho * (hg + acc * w_sigma_sqr);
-			eta1 += keep_m + rca * w_mean;
-		} else {
-			double vm = 0.0, vs = 0.0;
-			v_stat(x, E(r), Q<P>(r), TQ<P>(r), mo, so, vm, vs);
-			eta2 += keep_s + rho * (hg + acc * vs);
-			eta1 += keep_m + rca * vm;
-		}
+		ov_stat<IS_W, P>(r, x, mo, so, hg, rho, keep_m, keep_s, acc, rca, eta1, eta2);
 	}
 	group_sum2<G>(eta1, eta2, nullptr);
 	double mu = mo, sig = so;
 	bool go = false;
 	if (n) {
+		// ov_post's and ov_commit's text, kept here: through the helpers this kernel's instruction
+		// stream changes (it pre-reads tc and writes through the tagged pointers)
 		const double nmu = eta1 / n, nsig = eta2 / n;
 		mu = nmu / nsig;
 		sig = 1 / nsig;
@@ -740,8 +656,7 @@ __global__ __launch_bounds__(256) void k_ov_lord(const uint64_t *__restrict__ co
 		Rec r;
 		get(i, r);
 		const float x = xof(i, it);
-		if constexpr (IS_W) w_apply<NEXT>(r, x, fof(i), go, mo, so, mu, sig, nx);
-		else v_apply<P, NEXT>(r, x, fof(i), go, mo, so, mu, sig, nx);
+		vb_apply<IS_W, P, NEXT>(r, x, fof(i), go, mo, so, mu, sig, nx);
 		const uint32_t o = o0 + i;
 		if (o < m) {
 #pragma unroll

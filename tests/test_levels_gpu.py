@@ -260,6 +260,27 @@ def test_few_factors_long_column(k, layout, monkeypatch):
     _few_close(res, _few_oracle(k, long_column=True), k, (k, layout, "segments"))
 
 
+@pytest.mark.parametrize("layout", ["column", "level"])
+@pytest.mark.parametrize("k", [0, 2])
+def test_few_factors_overflow_column(k, layout, monkeypatch):
+    """A column longer than the workgroup's BLOCK x R that is not segmented. The ~670-entry column
+    sits in a level whose mean column length is ~13, so the level runs the 64 x 2 shape: 128 of the
+    column's entries are held in registers, about 540 are re-gathered by the overflow loops of the
+    statistics pass and of the write-back. With VBFM_SEG_MIN, VBFM_SEG_LEN and VBFM_LONG unset the
+    default rule segments only columns beyond max(1024, 4 x the level's mean), so this one stays
+    whole. k = 0 is the w sweep alone; k = 2 gives w with a next factor, then v on both slots.
+    Column layout fused and two-pass, level store fused, against the CPU oracle (1e-12: tree
+    against sequential column sums)."""
+    monkeypatch.delenv("VBFM_LONG", raising=False)
+    forms = [("fused", {"VBFM_FORCE_SPLIT": "0"})]
+    if layout == "column":
+        forms.append(("two-pass", {"VBFM_FORCE_SPLIT": "1", "VBFM_DEFER": "0"}))
+    ref = _few_oracle(k, long_column=True)
+    for form, env in forms:
+        res = _few_run(k, layout, env, monkeypatch, long_column=True)
+        _few_close(res, ref, k, (k, layout, form, "overflow"))
+
+
 def test_per_level_steps_refuse_misuse(monkeypatch):
     g = _learner("tiny", "auto")
     g.init_caches()
