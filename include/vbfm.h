@@ -481,6 +481,98 @@ void vbfm_free_host_data(vbfm_host_data *d);
 int vbfm_init_params_host(uint32_t seed, double init_stdev, int32_t num_factor, uint32_t num_attribute,
                           uint32_t num_attr_groups, vbfm_params *out, double *fm_v, double *fm_w);
 
+/* ---- model files and scoring (additive to ABI 4: new functions and structs only) --------
+ * No reference counterpart: the reference predicts only the test set attached while training
+ * (libfm.cpp:514-519) and keeps no model on disk. A model file holds the parameters a prediction
+ * reads and nothing else -- no row caches, no hyper-parameters, no attribute groups, no data
+ * fingerprint -- so it loads without the train set (a checkpoint, vbfm_save_state, does not).
+ * Little-endian: an 88-byte header (magic "VBFMMD01", format version, kind, k0, k1, num_factor,
+ * num_attribute, min_target, max_target, the caller's iteration count, the scalars, the payload's
+ * byte count and a 64-bit checksum of the payload), then the payload as the library stores it:
+ * VB kinds {mu, sigma} pairs of w [D] and of v [j*k + f]; ALS / MCMC w [D] and v [j*k + f].
+ * Written to <path>.tmp, fsync'ed and renamed. A reader checks magic, version, kind, that
+ * D * k * entry size does not overflow, that the header's sizes equal the file's size exactly and
+ * the checksum, all before any allocation that grows with the file. */
+#define VBFM_MODEL_VB 0
+#define VBFM_MODEL_VB_ONLINE 1
+#define VBFM_MODEL_ALS 2
+#define VBFM_MODEL_MCMC_DRAW 3   /* the LAST draw of the chain (fm.w0 / fm.w / fm.v after the last
+                                    iteration), not the chain average the MCMC learner's -out reports */
+typedef struct {
+	int32_t kind, k0, k1, num_factor;
+	uint32_t num_attribute;
+	float min_target, max_target;
+	uint32_t iter;
+	int32_t has_variance;     /* 1 for the VB kinds (the file holds sigma: T_n can be scored) */
+	double w0_or_mu0;         /* VB kinds: mu_0_dash; ALS / MCMC: w0 */
+	double sigma_0_dash;      /* VB kinds; 0 otherwise */
+	double alpha;
+} vbfm_model_info;
+/* Host-only (no GPU needed; failures in vbfm_last_error(NULL)). vbfm_model_file_info validates the
+ * whole file. The writer takes vb (VB kinds: mu_w, sigma_w, mu_v, sigma_v) or mc (ALS / MCMC: w, v);
+ * the reader fills caller-allocated arrays of whichever struct matches the file's kind, NULL
+ * pointers and NULL arrays skipped. vbfm_params / vbfm_mcmc_params hold v as [f][j], the file as
+ * [j][f]: both convert. has_variance, and the scalars of the kind's struct, come from info. */
+int vbfm_model_file_info(const char *path, vbfm_model_info *out);
+int vbfm_model_write_host(const char *path, const vbfm_model_info *info, const vbfm_params *vb,
+                          const vbfm_mcmc_params *mc);
+int vbfm_model_read_host(const char *path, vbfm_model_info *info, vbfm_params *vb, vbfm_mcmc_params *mc);
+
+/* A model on a device: the tables the scoring kernels read. Failures of a call that has a model
+ * are in vbfm_model_last_error(m), those without in vbfm_last_error(NULL). */
+typedef struct vbfm_model vbfm_model;
+/* the context's parameters as they are now (VB, online VB, MCMC / ALS context); with several ranks
+ * only rank 0 writes (the parameters are replicated), the others return 0 */
+int vbfm_model_save(vbfm_ctx *ctx, const char *path, uint32_t iter);
+int vbfm_model_from_ctx(vbfm_model **out, vbfm_ctx *ctx);   /* device-to-device snapshot on ctx's device */
+int vbfm_model_load(vbfm_model **out, const char *path, int32_t device);
+int vbfm_model_info_get(const vbfm_model *m, vbfm_model_info *out);
+const char *vbfm_model_last_error(const vbfm_model *m);
+void vbfm_model_destroy(vbfm_model *m);
+
+/* rows to score, CSR in host memory: row r's entries are row_ent[row_ptr[r] .. row_ptr[r + 1]),
+ * in any order: a row's terms are summed in ascending id (entries of one id in the order given),
+ * the order of the reference's transposed copy (Data.h:457-509) and of a context's predictions */
+typedef struct {
+	uint32_t num_rows;
+	uint64_t nnz;
+	const uint64_t *row_ptr;    /* [num_rows + 1] */
+	const vbfm_entry *row_ent;  /* [nnz] */
+} vbfm_csr;
+#define VBFM_ORDER_AUTO 0    /* the context's rule: exact while nnz * k <= 5e7, else group */
+#define VBFM_ORDER_EXACT 1   /* the reference's summation order (factor-major, entries ascending) */
+#define VBFM_ORDER_GROUP 2   /* the lane-group kernel: per-factor sums in entry order, the factors
+                                summed by a fixed butterfly (bit-identical to the wave kernels) */
+typedef struct {
+	int32_t order;         /* VBFM_ORDER_* */
+	int32_t clip;          /* 1: mean clipped to [min_target, max_target] as pred_this is */
+	int32_t unknown_ids;   /* ids >= num_attribute: 0 refuse (the message names the first such row and its
+	                          smallest unknown id), 1 skip the entry */
+	uint64_t chunk_bytes;  /* device memory per staged chunk of host rows, 0 = default (VBFM_SCORE_CHUNK_DEFAULT) */
+} vbfm_score_opts;
+#define VBFM_SCORE_CHUNK_DEFAULT ((uint64_t)64 << 20)
+typedef struct {
+	uint32_t n_chunks;
+	uint64_t skipped_entries;
+	double ms_copy, ms_kernel;   /* device time of the chunks' copies to the device / of their kernels, summed */
+	double ms_total;             /* host wall time of the call */
+} vbfm_score_stats;
+/* mean[r] = predict_data_and_write_to_eterms (fm_learn_vb.h:70-203) of row r on the model's
+ * parameters -- for ALS / MCMC kinds on the point values (MCMC_DRAW: the last draw's prediction,
+ * not the chain average). var (NULL, or [rows]) = the reference's T_n
+ * (predict_t_and_write_to_qterms, fm_learn_vb.h:207-312), refused for ALS / MCMC kinds; the
+ * predictive variance of y is T_n + 1 / alpha (alpha is in the info; the addition is the
+ * caller's). o == NULL: all defaults (auto order, clipped, refuse). vbfm_score never needs the
+ * rows in device memory at once: it cuts them into chunks of whole rows of at most chunk_bytes (a
+ * larger row is a chunk by itself), staged through two pinned host and two device buffers, chunk
+ * i + 1's copy under chunk i's kernel; results are bit-identical whatever the chunk size. */
+int vbfm_score(vbfm_model *m, const vbfm_csr *rows, const vbfm_score_opts *o, double *mean, double *var,
+               vbfm_score_stats *st);
+/* the same for the train (which = 0) or test (1) set a context holds in device memory (synthetic
+ * sets included); the context must be on the model's device */
+int vbfm_score_device(vbfm_model *m, vbfm_ctx *ctx, int32_t which, const vbfm_score_opts *o, double *mean,
+                      double *var, vbfm_score_stats *st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,15 @@
 
 extern "C" const char *vbfm_host_last_error(void);
 extern "C" void vbfm_host_set_error(const char *msg);
+// model files with the payload as the library stores it (vbfm_host.cpp): the w table, then the v
+// table [j*k + f]; {mu, sigma} pairs for the VB kinds, plain values for ALS / MCMC
+extern "C" int vbfm_host_model_write_raw(const char *path, const vbfm_model_info *info, const double *w_tab,
+                                         const double *v_tab);
+// alloc provides the tables once the file has proved sound (magic, sizes, checksum)
+extern "C" int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info,
+                                        int (*alloc)(void *user, const vbfm_model_info *info, double **w_tab,
+                                                     double **v_tab),
+                                        void *user);
 
 struct McState;   // vbfm_mcmc_capi.hip
 struct OvState;   // vbfm_online.hip
@@ -456,6 +465,8 @@ void mc_free(vbfm_ctx *c);
 uint64_t mc_state_payload(vbfm_ctx *c);
 void mc_state_write(vbfm_ctx *c, CkptFile &f);
 void mc_state_read(vbfm_ctx *c, CkptFile &f);
+// what a model snapshot takes beside the tables (vbfm_score.hip): fm.w0, alpha, sampling or ALS
+void mc_model_scalars(vbfm_ctx *c, double *w0, double *alpha, bool *sample);
 
 // ---- vbfm_online.hip: the online VB learner ---------------------------------------------------
 void ov_free(vbfm_ctx *c);

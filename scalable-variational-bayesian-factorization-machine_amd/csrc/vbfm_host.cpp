@@ -5,6 +5,9 @@
 //   * vbfm_init_params_host the reference's initial draws (glibc rand() after srand(seed),
 //                           Leva normals: src/util/random.h:150-176) in its exact order, on
 //                           a private copy of that generator (vbfm_rng.h).
+//   * vbfm_model_*_host /   model files (no reference counterpart): the parameters a prediction reads
+//     vbfm_model_file_info  behind a checked header; the device side (vbfm_score.hip) reads and writes
+//                           them through vbfm_host_model_{read,write}_raw.
 // Plain C++; built with -ffp-contract=off like the reference's x86-64 build (no FMA).
 #include "../../include/vbfm.h"
 #include "vbfm_rng.h"
@@ -17,6 +20,9 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include <sys/stat.h>
+#include <unistd.h>
 
 namespace {
 
@@ -357,9 +363,284 @@ int write_sparse(const std::string &fn, uint32_t nrows, uint32_t ncols, uint64_t
 	return 0;
 }
 
+// ---- model files (include/vbfm.h "model files and scoring") --------------------------------------
+struct ModelHeader {
+	char magic[8];            // "VBFMMD01"
+	uint32_t version;         // 1
+	int32_t kind, k0, k1, k;
+	uint32_t D;
+	float min_target, max_target;
+	uint32_t iter, reserved;
+	double s0, s1, alpha;     // VB kinds: mu_0_dash, sigma_0_dash; ALS / MCMC: w0, 0
+	uint64_t payload;         // bytes behind the header
+	uint64_t checksum;        // of the payload (Sum64)
+};
+static_assert(sizeof(ModelHeader) == 88, "model file header layout");
+constexpr char MODEL_MAGIC[8] = {'V', 'B', 'F', 'M', 'M', 'D', '0', '1'};
+constexpr uint32_t MODEL_VERSION = 1;
+constexpr size_t MODEL_BUF = 1 << 15;   // doubles per I/O piece (256 KiB): the only buffer of both passes
+
+// 64-bit checksum over the payload's 8-byte words in file order (the payload is doubles only)
+struct Sum64 {
+	uint64_t h = 0x9E3779B97F4A7C15ull;
+	void add(const double *p, size_t n)
+	{
+		for (size_t i = 0; i < n; i++) {
+			uint64_t w;
+			memcpy(&w, p + i, 8);
+			h = (((h << 5) | (h >> 59)) ^ w) * 0x100000001B3ull;
+		}
+	}
+};
+
+bool model_vb(int32_t kind) { return kind == VBFM_MODEL_VB || kind == VBFM_MODEL_VB_ONLINE; }
+
+// doubles of the w table and of the v table; false when D * (k + 1) * entry size overflows
+bool model_sizes(int32_t kind, int32_t k, uint32_t D, uint64_t *nw, uint64_t *nv, uint64_t *bytes)
+{
+	const uint64_t per = model_vb(kind) ? 2 : 1;
+	*nw = (uint64_t)D * per;
+	uint64_t kd;
+	if (__builtin_mul_overflow((uint64_t)D, (uint64_t)k, &kd) || __builtin_mul_overflow(kd, per, nv)) return false;
+	uint64_t n;
+	if (__builtin_add_overflow(*nw, *nv, &n) || __builtin_mul_overflow(n, (uint64_t)8, bytes)) return false;
+	return true;
+}
+
+ModelHeader model_header(const vbfm_model_info &in)
+{
+	ModelHeader h;
+	memset(&h, 0, sizeof(h));
+	memcpy(h.magic, MODEL_MAGIC, 8);
+	h.version = MODEL_VERSION;
+	h.kind = in.kind; h.k0 = in.k0 != 0; h.k1 = in.k1 != 0; h.k = in.num_factor;
+	h.D = in.num_attribute;
+	h.min_target = in.min_target; h.max_target = in.max_target;
+	h.iter = in.iter;
+	h.s0 = in.w0_or_mu0; h.s1 = model_vb(in.kind) ? in.sigma_0_dash : 0.0; h.alpha = in.alpha;
+	return h;
+}
+
+vbfm_model_info model_info(const ModelHeader &h)
+{
+	vbfm_model_info o;
+	memset(&o, 0, sizeof(o));
+	o.kind = h.kind; o.k0 = h.k0; o.k1 = h.k1; o.num_factor = h.k;
+	o.num_attribute = h.D;
+	o.min_target = h.min_target; o.max_target = h.max_target;
+	o.iter = h.iter;
+	o.has_variance = model_vb(h.kind) ? 1 : 0;
+	o.w0_or_mu0 = h.s0; o.sigma_0_dash = h.s1; o.alpha = h.alpha;
+	return o;
+}
+
+struct FileCloser {
+	FILE *f;
+	~FileCloser() { if (f) fclose(f); }
+};
+
+// header + payload to <path>.tmp, fsync, rename (as checkpoints are written); get(i) is the i-th
+// double of the payload
+template <class Get> int model_write(const char *path, const vbfm_model_info *info, Get get)
+{
+	if (!path || !info) { g_host_err = "model file: null argument"; return -1; }
+	if (info->kind < VBFM_MODEL_VB || info->kind > VBFM_MODEL_MCMC_DRAW) { g_host_err = "model file: unknown kind"; return -1; }
+	if (info->num_factor < 0) { g_host_err = "model file: negative number of factors"; return -1; }
+	ModelHeader h = model_header(*info);
+	uint64_t nw, nv;
+	if (!model_sizes(h.kind, h.k, h.D, &nw, &nv, &h.payload)) {
+		g_host_err = "model file: num_attribute * (num_factor + 1) * entry size overflows 64 bits";
+		return -1;
+	}
+	const std::string tmp = std::string(path) + ".tmp";
+	FileCloser fc{fopen(tmp.c_str(), "wb")};
+	if (!fc.f) { g_host_err = "cannot open model file " + tmp; return -1; }
+	bool ok = fwrite(&h, sizeof(h), 1, fc.f) == 1;
+	std::vector<double> buf(MODEL_BUF);
+	Sum64 sum;
+	const uint64_t n = nw + nv;
+	for (uint64_t o = 0; ok && o < n; o += MODEL_BUF) {
+		const size_t m = (size_t)std::min<uint64_t>(MODEL_BUF, n - o);
+		for (size_t i = 0; i < m; i++) buf[i] = get(o + i);
+		sum.add(buf.data(), m);
+		ok = fwrite(buf.data(), 8, m, fc.f) == m;
+	}
+	h.checksum = sum.h;
+	ok = ok && fseek(fc.f, 0, SEEK_SET) == 0 && fwrite(&h, sizeof(h), 1, fc.f) == 1;
+	ok = ok && fflush(fc.f) == 0 && fsync(fileno(fc.f)) == 0;
+	const bool closed = fclose(fc.f) == 0;
+	fc.f = nullptr;
+	if (!ok || !closed) { unlink(tmp.c_str()); g_host_err = "short write to " + tmp; return -1; }
+	if (rename(tmp.c_str(), path) != 0) { unlink(tmp.c_str()); g_host_err = "cannot rename " + tmp + " to " + path; return -1; }
+	return 0;
+}
+
+// Validate the whole file -- magic, version, kind, sizes without overflow, header sizes == file size,
+// checksum -- reading through one MODEL_BUF piece; then, with put, a second pass hands every double
+// of the payload to put(i, value). Nothing that grows with the file is allocated here.
+template <class Put> int model_read(const char *path, ModelHeader *hout, Put put, bool want)
+{
+	if (!path) { g_host_err = "model file: null path"; return -1; }
+	const std::string p(path);
+	FileCloser fc{fopen(path, "rb")};
+	if (!fc.f) { g_host_err = "cannot open model file " + p; return -1; }
+	struct stat sb;
+	if (fstat(fileno(fc.f), &sb) != 0) { g_host_err = "cannot stat model file " + p; return -1; }
+	const uint64_t fsize = (uint64_t)sb.st_size;
+	ModelHeader h;
+	if (fsize < sizeof(h) || fread(&h, sizeof(h), 1, fc.f) != 1) {
+		g_host_err = "model file truncated inside its header (" + std::to_string(fsize) + " of " +
+		             std::to_string(sizeof(h)) + " bytes): " + p;
+		return -1;
+	}
+	if (memcmp(h.magic, MODEL_MAGIC, 8) != 0) { g_host_err = "not a libvbfm model file (bad magic): " + p; return -1; }
+	if (h.version != MODEL_VERSION) {
+		g_host_err = "model file of format version " + std::to_string(h.version) + ", this library reads version " +
+		             std::to_string(MODEL_VERSION) + ": " + p;
+		return -1;
+	}
+	if (h.kind < VBFM_MODEL_VB || h.kind > VBFM_MODEL_MCMC_DRAW) {
+		g_host_err = "model file of unknown kind " + std::to_string(h.kind) + ": " + p;
+		return -1;
+	}
+	if (h.k < 0) { g_host_err = "model file with a negative number of factors: " + p; return -1; }
+	uint64_t nw, nv, bytes;
+	if (!model_sizes(h.kind, h.k, h.D, &nw, &nv, &bytes)) {
+		g_host_err = "model file header: num_attribute * (num_factor + 1) * entry size overflows 64 bits: " + p;
+		return -1;
+	}
+	if (h.payload != bytes) {
+		g_host_err = "model file header: payload byte count " + std::to_string(h.payload) + " does not match its sizes (" +
+		             std::to_string(bytes) + "): " + p;
+		return -1;
+	}
+	if (fsize - sizeof(h) < bytes) {
+		g_host_err = "model file truncated inside its payload (" + std::to_string(fsize - sizeof(h)) + " of " +
+		             std::to_string(bytes) + " bytes): " + p;
+		return -1;
+	}
+	if (fsize - sizeof(h) > bytes) {
+		g_host_err = "model file has " + std::to_string(fsize - sizeof(h) - bytes) + " trailing bytes: " + p;
+		return -1;
+	}
+	if (hout) *hout = h;   // (put may read it: the header is sound from here on)
+	std::vector<double> buf(MODEL_BUF);
+	const uint64_t n = nw + nv;
+	for (int pass = 0; pass < (want ? 2 : 1); pass++) {
+		if (fseek(fc.f, (long)sizeof(h), SEEK_SET) != 0) { g_host_err = "cannot seek in model file " + p; return -1; }
+		Sum64 sum;
+		for (uint64_t o = 0; o < n; o += MODEL_BUF) {
+			const size_t m = (size_t)std::min<uint64_t>(MODEL_BUF, n - o);
+			if (fread(buf.data(), 8, m, fc.f) != m) { g_host_err = "cannot read model file " + p; return -1; }
+			if (pass == 0) sum.add(buf.data(), m);
+			else for (size_t i = 0; i < m; i++) put(o + i, buf[i]);
+		}
+		if (pass == 0 && sum.h != h.checksum) {
+			g_host_err = "model file checksum mismatch (corrupt payload): " + p;
+			return -1;
+		}
+	}
+	return 0;
+}
+
+// where double i of a payload lies in the caller's arrays: vbfm_params / vbfm_mcmc_params keep v as
+// [f][j], the file as [j][f] (pairs for the VB kinds)
+struct ModelSlot { int arr; uint64_t idx; };   // arr: 0 mu_w | w, 1 sigma_w, 2 mu_v | v, 3 sigma_v
+ModelSlot model_slot(bool vb, uint64_t D, uint64_t k, uint64_t i)
+{
+	const uint64_t per = vb ? 2 : 1, nw = D * per;
+	if (i < nw) return ModelSlot{(int)(i % per), i / per};
+	const uint64_t q = (i - nw) / per, j = q / k, f = q % k;
+	return ModelSlot{2 + (int)((i - nw) % per), f * D + j};
+}
+
 }  // namespace
 
 extern "C" {
+
+int vbfm_model_file_info(const char *path, vbfm_model_info *out)
+{
+	ModelHeader h;
+	if (model_read(path, &h, [](uint64_t, double) {}, false)) return -1;
+	if (out) *out = model_info(h);
+	return 0;
+}
+
+int vbfm_model_write_host(const char *path, const vbfm_model_info *info, const vbfm_params *vb,
+                          const vbfm_mcmc_params *mc)
+{
+	if (!path || !info) { g_host_err = "vbfm_model_write_host: null argument"; return -1; }
+	const bool isvb = model_vb(info->kind);
+	const uint64_t D = info->num_attribute, k = (uint64_t)std::max(info->num_factor, 0);
+	const double *a[4] = {nullptr, nullptr, nullptr, nullptr};
+	if (isvb && vb) { a[0] = vb->mu_w; a[1] = vb->sigma_w; a[2] = vb->mu_v; a[3] = vb->sigma_v; }
+	if (!isvb && mc) { a[0] = mc->w; a[2] = mc->v; }
+	if ((D && !a[0]) || (D && isvb && !a[1]) || (D && k && !a[2]) || (D && k && isvb && !a[3])) {
+		g_host_err = isvb ? "vbfm_model_write_host: a VB kind needs mu_w, sigma_w, mu_v, sigma_v (vbfm_params)"
+		                  : "vbfm_model_write_host: an ALS / MCMC kind needs w and v (vbfm_mcmc_params)";
+		return -1;
+	}
+	return model_write(path, info, [&](uint64_t i) {
+		const ModelSlot s = model_slot(isvb, D, k, i);
+		return a[s.arr][s.idx];
+	});
+}
+
+int vbfm_model_read_host(const char *path, vbfm_model_info *info, vbfm_params *vb, vbfm_mcmc_params *mc)
+{
+	ModelHeader h;
+	double *avb[4] = {nullptr, nullptr, nullptr, nullptr}, *amc[4] = {nullptr, nullptr, nullptr, nullptr};
+	if (vb) { avb[0] = vb->mu_w; avb[1] = vb->sigma_w; avb[2] = vb->mu_v; avb[3] = vb->sigma_v; }
+	if (mc) { amc[0] = mc->w; amc[2] = mc->v; }
+	// one call: the first pass proves the whole file sound before the second stores a value
+	if (model_read(path, &h, [&](uint64_t i, double v) {
+		    const bool isvb = model_vb(h.kind);
+		    const ModelSlot s = model_slot(isvb, h.D, (uint64_t)h.k, i);
+		    double *a = (isvb ? avb : amc)[s.arr];
+		    if (a) a[s.idx] = v;
+	    }, vb || mc))
+		return -1;
+	if (model_vb(h.kind) && vb) { vb->mu_0_dash = h.s0; vb->sigma_0_dash = h.s1; vb->alpha = h.alpha; }
+	if (!model_vb(h.kind) && mc) { mc->w0 = h.s0; mc->alpha = h.alpha; }
+	if (info) *info = model_info(h);
+	return 0;
+}
+
+// the payload as the library stores it (internal: vbfm_score.hip): w_tab then v_tab, pairs for the
+// VB kinds
+int vbfm_host_model_write_raw(const char *path, const vbfm_model_info *info, const double *w_tab, const double *v_tab)
+{
+	if (!info) { g_host_err = "model file: null argument"; return -1; }
+	const uint64_t nw = (uint64_t)info->num_attribute * (model_vb(info->kind) ? 2 : 1);
+	return model_write(path, info, [&](uint64_t i) { return i < nw ? w_tab[i] : v_tab[i - nw]; });
+}
+
+// ... and read back: alloc(user, info, &w_tab, &v_tab) is called once the whole file has proved
+// sound (never for a refused file), then the tables are filled
+int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info,
+                             int (*alloc)(void *user, const vbfm_model_info *info, double **w_tab, double **v_tab),
+                             void *user)
+{
+	ModelHeader h;
+	double *w_tab = nullptr, *v_tab = nullptr;
+	bool ready = false, failed = false;
+	auto prepare = [&] {
+		const vbfm_model_info in = model_info(h);
+		failed = alloc(user, &in, &w_tab, &v_tab) != 0;
+		ready = true;
+	};
+	if (model_read(path, &h, [&](uint64_t i, double v) {
+		    if (!ready) prepare();
+		    if (failed) return;
+		    const uint64_t nw = (uint64_t)h.D * (model_vb(h.kind) ? 2 : 1);
+		    if (i < nw) w_tab[i] = v; else v_tab[i - nw] = v;
+	    }, true))
+		return -1;
+	if (!ready) prepare();   // an empty payload
+	if (failed) { g_host_err = "model file: out of memory for the tables: " + std::string(path); return -1; }
+	if (info) *info = model_info(h);
+	return 0;
+}
 
 int vbfm_save_data(const char *basename, const vbfm_host_data *d)
 {

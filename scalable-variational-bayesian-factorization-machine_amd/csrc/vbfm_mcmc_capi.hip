@@ -67,6 +67,13 @@ void mc_free(vbfm_ctx *c)
 	c->mc = nullptr;
 }
 
+void mc_model_scalars(vbfm_ctx *c, double *w0, double *alpha, bool *sample)
+{
+	*w0 = c->mc->w0;
+	*alpha = c->mc->alpha;
+	*sample = c->mc->sample != 0;
+}
+
 }  // namespace vbi
 
 namespace {

@@ -12,7 +12,10 @@
 //     other learners; -relation is not supported;
 //   * extra flags: -device (HIP ordinal), -vfile 0 (skip writing v_file.txt), -save_state /
 //     -resume (checkpoints), -parity_log (17-digit JSON lines per iteration), and the multi-GPU launch: -devices N | o0,o1,..., -shard
-//     rows|features, -transport rccl|host, -plan 1 (print the ranks' shard plan, no GPU).
+//     rows|features, -transport rccl|host, -plan 1 (print the ranks' shard plan, no GPU);
+//   * -save_model FILE (every method: the parameters alone, after the last iteration) and the
+//     predict-only mode -load_model FILE -test T -out P [-out_var V] (no -train; no reference
+//     counterpart: the reference predicts only the test set attached while training).
 //
 // Multi-GPU (-devices): the reference is one process on one core. Here this process parses the
 // flags and loads the data (host code only, no HIP call), then forks one rank process per GPU
@@ -43,6 +46,16 @@
 #include <sys/wait.h>
 #include <unistd.h>
 #include <vector>
+
+// The model and scoring entry points live in libvbfm's device code. They are referenced weakly: a
+// build of this launcher without them (its host logic under the sanitizers, linked with stand-ins
+// for the GPU entry points) links, and -save_model / -load_model fail there with a message.
+#pragma weak vbfm_model_save
+#pragma weak vbfm_model_load
+#pragma weak vbfm_model_info_get
+#pragma weak vbfm_model_last_error
+#pragma weak vbfm_model_destroy
+#pragma weak vbfm_score
 
 namespace {
 
@@ -250,6 +263,20 @@ void load(const std::string &fn, Data &d, const char *what)
 	          << "\tmin_target=" << d.h.min_target << "\tmax_target=" << d.h.max_target << std::endl;
 }
 
+static bool have_scorer()
+{
+	return vbfm_model_save && vbfm_model_load && vbfm_model_info_get && vbfm_model_last_error && vbfm_model_destroy &&
+	       vbfm_score;
+}
+
+// -save_model: the parameters alone, after the last iteration (every rank calls; rank 0 writes)
+static void save_model(vbfm_ctx *ctx, const std::string &file, uint32_t iter)
+{
+	if (file.empty()) return;
+	if (!have_scorer()) throw std::string("this build has no scorer");
+	check(vbfm_model_save(ctx, file.c_str(), iter), ctx);
+}
+
 // ---- ranks ------------------------------------------------------------------------------
 // The shared-memory page the forked ranks use: a process-shared barrier, rank 0's RCCL
 // unique id, one slot per rank for the host all-reduce, and the gathered test predictions
@@ -404,7 +431,7 @@ struct McmcRun {
 	uint32_t G, D;
 	int k0, k1, k;
 	bool vfile;
-	std::string rlog_file, out_file, parity_file, save_file, resume_file;
+	std::string rlog_file, out_file, parity_file, save_file, resume_file, model_file;
 };
 
 static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
@@ -530,6 +557,7 @@ static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
 		}
 		if (!r.save_file.empty())
 			check(vbfm_save_state(ctx, rk.rank_file(r.save_file).c_str(), it0 + r.num_iter), ctx);
+		save_model(ctx, r.model_file, it0 + r.num_iter);
 		std::cout << "after learn" << std::endl;   // libfm.cpp:507; no Final line for mcmc (:509)
 		if (!r.out_file.empty()) {                 // libfm.cpp:514-519
 			uint32_t lo, hi;
@@ -585,7 +613,7 @@ struct OnlineRun {
 	uint32_t G, D;
 	int k0, k1, k;
 	bool vfile;
-	std::string rlog_file, out_file, parity_file, save_file, resume_file;
+	std::string rlog_file, out_file, parity_file, save_file, resume_file, model_file;
 };
 
 static void run_online(const OnlineRun &r, Data &train, Data &test, const Rank &rk)
@@ -687,6 +715,7 @@ static void run_online(const OnlineRun &r, Data &train, Data &test, const Rank &
 			}
 		}
 		if (!r.save_file.empty()) check(vbfm_save_state(ctx, r.save_file.c_str(), it0 + r.num_iter), ctx);
+		save_model(ctx, r.model_file, it0 + r.num_iter);
 		std::cout << "after learn" << std::endl;                              // libfm.cpp:507
 		std::cout << "Final\tTrain=" << NAN << "\tTest=" << NAN << std::endl;   // evaluate() is NaN (:17)
 		if (!r.out_file.empty()) {
@@ -713,7 +742,7 @@ struct VbRun {
 	uint32_t G, D;
 	int k0, k1, k;
 	bool vfile;
-	std::string rlog_file, out_file, save_file, resume_file, parity_file;
+	std::string rlog_file, out_file, save_file, resume_file, parity_file, model_file;
 };
 
 static void run_vb(const VbRun &r, Data &train, Data &test, const Rank &rk)
@@ -840,6 +869,7 @@ static void run_vb(const VbRun &r, Data &train, Data &test, const Rank &rk)
 		}
 		if (!r.save_file.empty())
 			check(vbfm_save_state(ctx, rk.rank_file(r.save_file).c_str(), it0 + r.num_iter), ctx);
+		save_model(ctx, r.model_file, it0 + r.num_iter);
 		// libfm.cpp:509-511: fm_learn_vb::evaluate returns NaN
 		std::cout << "Final\tTrain=" << NAN << "\tTest=" << NAN << std::endl;
 		if (!r.out_file.empty()) {   // libfm.cpp:514-519, DVector::save (matrix.h:284-295)
@@ -858,6 +888,61 @@ static void run_vb(const VbRun &r, Data &train, Data &test, const Rank &rk)
 		vbfm_destroy(ctx);
 	} catch (...) {
 		if (ctx) vbfm_destroy(ctx);
+		throw;
+	}
+}
+
+// -load_model FILE -test T -out P [-out_var V]: score T's rows with a saved model, no training. P
+// has the format and clipping of a training run's -out, V one T_n per line at 17 digits (VB kinds).
+struct ScoreRun {
+	std::string model_file, test_file, out_file, var_file;
+	int32_t device;
+	bool skip_unknown;
+};
+
+static void run_score(const ScoreRun &r)
+{
+	if (!have_scorer()) throw std::string("this build has no scorer");
+	Data test;
+	load(r.test_file, test, "test");
+	vbfm_model *m = nullptr;
+	if (vbfm_model_load(&m, r.model_file.c_str(), r.device) != 0) throw std::string(vbfm_last_error(nullptr));
+	try {
+		vbfm_model_info info;
+		if (vbfm_model_info_get(m, &info) != 0) throw std::string(vbfm_last_error(nullptr));
+		static const char *const kinds[4] = {"vb", "vb_online", "als", "mcmc (last draw)"};
+		std::cout << "model " << r.model_file << ": " << kinds[info.kind] << ", dim " << info.k0 << "," << info.k1 << ","
+		          << info.num_factor << ", num_attribute=" << info.num_attribute << ", after " << info.iter
+		          << " iterations" << std::endl;
+		const uint32_t n = test.h.num_rows;
+		std::vector<double> mean(n), var(r.var_file.empty() ? 0 : n);
+		const vbfm_csr rows{n, test.h.nnz, test.h.row_ptr, test.h.row_ent};
+		const vbfm_score_opts o{VBFM_ORDER_AUTO, 1, r.skip_unknown ? 1 : 0, 0};
+		vbfm_score_stats st;
+		if (vbfm_score(m, &rows, &o, mean.data(), r.var_file.empty() ? nullptr : var.data(), &st) != 0)
+			throw std::string(vbfm_model_last_error(m));
+		if (st.skipped_entries) std::cout << "skipped " << st.skipped_entries << " entries with ids the model does not have" << std::endl;
+		double s2 = 0.0, s1 = 0.0;   // the mean is clipped to the model's target range already
+		for (uint32_t i = 0; i < n; i++) {
+			const double err = mean[i] - test.h.target[i];
+			s2 += err * err;
+			s1 += std::fabs(err);
+		}
+		if (n) std::cout << "Test RMSE=" << std::sqrt(s2 / n) << "\tMAE=" << s1 / n << std::endl;
+		{
+			std::ofstream out(r.out_file.c_str());
+			if (!out.is_open()) throw std::string("Unable to open file " + r.out_file);
+			for (double x : mean) out << x << std::endl;
+		}
+		if (!r.var_file.empty()) {
+			FILE *f = fopen(r.var_file.c_str(), "w");
+			if (!f) throw std::string("Unable to open file " + r.var_file);
+			for (double x : var) fprintf(f, "%.17g\n", x);
+			fclose(f);
+		}
+		vbfm_model_destroy(m);
+	} catch (...) {
+		vbfm_model_destroy(m);
 		throw;
 	}
 }
@@ -1042,8 +1127,25 @@ int main(int argc, char **argv)
 		const std::string p_save = cmd.reg("save_state", "vb, vb_online, mcmc, als: write the learner's state to this file after the last iteration (.<rank> per rank with -devices)");
 		const std::string p_plog = cmd.reg("parity_log", "JSON lines: a 'setup' line (set-up costs), then one per iteration: the printed values at 17 digits, phase times, sweep nnz*k/s, HBM roofline fraction and the exchange's calls / bytes / ms; default=''");
 		const std::string p_resume = cmd.reg("resume", "vb, vb_online, mcmc, als: continue from a -save_state file (same data and -dim) instead of the initial draws");
+		const std::string p_savem = cmd.reg("save_model", "every method: write the model's parameters to this file after the last iteration (rank 0 with -devices); -load_model scores with it");
+		const std::string p_loadm = cmd.reg("load_model", "predict only: score -test with this -save_model file and write -out (no -train; not with -method, -dim, -iter)");
+		const std::string p_outvar = cmd.reg("out_var", "with -load_model: one variance term T_n per line at 17 digits (vb and vb_online models; var(y) = T_n + 1/alpha)");
+		const std::string p_unknown = cmd.reg("unknown_ids", "with -load_model: refuse (default) or skip entries whose feature id the model does not have");
 		if (cmd.has(p_help) || argc == 1) { cmd.print_help(); return 0; }
 		cmd.check();
+
+		if (cmd.has(p_loadm)) {   // predict only: the model decides method and dimensions
+			for (const std::string &p : {p_method, p_dim, p_iter})
+				if (cmd.has(p)) throw std::string("-load_model scores with a trained model: -" + p + " does not apply");
+			if (cmd.get(p_task) != "r") throw std::string("unknown task");
+			if (!cmd.has(p_test) || !cmd.has(p_out)) throw std::string("-load_model needs -test and -out");
+			const std::string unk = cmd.get(p_unknown, "refuse");
+			if (unk != "refuse" && unk != "skip") throw std::string("-unknown_ids: refuse or skip");
+			run_score(ScoreRun{cmd.get(p_loadm), cmd.get(p_test), cmd.get(p_out), cmd.get(p_outvar),
+			                   (int32_t)cmd.geti(p_dev, 0), unk == "skip"});
+			return 0;
+		}
+		if (cmd.has(p_outvar) || cmd.has(p_unknown)) throw std::string("-out_var and -unknown_ids belong to -load_model");
 
 		const uint32_t seed = cmd.has(p_seed) ? (uint32_t)cmd.geti(p_seed, 0) : (uint32_t)time(NULL);
 		const std::string method = cmd.get(p_method, "mcmc");
@@ -1128,14 +1230,15 @@ int main(int argc, char **argv)
 		job.plan = cmd.geti(p_plan, 0) != 0;
 		job.online = OnlineRun{seed, init_stdev, num_iter, (uint32_t)cmd.geti(p_batch, 50), gp, G, D, k0, k1, k, vfile,
 		                       rlog, out, plog, cmd.has(p_save) ? cmd.get(p_save) : std::string(),
-		                       cmd.has(p_resume) ? cmd.get(p_resume) : std::string()};
+		                       cmd.has(p_resume) ? cmd.get(p_resume) : std::string(), cmd.get(p_savem)};
 		std::vector<double> reg;
 		for (const std::string &r : cmd.list(p_reg)) reg.push_back(atof(r.c_str()));
 		job.mc = McmcRun{method == "mcmc", seed, init_stdev, num_iter, reg, gp, G, D, k0, k1, k, vfile, rlog, out, plog,
-		                 cmd.has(p_save) ? cmd.get(p_save) : std::string(), cmd.has(p_resume) ? cmd.get(p_resume) : std::string()};
+		                 cmd.has(p_save) ? cmd.get(p_save) : std::string(), cmd.has(p_resume) ? cmd.get(p_resume) : std::string(),
+		                 cmd.get(p_savem)};
 		job.vb = VbRun{seed, init_stdev, num_iter, gp, G, D, k0, k1, k, vfile, rlog, out,
 		               cmd.has(p_save) ? cmd.get(p_save) : std::string(), cmd.has(p_resume) ? cmd.get(p_resume) : std::string(),
-		               plog};
+		               plog, cmd.get(p_savem)};
 
 		if (proto.nranks == 1) {   // one GPU, this process
 			run_rank(job, train, test, proto);

@@ -161,6 +161,40 @@ class HostData(C.Structure):
                 ("row_ptr", P_u64), ("row_ent", C.c_void_p), ("col_ptr", P_u64), ("col_ent", C.c_void_p)]
 
 
+MODEL_KINDS = {0: "vb", 1: "vb_online", 2: "als", 3: "mcmc_draw"}   # VBFM_MODEL_* (include/vbfm.h)
+ORDERS = {"auto": 0, "exact": 1, "group": 2}                         # VBFM_ORDER_*
+UNKNOWN_IDS = {"refuse": 0, "skip": 1}
+
+
+class ModelInfo(C.Structure):
+    """vbfm_model_info: what a model file's header says."""
+    _fields_ = [("kind", C.c_int32), ("k0", C.c_int32), ("k1", C.c_int32), ("num_factor", C.c_int32),
+                ("num_attribute", C.c_uint32), ("min_target", C.c_float), ("max_target", C.c_float),
+                ("iter", C.c_uint32), ("has_variance", C.c_int32), ("w0_or_mu0", C.c_double),
+                ("sigma_0_dash", C.c_double), ("alpha", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["kind_name"] = MODEL_KINDS.get(self.kind, "?")
+        return d
+
+
+class Csr(C.Structure):
+    _fields_ = [("num_rows", C.c_uint32), ("nnz", C.c_uint64), ("row_ptr", P_u64), ("row_ent", C.c_void_p)]
+
+
+class ScoreOpts(C.Structure):
+    _fields_ = [("order", C.c_int32), ("clip", C.c_int32), ("unknown_ids", C.c_int32), ("chunk_bytes", C.c_uint64)]
+
+
+class ScoreStats(C.Structure):
+    _fields_ = [("n_chunks", C.c_uint32), ("skipped_entries", C.c_uint64), ("ms_copy", C.c_double),
+                ("ms_kernel", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/vbfm.h declares (checked by tests/test_capi_cpu.py)
 EXPORTS = ["vbfm_abi_version", "vbfm_last_error", "vbfm_create", "vbfm_destroy", "vbfm_set_train",
            "vbfm_set_test", "vbfm_synth_generate", "vbfm_synth_multihot", "vbfm_get_csc", "vbfm_get_shape", "vbfm_get_levels",
@@ -172,7 +206,10 @@ EXPORTS = ["vbfm_abi_version", "vbfm_last_error", "vbfm_create", "vbfm_destroy",
            "vbfm_comm_unique_id", "vbfm_comm_init", "vbfm_comm_init_host", "vbfm_comm_info", "vbfm_exchange_info", "vbfm_placement_info", "vbfm_setup_info", "vbfm_load_data", "vbfm_free_host_data", "vbfm_save_data",
            "vbfm_init_params_host", "vbfm_mcmc_init", "vbfm_mcmc_set_params", "vbfm_mcmc_get_params",
            "vbfm_mcmc_init_caches", "vbfm_mcmc_iterate", "vbfm_mcmc_get_test_pred", "vbfm_mcmc_factor_sweep",
-           "vbfm_online_init", "vbfm_online_epoch", "vbfm_online_get_state", "vbfm_save_state", "vbfm_load_state"]
+           "vbfm_online_init", "vbfm_online_epoch", "vbfm_online_get_state", "vbfm_save_state", "vbfm_load_state",
+           "vbfm_model_file_info", "vbfm_model_write_host", "vbfm_model_read_host", "vbfm_model_save",
+           "vbfm_model_from_ctx", "vbfm_model_load", "vbfm_model_info_get", "vbfm_model_last_error",
+           "vbfm_model_destroy", "vbfm_score", "vbfm_score_device"]
 
 # vbfm_exchange_fn: int fn(void *user, void *buf, uint64_t count, int32_t dtype, int32_t op)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32)
@@ -254,6 +291,19 @@ def lib():
         L.vbfm_online_get_state.argtypes = [V, P_f64, P_f64, P_f64, P_f64, P_f64, P_f64, P_f64]
         L.vbfm_save_state.argtypes = [V, C.c_char_p, C.c_uint32]
         L.vbfm_load_state.argtypes = [V, C.c_char_p, C.POINTER(C.c_uint32)]
+        L.vbfm_model_file_info.argtypes = [C.c_char_p, C.POINTER(ModelInfo)]
+        L.vbfm_model_write_host.argtypes = [C.c_char_p, C.POINTER(ModelInfo), C.POINTER(Params), C.POINTER(McmcParams)]
+        L.vbfm_model_read_host.argtypes = [C.c_char_p, C.POINTER(ModelInfo), C.POINTER(Params), C.POINTER(McmcParams)]
+        L.vbfm_model_save.argtypes = [V, C.c_char_p, C.c_uint32]
+        L.vbfm_model_from_ctx.argtypes = [C.POINTER(V), V]
+        L.vbfm_model_load.argtypes = [C.POINTER(V), C.c_char_p, C.c_int32]
+        L.vbfm_model_info_get.argtypes = [V, C.POINTER(ModelInfo)]
+        L.vbfm_model_last_error.argtypes = [V]
+        L.vbfm_model_last_error.restype = C.c_char_p
+        L.vbfm_model_destroy.argtypes = [V]
+        L.vbfm_model_destroy.restype = None
+        L.vbfm_score.argtypes = [V, C.POINTER(Csr), C.POINTER(ScoreOpts), P_f64, P_f64, C.POINTER(ScoreStats)]
+        L.vbfm_score_device.argtypes = [V, V, C.c_int32, C.POINTER(ScoreOpts), P_f64, P_f64, C.POINTER(ScoreStats)]
         _lib = L
     return _lib
 
@@ -530,6 +580,12 @@ class FMLearnVB:
         self.num_iter_done = it.value
         return it.value
 
+    def save_model(self, path, num_iter=None):
+        """The parameters alone as a model file (include/vbfm.h vbfm_model_save): Model.load reads
+        it back without the train set. With several ranks only rank 0 writes."""
+        it = self.num_iter_done if num_iter is None else num_iter
+        _check(lib().vbfm_model_save(self._ctx, os.fsencode(path), int(it)), self._ctx)
+
     def predict(self):
         """pred_this: clipped test predictions of the last iteration."""
         out = np.zeros(self.n_test)
@@ -783,3 +839,135 @@ class FMLearnVBOnline(FMLearnVB):
                                                         ("nat_mu_w", "nat_sigma_w", "nat_mu_v", "nat_sigma_v",
                                                          "new_wj", "new_vj", "scalars")]), self._ctx)
         return out
+
+
+class Model:
+    """A trained model on one MI355X, scoring arbitrary rows (include/vbfm.h "model files and
+    scoring"): the mean prediction and, for the VB kinds, the variance term T_n (the predictive
+    variance of y is T_n + 1 / alpha).
+
+        m = Model.load("model.vbfm")                      # or Model.from_learner(fml)
+        mean, T = m.score(DataSubset.load("new.libfm"), variance=True)
+    """
+
+    def __init__(self, handle):
+        self._m = handle
+        self.last_stats = None
+        inf = ModelInfo()
+        _check(lib().vbfm_model_info_get(self._m, C.byref(inf)))
+        self.info = inf.as_dict()
+
+    @classmethod
+    def load(cls, path, device=0):
+        h = C.c_void_p()
+        _check(lib().vbfm_model_load(C.byref(h), os.fsencode(path), int(device)))
+        return cls(h)
+
+    @classmethod
+    def from_learner(cls, fml):
+        """Device-to-device snapshot of a learner's parameters as they are now."""
+        h = C.c_void_p()
+        _check(lib().vbfm_model_from_ctx(C.byref(h), fml._ctx), fml._ctx)
+        return cls(h)
+
+    @staticmethod
+    def file_info(path):
+        """The header of a model file, after validating the whole file. No GPU."""
+        inf = ModelInfo()
+        _check(lib().vbfm_model_file_info(os.fsencode(path), C.byref(inf)))
+        return inf.as_dict()
+
+    @staticmethod
+    def read_params(path):
+        """A model file's parameters as numpy arrays (v as [f][j], like get_params). No GPU."""
+        info = Model.file_info(path)
+        D, kd = info["num_attribute"], info["num_attribute"] * info["num_factor"]
+        if info["has_variance"]:
+            p = {k: np.zeros(n) for k, n in (("mu_w", D), ("sigma_w", D), ("mu_v", kd), ("sigma_v", kd))}
+            ps = Params(_ptr(p["mu_w"], P_f64), _ptr(p["sigma_w"], P_f64), _ptr(p["mu_v"], P_f64),
+                        _ptr(p["sigma_v"], P_f64), None, None, 0.0, 0.0, 0.0, 0.0)
+            _check(lib().vbfm_model_read_host(os.fsencode(path), None, C.byref(ps), None))
+            p.update(mu_0_dash=ps.mu_0_dash, sigma_0_dash=ps.sigma_0_dash, alpha=ps.alpha)
+        else:
+            p = {"w": np.zeros(D), "v": np.zeros(kd)}
+            ps = McmcParams(_ptr(p["w"], P_f64), _ptr(p["v"], P_f64), None, None, None, None, 0.0, 0.0, 0.0)
+            _check(lib().vbfm_model_read_host(os.fsencode(path), None, None, C.byref(ps)))
+            p.update(w0=ps.w0, alpha=ps.alpha)
+        p["info"] = info
+        return p
+
+    @staticmethod
+    def write_params(path, info, params):
+        """Write a model file from host arrays (info: the ModelInfo fields as a dict; params as
+        read_params returns them). No GPU."""
+        inf = ModelInfo(**{k: info[k] for k, _ in ModelInfo._fields_ if k in info})
+        a = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in params.items() if isinstance(v, np.ndarray)}
+        if inf.kind in (0, 1):
+            ps = Params(_ptr(a.get("mu_w"), P_f64), _ptr(a.get("sigma_w"), P_f64), _ptr(a.get("mu_v"), P_f64),
+                        _ptr(a.get("sigma_v"), P_f64), None, None, 0.0, 0.0, 0.0, 0.0)
+            _check(lib().vbfm_model_write_host(os.fsencode(path), C.byref(inf), C.byref(ps), None))
+        else:
+            ps = McmcParams(_ptr(a.get("w"), P_f64), _ptr(a.get("v"), P_f64), None, None, None, None, 0.0, 0.0, 0.0)
+            _check(lib().vbfm_model_write_host(os.fsencode(path), C.byref(inf), None, C.byref(ps)))
+
+    @property
+    def alpha(self):
+        return self.info["alpha"]
+
+    def _mcheck(self, rc):
+        if rc != 0:
+            msg = lib().vbfm_model_last_error(self._m)
+            raise VbfmError(msg.decode() if msg else "libvbfm error %d" % rc)
+
+    @staticmethod
+    def _opts(order, clip, unknown_ids, chunk_bytes):
+        return ScoreOpts(ORDERS[order], int(bool(clip)), UNKNOWN_IDS[unknown_ids], int(chunk_bytes))
+
+    def score(self, data, variance=False, order="auto", clip=True, unknown_ids="refuse", chunk_bytes=0):
+        """Mean prediction of every row of `data` -- a DataSubset that holds its rows (from
+        DataSubset.load) or a (row_ptr, feat, val) triple -- and with variance=True the pair
+        (mean, T). The rows stay in host memory and are staged in chunks of chunk_bytes."""
+        if isinstance(data, DataSubset):
+            if data.row_ptr is None:
+                raise VbfmError("score needs the rows (a data set from DataSubset.load, or a (row_ptr, feat, val) triple)")
+            rp = np.ascontiguousarray(data.row_ptr, dtype=np.uint64)
+            ent = np.ascontiguousarray(data.row_ent, dtype=ENTRY_DTYPE)
+        else:
+            row_ptr, feat, val = data
+            rp = np.ascontiguousarray(row_ptr, dtype=np.uint64)
+            ent = np.empty(len(feat), dtype=ENTRY_DTYPE)
+            ent["id"] = feat
+            ent["value"] = val
+        n = len(rp) - 1 if len(rp) else 0
+        rows = Csr(n, len(ent), _ptr(rp, P_u64), ent.ctypes.data if len(ent) else None)
+        mean = np.zeros(n)
+        var = np.zeros(n) if variance else None
+        st = ScoreStats()
+        o = self._opts(order, clip, unknown_ids, chunk_bytes)
+        self._mcheck(lib().vbfm_score(self._m, C.byref(rows), C.byref(o), _ptr(mean, P_f64), _ptr(var, P_f64),
+                                      C.byref(st)))
+        self.last_stats = st.as_dict()
+        return (mean, var) if variance else mean
+
+    def score_device(self, fml, which, variance=False, order="auto", clip=True, unknown_ids="refuse"):
+        """The same for the train (which=0) or test (1) set a learner holds on the device."""
+        n = fml.shape(which)[0]
+        mean = np.zeros(n)
+        var = np.zeros(n) if variance else None
+        st = ScoreStats()
+        o = self._opts(order, clip, unknown_ids, 0)
+        self._mcheck(lib().vbfm_score_device(self._m, fml._ctx, int(which), C.byref(o), _ptr(mean, P_f64),
+                                             _ptr(var, P_f64), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return (mean, var) if variance else mean
+
+    def close(self):
+        if self._m:
+            lib().vbfm_model_destroy(self._m)
+            self._m = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
