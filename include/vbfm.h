@@ -42,6 +42,10 @@ extern "C" {
 
 typedef struct vbfm_ctx vbfm_ctx;
 
+/* vbfm_config::task (-task r | c, libfm.cpp:137-143) */
+#define VBFM_TASK_REGRESSION 0
+#define VBFM_TASK_CLASSIFICATION 1
+
 /* == sparse_entry<float> (src/util/fmatrix.h:36-39): 8 bytes, id then value. In a
  * transposed (column) matrix `id` is the row index. */
 typedef struct {
@@ -73,7 +77,9 @@ typedef struct {
 	float min_target;         /* train.min_target (libfm.cpp:333) */
 	float max_target;         /* train.max_target (libfm.cpp:332) */
 	int32_t device;           /* HIP device ordinal */
-	int32_t task;             /* 0 = regression (the only task the VB learner evaluates) */
+	int32_t task;             /* VBFM_TASK_REGRESSION, or VBFM_TASK_CLASSIFICATION (-task c: binary targets,
+	                             probit link) which the MCMC / ALS learner provides; the VB and online VB
+	                             entry points refuse a classification context */
 	/* Placement search of the level-ordered store's two record buffers (no reference counterpart;
 	 * DESIGN.md §5b): the scattered record writes of a level run up to ~20 % faster or slower
 	 * depending on where the driver placed the buffers, so at store build (>= 2e6 rows) the library
@@ -156,6 +162,11 @@ int vbfm_synth_generate(vbfm_ctx *ctx, int32_t which, uint32_t num_rows, uint32_
  * column-gather layout. Rows [row_offset, row_offset + num_rows) of the one-rank data set. */
 int vbfm_synth_multihot(vbfm_ctx *ctx, int32_t which, uint32_t num_rows, uint32_t num_features, uint32_t lo,
                         uint32_t hi, uint64_t seed, int32_t xmode, uint64_t model_seed, uint64_t row_offset);
+/* Binary targets from a device-generated set (no reference counterpart): target = target >=
+ * threshold ? +1 : -1 on the device; *positives (may be NULL) receives the number of +1 rows of
+ * this rank's set. The set's target range becomes [-1, 1]. Binarizing the train set of an MCMC /
+ * ALS context drops its row caches (they hold yhat - the old target): vbfm_mcmc_init_caches follows. */
+int vbfm_synth_binarize(vbfm_ctx *ctx, int32_t which, float threshold, uint64_t *positives);
 /* Copy back the device copy of a data set (parity of the device transpose / generator). */
 int vbfm_get_csc(vbfm_ctx *ctx, int32_t which, uint64_t *col_ptr /*[nf+1]*/, vbfm_entry *col_ent /*[nnz]*/,
                  float *target /*[rows]*/);
@@ -392,7 +403,8 @@ int vbfm_online_get_state(vbfm_ctx *ctx, double *nat_mu_w, double *nat_sigma_w, 
 
 /* ---- MCMC / ALS learner (-method mcmc | als) -------------------------------------------
  * Replaces fm_learn_mcmc / fm_learn_mcmc_simultaneous (src/libfm/src/fm_learn_mcmc.h,
- * src/libfm/src/fm_learn_mcmc_simultaneous.h), regression, without relation blocks.
+ * src/libfm/src/fm_learn_mcmc_simultaneous.h), regression and binary classification, without
+ * relation blocks.
  * vbfm_mcmc_init turns a context made by vbfm_create into an MCMC/ALS learner; the data
  * hand-over (vbfm_set_train / vbfm_set_test / vbfm_synth_generate), vbfm_comm_init and the
  * level schedule are the VB learner's. State is the model's point values fm.w0 / fm.w /
@@ -452,6 +464,29 @@ int vbfm_mcmc_iterate(vbfm_ctx *ctx, vbfm_mcmc_stats *out);        /* one pass o
 /* fm_learn_mcmc::predict (fm_learn_mcmc.h:355-381): sampling -> pred_sum_all / num_iter,
  * else the last iteration's predictions; clipped to the train target range */
 int vbfm_mcmc_get_test_pred(vbfm_ctx *ctx, int32_t num_iter, double *pred /*[test rows]*/);
+/* Binary classification (vbfm_config::task = VBFM_TASK_CLASSIFICATION; the augmented probit
+ * sampler of fm_learn_mcmc_simultaneous.h:82-89, 176-221, 262-301). Targets are < 0 or >= 0. The
+ * sweeps are regression's on a latent target: after every re-prediction each train row's e becomes
+ * yhat - s, s from N(yhat, 1) truncated to the target's side of 0 -- its expectation (als), a draw
+ * from the reference's stream row by row after draw_all's draws (mcmc, VBFM_RNG_REFERENCE; one rank
+ * only) or a draw of the counter-based generator keyed (seed, iteration, global row, attempt)
+ * (mcmc, VBFM_RNG_DEVICE; row shards must be contiguous in rank order). Test predictions are
+ * Phi(yhat) with the reference's polynomial erf (random.h:47-69). vbfm_mcmc_stats then holds 0 in
+ * train_rmse, rmse_* and mae_*; vbfm_mcmc_class_info returns the last iteration's figures
+ * (_evaluate_class, :383-401: accuracy, and the mean log10-likelihood with p clamped to
+ * [0.01, 0.99]; ll_all, which the reference leaves uninitialised, is computed on the running mean).
+ * MAP@5 of the reference's "#Iter=" line is not reproduced (it reads a fixed side file).
+ * vbfm_mcmc_get_test_pred clips to [0, 1]. */
+typedef struct {
+	double acc_train;           /* "Train=": correct train rows / rows, on this iteration's yhat */
+	double acc_this, acc_all;   /* test: this iteration's Phi(yhat); the running mean ("Test=") */
+	double ll_this, ll_all;
+	uint64_t n_train_correct, n_test_correct_this, n_test_correct_all;   /* the counts, over all ranks */
+	uint32_t nonfinite_rows;    /* train rows whose yhat was NaN or +-inf (their e is NaN) */
+	uint32_t capped_rows;       /* VBFM_RNG_DEVICE: rows whose 64 rejection attempts all failed (p <= 2^-64
+	                               each) and that took the truncated expectation */
+} vbfm_mcmc_class_stats;
+int vbfm_mcmc_class_info(vbfm_ctx *ctx, vbfm_mcmc_class_stats *out);   /* fails on a regression context */
 /* the v draws of all factors alone (q-cache + draw_v sweeps, :501-621), for the bench */
 int vbfm_mcmc_factor_sweep(vbfm_ctx *ctx, double *ms_device);
 
@@ -517,6 +552,15 @@ int vbfm_model_file_info(const char *path, vbfm_model_info *out);
 int vbfm_model_write_host(const char *path, const vbfm_model_info *info, const vbfm_params *vb,
                           const vbfm_mcmc_params *mc);
 int vbfm_model_read_host(const char *path, vbfm_model_info *info, vbfm_params *vb, vbfm_mcmc_params *mc);
+/* The task of a model (VBFM_TASK_*). vbfm_model_info cannot grow, so the task travels beside it: in
+ * the file it is the header word that was reserved (0 = regression: every earlier file reads as
+ * before). The earlier reader ignored that word, so a classification model is written with format
+ * version 3, which an earlier library refuses (2 was never written and stays refused); regression
+ * files keep version 1 byte for byte.
+ * vbfm_model_write_host writes a regression model; only the ALS / MCMC kinds take task c. */
+int vbfm_model_file_task(const char *path, int32_t *task);   /* host-only; validates the whole file */
+int vbfm_model_write_host_task(const char *path, const vbfm_model_info *info, const vbfm_params *vb,
+                               const vbfm_mcmc_params *mc, int32_t task);
 
 /* A model on a device: the tables the scoring kernels read. Failures of a call that has a model
  * are in vbfm_model_last_error(m), those without in vbfm_last_error(NULL). */
@@ -527,6 +571,7 @@ int vbfm_model_save(vbfm_ctx *ctx, const char *path, uint32_t iter);
 int vbfm_model_from_ctx(vbfm_model **out, vbfm_ctx *ctx);   /* device-to-device snapshot on ctx's device */
 int vbfm_model_load(vbfm_model **out, const char *path, int32_t device);
 int vbfm_model_info_get(const vbfm_model *m, vbfm_model_info *out);
+int vbfm_model_task(const vbfm_model *m, int32_t *task);
 const char *vbfm_model_last_error(const vbfm_model *m);
 void vbfm_model_destroy(vbfm_model *m);
 
@@ -545,7 +590,8 @@ typedef struct {
                                 summed by a fixed butterfly (bit-identical to the wave kernels) */
 typedef struct {
 	int32_t order;         /* VBFM_ORDER_* */
-	int32_t clip;          /* 1: mean clipped to [min_target, max_target] as pred_this is */
+	int32_t clip;          /* 1: mean clipped to [min_target, max_target] as pred_this is; a model of task c:
+	                          1 = the probability Phi(yhat) as pred_this is, 0 = the raw yhat */
 	int32_t unknown_ids;   /* ids >= num_attribute: 0 refuse (the message names the first such row and its
 	                          smallest unknown id), 1 skip the entry */
 	uint64_t chunk_bytes;  /* device memory per staged chunk of host rows, 0 = default (VBFM_SCORE_CHUNK_DEFAULT) */

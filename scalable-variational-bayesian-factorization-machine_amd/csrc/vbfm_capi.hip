@@ -160,6 +160,14 @@ void require_train(vbfm_ctx *c)
 	if (!c->sched_ready) build_schedule(c);
 }
 
+// The reference's VB classification branch rewrites e under row caches that VB never re-predicts:
+// not a defined algorithm, so the VB learners take regression only
+void require_regression(vbfm_ctx *c)
+{
+	if (c->task != VBFM_TASK_REGRESSION)
+		throw std::string("task c (binary classification) is provided by the mcmc and als learners, not by vb / vb_online");
+}
+
 // VBFM_PREFETCH=0 (A/B): the level kernels do not touch the next level's column bounds (read once
 // per context)
 static bool pf_enabled(vbfm_ctx *c)
@@ -647,7 +655,8 @@ int vbfm_create(vbfm_ctx **out, const vbfm_config *cfg)
 {
 	if (!out || !cfg) return fail(nullptr, "vbfm_create: null argument");
 	*out = nullptr;
-	if (cfg->task != 0) return fail(nullptr, "task not supported by the VB learner (regression only)");
+	if (cfg->task != VBFM_TASK_REGRESSION && cfg->task != VBFM_TASK_CLASSIFICATION)
+		return fail(nullptr, "unknown task (VBFM_TASK_REGRESSION or VBFM_TASK_CLASSIFICATION)");
 	if (cfg->num_factor < 0) return fail(nullptr, "negative number of factors");
 	if (cfg->num_attr_groups == 0) return fail(nullptr, "num_attr_groups must be >= 1");
 	if (cfg->place_candidates < 0) return fail(nullptr, "place_candidates must be >= 0");
@@ -659,6 +668,7 @@ int vbfm_create(vbfm_ctx **out, const vbfm_config *cfg)
 	c->k0 = cfg->k0 != 0; c->k1 = cfg->k1 != 0; c->k = cfg->num_factor;
 	c->D = cfg->num_attribute; c->G = cfg->num_attr_groups;
 	c->min_target = cfg->min_target; c->max_target = cfg->max_target;
+	c->task = cfg->task;
 	c->place.cands_cfg = cfg->place_candidates;
 	c->place.budget_cfg = cfg->place_budget_bytes;
 	{
@@ -880,7 +890,7 @@ int vbfm_init_caches(vbfm_ctx *c)
 	return guarded(c, [&] {
 		if (c->mc) throw std::string("an MCMC / ALS context: use the vbfm_mcmc_* entry points");
 		if (c->ov) throw std::string("an online VB context: use vbfm_online_epoch");
-		require_train(c);
+		require_regression(c); require_train(c);
 		no_partial(c);
 		// fm_learn_vb_simultaneous.h:37-44: yhat of train and test, T of train, e = y - yhat
 		rows_row_order(c);
@@ -895,20 +905,20 @@ int vbfm_init_caches(vbfm_ctx *c)
 int vbfm_step_w0(vbfm_ctx *c)
 {
 	if (!c) return fail(nullptr, "null context");
-	return guarded(c, [&] { require_train(c); no_partial(c); if (c->k0) step_w0(c); sync(c); });
+	return guarded(c, [&] { require_regression(c); require_train(c); no_partial(c); if (c->k0) step_w0(c); sync(c); });
 }
 
 int vbfm_step_w(vbfm_ctx *c)
 {
 	if (!c) return fail(nullptr, "null context");
-	return guarded(c, [&] { require_train(c); no_partial(c); if (c->k1) step_w(c); sync(c); });
+	return guarded(c, [&] { require_regression(c); require_train(c); no_partial(c); if (c->k1) step_w(c); sync(c); });
 }
 
 int vbfm_step_qcache(vbfm_ctx *c, int32_t f)
 {
 	if (!c) return fail(nullptr, "null context");
 	return guarded(c, [&] {
-		require_train(c);
+		require_regression(c); require_train(c);
 		if (f < 0 || f >= c->k) throw std::string("factor out of range");
 		no_partial(c);
 		step_qcache(c, f);
@@ -920,7 +930,7 @@ int vbfm_step_v(vbfm_ctx *c, int32_t f)
 {
 	if (!c) return fail(nullptr, "null context");
 	return guarded(c, [&] {
-		require_train(c);
+		require_regression(c); require_train(c);
 		if (f < 0 || f >= c->k) throw std::string("factor out of range");
 		no_partial(c);
 		if (c->q_ready[f & 1] != f) throw std::string("vbfm_step_v: q-cache of this factor is not current (vbfm_step_qcache)");
@@ -933,7 +943,7 @@ int vbfm_step_w_level(vbfm_ctx *c, int32_t level)
 {
 	if (!c) return fail(nullptr, "null context");
 	return guarded(c, [&] {
-		require_train(c);
+		require_regression(c); require_train(c);
 		if (!c->k1) throw std::string("k1 = 0: there is no w sweep");
 		step_level(c, true, 0, (uint32_t)level);
 		sync(c);
@@ -944,7 +954,7 @@ int vbfm_step_v_level(vbfm_ctx *c, int32_t f, int32_t level)
 {
 	if (!c) return fail(nullptr, "null context");
 	return guarded(c, [&] {
-		require_train(c);
+		require_regression(c); require_train(c);
 		if (f < 0 || f >= c->k) throw std::string("factor out of range");
 		step_level(c, false, f, (uint32_t)level);
 		sync(c);
@@ -955,7 +965,7 @@ int vbfm_step_hyper(vbfm_ctx *c, int32_t *early)
 {
 	if (!c) return fail(nullptr, "null context");
 	return guarded(c, [&] {
-		require_train(c);
+		require_regression(c); require_train(c);
 		no_partial(c);
 		const bool e = step_hyper(c, nullptr, nullptr, nullptr);
 		if (early) *early = e ? 1 : 0;
@@ -1031,7 +1041,7 @@ int vbfm_iterate(vbfm_ctx *c, vbfm_iter_stats *o)
 	return guarded(c, [&] {
 		if (c->mc) throw std::string("an MCMC / ALS context: use the vbfm_mcmc_* entry points");
 		if (c->ov) throw std::string("an online VB context: use vbfm_online_epoch");
-		require_train(c);
+		require_regression(c); require_train(c);
 		no_partial(c);
 		if (!c->e_test) throw std::string("no test data set (vbfm_set_test)");
 		vbfm_iter_stats st;

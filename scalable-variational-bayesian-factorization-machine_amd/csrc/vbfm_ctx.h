@@ -21,10 +21,10 @@ extern "C" const char *vbfm_host_last_error(void);
 extern "C" void vbfm_host_set_error(const char *msg);
 // model files with the payload as the library stores it (vbfm_host.cpp): the w table, then the v
 // table [j*k + f]; {mu, sigma} pairs for the VB kinds, plain values for ALS / MCMC
-extern "C" int vbfm_host_model_write_raw(const char *path, const vbfm_model_info *info, const double *w_tab,
-                                         const double *v_tab);
+extern "C" int vbfm_host_model_write_raw(const char *path, const vbfm_model_info *info, int32_t task,
+                                         const double *w_tab, const double *v_tab);
 // alloc provides the tables once the file has proved sound (magic, sizes, checksum)
-extern "C" int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info,
+extern "C" int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info, int32_t *task,
                                         int (*alloc)(void *user, const vbfm_model_info *info, double **w_tab,
                                                      double **v_tab),
                                         void *user);
@@ -137,6 +137,7 @@ struct vbfm_ctx {
 	std::vector<uint32_t> group_h, per_group;
 	uint32_t *group_d = nullptr;
 	float min_target = 0, max_target = 0;
+	int task = VBFM_TASK_REGRESSION;   // VBFM_TASK_*: classification runs on the MCMC / ALS learner only
 	DevData tr, te;
 	RowRec *rows = nullptr;
 	double *scratch_n = nullptr;   // yhat of train at init
@@ -411,6 +412,7 @@ void alloc_rows(vbfm_ctx *c);                     // the records of a new train 
 uint32_t global_nf(vbfm_ctx *c, uint32_t nf);     // the train feature count every shard pads to
 double finish_sum(vbfm_ctx *c, uint32_t nblocks);
 void require_train(vbfm_ctx *c);
+void require_regression(vbfm_ctx *c);   // the VB and online VB learners: refuse a task-c context
 void no_partial(vbfm_ctx *c);
 uint32_t nlevels(vbfm_ctx *c);
 constexpr size_t NO_SPAN = ~(size_t)0;   // prof_begin: this launch is not timed
@@ -467,6 +469,8 @@ void mc_state_write(vbfm_ctx *c, CkptFile &f);
 void mc_state_read(vbfm_ctx *c, CkptFile &f);
 // what a model snapshot takes beside the tables (vbfm_score.hip): fm.w0, alpha, sampling or ALS
 void mc_model_scalars(vbfm_ctx *c, double *w0, double *alpha, bool *sample);
+// the train targets changed under the row caches (vbfm_synth_binarize): vbfm_mcmc_init_caches again
+void mc_drop_caches(vbfm_ctx *c);
 
 // ---- vbfm_online.hip: the online VB learner ---------------------------------------------------
 void ov_free(vbfm_ctx *c);

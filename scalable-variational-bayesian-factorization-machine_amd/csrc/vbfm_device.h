@@ -132,6 +132,8 @@ enum {
 	CNT_NAN_MU_W = 0, CNT_NAN_SIGMA_W, CNT_INF_MU_W,
 	CNT_NAN_MU_V, CNT_NAN_SIGMA_V, CNT_INF_MU_V,
 	CNT_RNG_SKIP,   // MCMC: draws not taken (non-finite or zero variance)
+	CNT_CLASS_NONFINITE,   // task c: train rows whose yhat was NaN or +-inf (e becomes NaN)
+	CNT_CLASS_CAPPED,      // task c, device draws: rows that took the expectation after the attempt cap
 	CNT_N
 };
 
@@ -488,6 +490,24 @@ hipError_t mc_train_update(RowRec *rows, const double *yhat, const float *target
 hipError_t mc_test_update(const double *e_test, const float *target, uint32_t n, double mn, double mx,
                           double inv_iters, double *pred_this, double *pred_sum, double *out, uint32_t nblocks,
                           hipStream_t s);
+// task c (vbfm_class_math.h), in place of mc_train_update: per block the count of correct train
+// rows at out[b]; e = yhat - s with the latent target s of mode VBFM_CLASS_ALS (truncated
+// expectation), _GIVEN (s_given[row]: drawn on the host from the reference's stream) or _DEVICE
+// (drawn in the kernel, keyed (seed, stream, row0 + row, attempt))
+#define VBFM_CLASS_ALS 0
+#define VBFM_CLASS_GIVEN 1
+#define VBFM_CLASS_DEVICE 2
+hipError_t mc_class_train_update(RowRec *rows, const double *yhat, const float *target, uint32_t n, int mode,
+                                 const double *s_given, uint64_t seed, uint64_t stream, uint64_t row0,
+                                 uint32_t *counters, double *out, uint32_t nblocks, const uint32_t *pos, hipStream_t s);
+// task c, in place of mc_test_update: pred_this = Phi(yhat), pred_sum += Phi(yhat); per block
+// (correct_this, ll_this, correct_all, ll_all) at out[4*b]
+hipError_t mc_class_test_update(const double *e_test, const float *target, uint32_t n, double inv_iters,
+                                double *pred_this, double *pred_sum, double *out, uint32_t nblocks, hipStream_t s);
+// target = target >= threshold ? +1 : -1 in place; *positives (preset to 0) counts the +1
+hipError_t mc_binarize(float *target, uint32_t n, float threshold, uint32_t *positives, hipStream_t s);
+// out[r] = Phi(out[r]) (scores of a task-c model)
+hipError_t mc_class_link(double *out, uint32_t n, hipStream_t s);
 // mode 0: sum p ; mode 1: sum (p - c)^2 per (w | factor f, group g) chunk
 hipError_t mc_param_sums(const double2 *pw, const double2 *pv, const uint32_t *perm, const Chunk *chunks,
                          uint32_t nchunks, int mode, const double *cw, const double *cv, int k, double *out,

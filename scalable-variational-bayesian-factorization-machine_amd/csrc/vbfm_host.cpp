@@ -366,18 +366,22 @@ int write_sparse(const std::string &fn, uint32_t nrows, uint32_t ncols, uint64_t
 // ---- model files (include/vbfm.h "model files and scoring") --------------------------------------
 struct ModelHeader {
 	char magic[8];            // "VBFMMD01"
-	uint32_t version;         // 1
+	uint32_t version;         // 1; 3 for a file whose task is not regression
 	int32_t kind, k0, k1, k;
 	uint32_t D;
 	float min_target, max_target;
-	uint32_t iter, reserved;
+	uint32_t iter, task;      // task: VBFM_TASK_*; 0 in every version-1 file (the word was reserved)
 	double s0, s1, alpha;     // VB kinds: mu_0_dash, sigma_0_dash; ALS / MCMC: w0, 0
 	uint64_t payload;         // bytes behind the header
 	uint64_t checksum;        // of the payload (Sum64)
 };
 static_assert(sizeof(ModelHeader) == 88, "model file header layout");
 constexpr char MODEL_MAGIC[8] = {'V', 'B', 'F', 'M', 'M', 'D', '0', '1'};
-constexpr uint32_t MODEL_VERSION = 1;
+// Version 1 readers ignore the word that now holds the task, so a classification model is written
+// with a later version: an older library refuses it instead of scoring it as a regression model.
+// Regression files stay version 1, byte for byte. The later version is 3: version 2 was never
+// written and stays refused (the model tests use it as their example of a future version).
+constexpr uint32_t MODEL_VERSION = 1, MODEL_VERSION_TASK = 3;
 constexpr size_t MODEL_BUF = 1 << 15;   // doubles per I/O piece (256 KiB): the only buffer of both passes
 
 // 64-bit checksum over the payload's 8-byte words in file order (the payload is doubles only)
@@ -407,12 +411,13 @@ bool model_sizes(int32_t kind, int32_t k, uint32_t D, uint64_t *nw, uint64_t *nv
 	return true;
 }
 
-ModelHeader model_header(const vbfm_model_info &in)
+ModelHeader model_header(const vbfm_model_info &in, int32_t task)
 {
 	ModelHeader h;
 	memset(&h, 0, sizeof(h));
 	memcpy(h.magic, MODEL_MAGIC, 8);
-	h.version = MODEL_VERSION;
+	h.version = task == VBFM_TASK_REGRESSION ? MODEL_VERSION : MODEL_VERSION_TASK;
+	h.task = (uint32_t)task;
 	h.kind = in.kind; h.k0 = in.k0 != 0; h.k1 = in.k1 != 0; h.k = in.num_factor;
 	h.D = in.num_attribute;
 	h.min_target = in.min_target; h.max_target = in.max_target;
@@ -441,12 +446,17 @@ struct FileCloser {
 
 // header + payload to <path>.tmp, fsync, rename (as checkpoints are written); get(i) is the i-th
 // double of the payload
-template <class Get> int model_write(const char *path, const vbfm_model_info *info, Get get)
+template <class Get> int model_write(const char *path, const vbfm_model_info *info, int32_t task, Get get)
 {
 	if (!path || !info) { g_host_err = "model file: null argument"; return -1; }
+	if (task != VBFM_TASK_REGRESSION && task != VBFM_TASK_CLASSIFICATION) { g_host_err = "model file: unknown task"; return -1; }
+	if (task == VBFM_TASK_CLASSIFICATION && info->kind != VBFM_MODEL_ALS && info->kind != VBFM_MODEL_MCMC_DRAW) {
+		g_host_err = "model file: task c is provided by the ALS / MCMC kinds only";
+		return -1;
+	}
 	if (info->kind < VBFM_MODEL_VB || info->kind > VBFM_MODEL_MCMC_DRAW) { g_host_err = "model file: unknown kind"; return -1; }
 	if (info->num_factor < 0) { g_host_err = "model file: negative number of factors"; return -1; }
-	ModelHeader h = model_header(*info);
+	ModelHeader h = model_header(*info, task);
 	uint64_t nw, nv;
 	if (!model_sizes(h.kind, h.k, h.D, &nw, &nv, &h.payload)) {
 		g_host_err = "model file: num_attribute * (num_factor + 1) * entry size overflows 64 bits";
@@ -494,13 +504,22 @@ template <class Put> int model_read(const char *path, ModelHeader *hout, Put put
 		return -1;
 	}
 	if (memcmp(h.magic, MODEL_MAGIC, 8) != 0) { g_host_err = "not a libvbfm model file (bad magic): " + p; return -1; }
-	if (h.version != MODEL_VERSION) {
+	if (h.version != MODEL_VERSION && h.version != MODEL_VERSION_TASK) {
 		g_host_err = "model file of format version " + std::to_string(h.version) + ", this library reads version " +
-		             std::to_string(MODEL_VERSION) + ": " + p;
+		             std::to_string(MODEL_VERSION) + " (and " + std::to_string(MODEL_VERSION_TASK) + ", a model of task c): " + p;
+		return -1;
+	}
+	if (h.version == MODEL_VERSION) h.task = VBFM_TASK_REGRESSION;   // the word was reserved
+	if (h.task != VBFM_TASK_REGRESSION && h.task != VBFM_TASK_CLASSIFICATION) {
+		g_host_err = "model file of unknown task " + std::to_string(h.task) + ": " + p;
 		return -1;
 	}
 	if (h.kind < VBFM_MODEL_VB || h.kind > VBFM_MODEL_MCMC_DRAW) {
 		g_host_err = "model file of unknown kind " + std::to_string(h.kind) + ": " + p;
+		return -1;
+	}
+	if (h.task == VBFM_TASK_CLASSIFICATION && h.kind != VBFM_MODEL_ALS && h.kind != VBFM_MODEL_MCMC_DRAW) {
+		g_host_err = "model file of task c with a kind other than ALS / MCMC: " + p;
 		return -1;
 	}
 	if (h.k < 0) { g_host_err = "model file with a negative number of factors: " + p; return -1; }
@@ -566,8 +585,22 @@ int vbfm_model_file_info(const char *path, vbfm_model_info *out)
 	return 0;
 }
 
+int vbfm_model_file_task(const char *path, int32_t *task)
+{
+	ModelHeader h;
+	if (model_read(path, &h, [](uint64_t, double) {}, false)) return -1;
+	if (task) *task = (int32_t)h.task;
+	return 0;
+}
+
 int vbfm_model_write_host(const char *path, const vbfm_model_info *info, const vbfm_params *vb,
                           const vbfm_mcmc_params *mc)
+{
+	return vbfm_model_write_host_task(path, info, vb, mc, VBFM_TASK_REGRESSION);
+}
+
+int vbfm_model_write_host_task(const char *path, const vbfm_model_info *info, const vbfm_params *vb,
+                               const vbfm_mcmc_params *mc, int32_t task)
 {
 	if (!path || !info) { g_host_err = "vbfm_model_write_host: null argument"; return -1; }
 	const bool isvb = model_vb(info->kind);
@@ -580,7 +613,7 @@ int vbfm_model_write_host(const char *path, const vbfm_model_info *info, const v
 		                  : "vbfm_model_write_host: an ALS / MCMC kind needs w and v (vbfm_mcmc_params)";
 		return -1;
 	}
-	return model_write(path, info, [&](uint64_t i) {
+	return model_write(path, info, task, [&](uint64_t i) {
 		const ModelSlot s = model_slot(isvb, D, k, i);
 		return a[s.arr][s.idx];
 	});
@@ -608,16 +641,17 @@ int vbfm_model_read_host(const char *path, vbfm_model_info *info, vbfm_params *v
 
 // the payload as the library stores it (internal: vbfm_score.hip): w_tab then v_tab, pairs for the
 // VB kinds
-int vbfm_host_model_write_raw(const char *path, const vbfm_model_info *info, const double *w_tab, const double *v_tab)
+int vbfm_host_model_write_raw(const char *path, const vbfm_model_info *info, int32_t task, const double *w_tab,
+                              const double *v_tab)
 {
 	if (!info) { g_host_err = "model file: null argument"; return -1; }
 	const uint64_t nw = (uint64_t)info->num_attribute * (model_vb(info->kind) ? 2 : 1);
-	return model_write(path, info, [&](uint64_t i) { return i < nw ? w_tab[i] : v_tab[i - nw]; });
+	return model_write(path, info, task, [&](uint64_t i) { return i < nw ? w_tab[i] : v_tab[i - nw]; });
 }
 
 // ... and read back: alloc(user, info, &w_tab, &v_tab) is called once the whole file has proved
 // sound (never for a refused file), then the tables are filled
-int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info,
+int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info, int32_t *task,
                              int (*alloc)(void *user, const vbfm_model_info *info, double **w_tab, double **v_tab),
                              void *user)
 {
@@ -639,6 +673,7 @@ int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info,
 	if (!ready) prepare();   // an empty payload
 	if (failed) { g_host_err = "model file: out of memory for the tables: " + std::string(path); return -1; }
 	if (info) *info = model_info(h);
+	if (task) *task = (int32_t)h.task;
 	return 0;
 }
 

@@ -11,6 +11,7 @@
 // feature j (host replay of glibc rand(), see vbfm_rng.h), or -- in device-RNG mode -- a
 // counter-based normal keyed by (seed, iteration, factor, feature), the same on every shard.
 #include "vbfm_mc_math.h"
+#include "vbfm_class_math.h"
 
 namespace {
 
@@ -234,6 +235,100 @@ __global__ __launch_bounds__(BLOCK) void k_mc_test_update(const double *e_test, 
 	}
 }
 
+// ---- binary classification (-task c, probit link; vbfm_class_math.h) ------------------------
+// The row step after the full re-predict of train (fm_learn_mcmc_simultaneous.h:189-221), in
+// place of k_mc_train_update: count the correct rows, form the latent target s of the row and
+// leave e = yhat - s. MODE VBFM_CLASS_ALS: s is the expectation of the truncated normal;
+// _GIVEN: s was drawn on the host from the reference's stream (s_given[row]); _DEVICE: s is drawn
+// here from the counter-based generator. The rejection loop of _DEVICE is bounded
+// (CLASS_MAX_ATTEMPTS) and not entered for a non-finite yhat, so the kernel cannot spin; such
+// rows are counted (CNT_CLASS_NONFINITE, CNT_CLASS_CAPPED). The block sum of the 0 / 1 counts is
+// exact in fp64.
+template <int BLOCK, int MODE>
+__global__ __launch_bounds__(BLOCK) void k_mc_class_train_update(RowRec *rows, const double *yhat, const float *target,
+                                                                 uint32_t n, const double *s_given, uint64_t seed,
+                                                                 uint64_t stream, uint64_t row0, uint32_t *counters,
+                                                                 double *out, const uint32_t *pos)
+{
+	__shared__ double lds[BLOCK / 64];
+	double cnt = 0.0;
+	uint32_t nonfinite = 0, capped = 0;
+	for (uint32_t c = blockIdx.x * BLOCK + threadIdx.x; c < n; c += gridDim.x * BLOCK) {
+		const double yh = yhat[c];
+		const float y = target[c];
+		if (vbcm::class_correct(vbcm::Phi(yh), y)) cnt += 1.0;
+		const bool positive = y >= 0.0f;
+		double s;
+		if constexpr (MODE == VBFM_CLASS_ALS) {
+			s = positive ? vbcm::expect_left(yh) : vbcm::expect_right(yh);
+			if (bad(yh)) nonfinite++;
+		} else if constexpr (MODE == VBFM_CLASS_GIVEN) {
+			s = s_given[c];
+		} else {
+			const vbcm::RowKey key(seed, stream, row0 + c);
+			int attempts = 0, flag;
+			s = vbcm::class_sample_target(yh, positive, key, vbcm::CLASS_MAX_ATTEMPTS, &attempts, &flag);
+			nonfinite += flag == vbcm::CLASS_NONFINITE;
+			capped += flag == vbcm::CLASS_CAPPED;
+		}
+		rows[pos ? pos[c] : c].e = yh - s;
+	}
+	if (nonfinite) atomicAdd(&counters[CNT_CLASS_NONFINITE], nonfinite);
+	if (capped) atomicAdd(&counters[CNT_CLASS_CAPPED], capped);
+	cnt = block_sum1<BLOCK>(cnt, lds);
+	if (threadIdx.x == 0) out[blockIdx.x] = cnt;
+}
+
+// test side of task c (:178-186 and _evaluate_class :383-401): pred_this = Phi(yhat), pred_sum +=
+// Phi(yhat) without a clip; per block (correct_this, ll_this, correct_all, ll_all), the layout of
+// k_mc_test_update's out
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_mc_class_test_update(const double *e_test, const float *target, uint32_t n,
+                                                                double inv_iters, double *pred_this, double *pred_sum,
+                                                                double *out)
+{
+	__shared__ double lds[BLOCK / 64];
+	double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+	for (uint32_t c = blockIdx.x * BLOCK + threadIdx.x; c < n; c += gridDim.x * BLOCK) {
+		const double p = vbcm::Phi(e_test[c]);
+		pred_this[c] = p;
+		const double sum = pred_sum[c] + p;
+		pred_sum[c] = sum;
+		const float y = target[c];
+		const double pa = sum * inv_iters;
+		if (vbcm::class_correct(p * 1.0, y)) s0 += 1.0;
+		s1 += vbcm::class_ll(p * 1.0, y);
+		if (vbcm::class_correct(pa, y)) s2 += 1.0;
+		s3 += vbcm::class_ll(pa, y);
+	}
+	s0 = block_sum1<BLOCK>(s0, lds);
+	s1 = block_sum1<BLOCK>(s1, lds);
+	s2 = block_sum1<BLOCK>(s2, lds);
+	s3 = block_sum1<BLOCK>(s3, lds);
+	if (threadIdx.x == 0) {
+		double *o = out + 4 * (size_t)blockIdx.x;
+		o[0] = s0; o[1] = s1; o[2] = s2; o[3] = s3;
+	}
+}
+
+__global__ void k_mc_binarize(float *target, uint32_t n, float threshold, uint32_t *positives)
+{
+	const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+	bool p = false;
+	if (r < n) {
+		p = target[r] >= threshold;
+		target[r] = p ? 1.0f : -1.0f;
+	}
+	const uint32_t cnt = (uint32_t)__popcll(__ballot(p));
+	if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(positives, cnt);
+}
+
+__global__ void k_mc_class_link(double *out, uint32_t n)
+{
+	const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+	if (r < n) out[r] = vbcm::Phi(out[r]);
+}
+
 // hyper-prior sums over one chunk of a (w or factor f, group g) segment: mode 0 sum p,
 // mode 1 sum (p - c)^2 with c = the segment's prior mean (draw_w_mu / draw_w_lambda,
 // draw_v_mu / draw_v_lambda: fm_learn_mcmc.h:931-1089)
@@ -329,6 +424,43 @@ hipError_t mc_test_update(const double *e_test, const float *target, uint32_t n,
                           hipStream_t s)
 {
 	k_mc_test_update<256><<<nblocks, 256, 0, s>>>(e_test, target, n, mn, mx, inv_iters, pred_this, pred_sum, out);
+	return hipGetLastError();
+}
+
+hipError_t mc_class_train_update(RowRec *rows, const double *yhat, const float *target, uint32_t n, int mode,
+                                 const double *s_given, uint64_t seed, uint64_t stream, uint64_t row0,
+                                 uint32_t *counters, double *out, uint32_t nblocks, const uint32_t *pos, hipStream_t s)
+{
+	if (mode == VBFM_CLASS_ALS)
+		k_mc_class_train_update<256, VBFM_CLASS_ALS><<<nblocks, 256, 0, s>>>(rows, yhat, target, n, s_given, seed, stream,
+		                                                                     row0, counters, out, pos);
+	else if (mode == VBFM_CLASS_GIVEN)
+		k_mc_class_train_update<256, VBFM_CLASS_GIVEN><<<nblocks, 256, 0, s>>>(rows, yhat, target, n, s_given, seed,
+		                                                                       stream, row0, counters, out, pos);
+	else
+		k_mc_class_train_update<256, VBFM_CLASS_DEVICE><<<nblocks, 256, 0, s>>>(rows, yhat, target, n, s_given, seed,
+		                                                                        stream, row0, counters, out, pos);
+	return hipGetLastError();
+}
+
+hipError_t mc_class_test_update(const double *e_test, const float *target, uint32_t n, double inv_iters,
+                                double *pred_this, double *pred_sum, double *out, uint32_t nblocks, hipStream_t s)
+{
+	k_mc_class_test_update<256><<<nblocks, 256, 0, s>>>(e_test, target, n, inv_iters, pred_this, pred_sum, out);
+	return hipGetLastError();
+}
+
+hipError_t mc_binarize(float *target, uint32_t n, float threshold, uint32_t *positives, hipStream_t s)
+{
+	if (n == 0) return hipSuccess;
+	k_mc_binarize<<<grid_for(n), 256, 0, s>>>(target, n, threshold, positives);
+	return hipGetLastError();
+}
+
+hipError_t mc_class_link(double *out, uint32_t n, hipStream_t s)
+{
+	if (n == 0) return hipSuccess;
+	k_mc_class_link<<<grid_for(n), 256, 0, s>>>(out, n);
 	return hipGetLastError();
 }
 

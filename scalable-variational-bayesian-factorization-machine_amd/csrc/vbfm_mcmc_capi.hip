@@ -1,7 +1,8 @@
 // vbfm_mcmc_capi.hip -- the MCMC / ALS learner of include/vbfm.h (-method mcmc | als).
 //
 // Replaces fm_learn_mcmc / fm_learn_mcmc_simultaneous (src/libfm/src/fm_learn_mcmc.h,
-// src/libfm/src/fm_learn_mcmc_simultaneous.h) for regression without relation blocks. The
+// src/libfm/src/fm_learn_mcmc_simultaneous.h) for regression and binary classification (probit
+// link: the same sweeps on a latent target, class_train_step) without relation blocks. The
 // host keeps draw_all's control flow and every scalar / per-group hyper-prior draw, in the
 // reference's order on the reference's random stream (vbfm_rng.h); the sweeps over the
 // attributes (draw_w, draw_v with their e / q corrections), the q-cache, the prior draws of
@@ -10,6 +11,7 @@
 // same dependency levels as the VB sweep (exact Gauss-Seidel order).
 #include "vbfm_ctx.h"
 #include "vbfm_rng.h"
+#include "vbfm_class_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -50,6 +52,13 @@ struct McState {
 	uint32_t iter = 0;
 	bool caches = false;
 	bool pred_acc = false;                                // v sweeps accumulate the train re-prediction
+	// task c: the last iteration's figures, this rank's first row in the one-rank data set (keys the
+	// device draws), the latent targets drawn from the reference's stream
+	vbfm_mcmc_class_stats cls = {};
+	uint64_t row0 = 0;
+	double *s_d = nullptr;                                // [s_cap]: grows with the train set (class_train_step)
+	size_t s_cap = 0;
+	std::vector<double> s_h;
 	uint32_t hc[HC_N] = {};
 	hipEvent_t ev[MEV_N] = {};
 };
@@ -61,10 +70,16 @@ void mc_free(vbfm_ctx *c)
 	McState *m = c->mc;
 	if (!m) return;
 	dfree(m->hyp_d); dfree(m->z_d); dfree(m->pred_this); dfree(m->pred_sum); dfree(m->red_d); dfree(m->vc); dfree(m->pc);
+	dfree(m->s_d);
 	for (int i = 0; i < MEV_N; i++)
 		if (m->ev[i]) (void)hipEventDestroy(m->ev[i]);
 	delete m;
 	c->mc = nullptr;
+}
+
+void mc_drop_caches(vbfm_ctx *c)
+{
+	if (c->mc) c->mc->caches = false;
 }
 
 void mc_model_scalars(vbfm_ctx *c, double *w0, double *alpha, bool *sample)
@@ -452,6 +467,68 @@ void scan_columns(vbfm_ctx *c)
 	}
 }
 
+// this rank's first row in the one-rank data set: the ranks' row counts, each at its own index,
+// summed over the ranks (shards are contiguous in rank order)
+void class_row_offset(vbfm_ctx *c)
+{
+	McState &m = *c->mc;
+	m.row0 = 0;
+	if (!c->row_comm()) return;
+	const int R = c->net.nranks, me = c->net.rank;
+	std::vector<uint32_t> cnt((size_t)R, 0u);
+	cnt[me] = c->tr.n;
+	DevScratch<uint32_t> d((size_t)R);
+	HIPCHK(hipMemcpyAsync(d, cnt.data(), (size_t)R * 4, hipMemcpyHostToDevice, c->s));
+	allreduce_dev(c, d, (size_t)R, ncclUint32, ncclSum);
+	HIPCHK(d2h(c, cnt.data(), d, (size_t)R * 4));
+	sync(c);
+	for (int r = 0; r < me; r++) m.row0 += cnt[r];
+}
+
+// task c, after the re-prediction left yhat of train in scratch_n (fm_learn_mcmc_simultaneous.h:
+// 189-221): count the correct rows and leave e = yhat - s. Sampling from the reference's stream
+// draws s on the host row by row in ascending row order -- the reference's stream position: after
+// all of draw_all's draws -- and hands it to the kernel. Returns this rank's correct count.
+double class_train_step(vbfm_ctx *c)
+{
+	McState &m = *c->mc;
+	const uint32_t n = c->tr.n;
+	int mode = VBFM_CLASS_ALS;
+	if (m.sample && m.rng == VBFM_RNG_REFERENCE) {
+		mode = VBFM_CLASS_GIVEN;
+		if (c->row_comm())
+			throw std::string("task c with -method mcmc on several ranks needs VBFM_RNG_DEVICE: the reference stream's "
+			                  "position on one rank depends on the other ranks' rejections");
+		m.s_h.resize(n);
+		std::vector<double> yh(n);
+		std::vector<float> y(n);
+		if (n) {
+			HIPCHK(d2h(c, yh.data(), c->scratch_n, (size_t)n * 8));
+			HIPCHK(d2h(c, y.data(), c->tr.target, (size_t)n * 4));
+		}
+		sync(c);
+		for (uint32_t r = 0; r < n; r++) {
+			if (!std::isfinite(yh[r]))
+				throw std::string("task c: non-finite prediction of train row ") + std::to_string(r) +
+				      " (the reference's truncated-normal draw would not return)";
+			m.s_h[r] = y[r] >= 0.0f ? m.stream.left_tgaussian(0.0, yh[r], 1.0) : m.stream.right_tgaussian(0.0, yh[r], 1.0);
+		}
+		if (n > m.s_cap) {   // a larger train set than the buffer was made for
+			dfree(m.s_d);
+			m.s_cap = 0;
+			m.s_d = dalloc<double>(n);
+			m.s_cap = n;
+		}
+		if (n) HIPCHK(hipMemcpyAsync(m.s_d, m.s_h.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->s));
+	} else if (m.sample) {
+		mode = VBFM_CLASS_DEVICE;
+	}
+	HIPCHK(vbk::mc_class_train_update(c->rows, c->scratch_n, c->tr.target, n, mode, m.s_d, m.seed,
+	                                  vbcm::CLASS_STREAM | (uint64_t)m.iter, m.row0, c->counters, c->red_d, c->RED_BLOCKS,
+	                                  c->store.rows_lorder ? c->store.lpos0 : nullptr, c->s));
+	return finish_sum(c, c->RED_BLOCKS);
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -580,6 +657,12 @@ int vbfm_mcmc_init_caches(vbfm_ctx *c)
 		HIPCHK(vbk::mc_train_update(c->rows, c->scratch_n, c->tr.target, c->tr.n, c->min_target, c->max_target,
 		                            m.red_d, MC_RED_BLOCKS, c->store.rows_lorder ? c->store.lpos0 : nullptr, c->s));
 		sync(c);
+		if (c->task == VBFM_TASK_CLASSIFICATION) {
+			if (m.sample && m.rng == VBFM_RNG_REFERENCE && c->row_comm())
+				throw std::string("task c with -method mcmc on several ranks needs VBFM_RNG_DEVICE: the reference "
+				                  "stream's position on one rank depends on the other ranks' rejections");
+			class_row_offset(c);
+		}
 		m.iter = 0;
 		m.caches = true;
 		c->q_ready[0] = c->q_ready[1] = -1;
@@ -622,11 +705,17 @@ int vbfm_mcmc_iterate(vbfm_ctx *c, vbfm_mcmc_stats *o)
 		// re-predict and evaluate (fm_learn_mcmc_simultaneous.h:134-175, 238-245)
 		mc_predict(c, !fused);
 		const double mn = c->min_target, mx = c->max_target;
-		HIPCHK(vbk::mc_test_update(c->e_test, c->te.target, c->te.n, mn, mx, 1.0 / (m.iter + 1), m.pred_this,
-		                           m.pred_sum, m.red_d, MC_RED_BLOCKS, c->s));
+		const bool cls = c->task == VBFM_TASK_CLASSIFICATION;
+		if (cls)
+			HIPCHK(vbk::mc_class_test_update(c->e_test, c->te.target, c->te.n, 1.0 / (m.iter + 1), m.pred_this, m.pred_sum,
+			                                 m.red_d, MC_RED_BLOCKS, c->s));
+		else
+			HIPCHK(vbk::mc_test_update(c->e_test, c->te.target, c->te.n, mn, mx, 1.0 / (m.iter + 1), m.pred_this,
+			                           m.pred_sum, m.red_d, MC_RED_BLOCKS, c->s));
 		HIPCHK(d2h(c, m.red_h.data(), m.red_d, 4 * MC_RED_BLOCKS * 8));
 		sync(c);
-		double tm[5] = {0, 0, 0, 0, 0};
+		double tm[7] = {0, 0, 0, 0, 0, 0, 0};
+		uint32_t h[CNT_N];
 		for (uint32_t b = 0; b < MC_RED_BLOCKS; b++)
 			for (int q = 0; q < 4; q++) tm[q] += m.red_h[4 * b + q];
 		if (fused) {   // yhat of train from the sweeps' accumulators + the last factor and w
@@ -635,23 +724,43 @@ int vbfm_mcmc_iterate(vbfm_ctx *c, vbfm_mcmc_stats *o)
 			                          c->rows, c->store.rows_lorder ? c->store.lpos0 : nullptr, c->tr.n, c->D, m.pc, c->scratch_n,
 			                          c->s));
 		}
-		HIPCHK(vbk::mc_train_update(c->rows, c->scratch_n, c->tr.target, c->tr.n, mn, mx, c->red_d, c->RED_BLOCKS,
-		                            c->store.rows_lorder ? c->store.lpos0 : nullptr, c->s));
-		tm[4] = finish_sum(c, c->RED_BLOCKS);
-		allreduce_host(c, tm, 5);
+		if (cls) {
+			tm[4] = class_train_step(c);
+			// the rows the step could not draw join the same exchange (the stream is idle: finish_sum)
+			HIPCHK(hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost));
+			tm[5] = (double)h[CNT_CLASS_NONFINITE];
+			tm[6] = (double)h[CNT_CLASS_CAPPED];
+		} else {
+			HIPCHK(vbk::mc_train_update(c->rows, c->scratch_n, c->tr.target, c->tr.n, mn, mx, c->red_d, c->RED_BLOCKS,
+			                            c->store.rows_lorder ? c->store.lpos0 : nullptr, c->s));
+			tm[4] = finish_sum(c, c->RED_BLOCKS);
+		}
+		allreduce_host(c, tm, cls ? 7 : 5);
 		HIPCHK(hipEventRecord(m.ev[MEV_PRED], c->s));
 		sync(c);
 		m.iter++;
 		const double nt = (double)c->test_n_global;
-		st.rmse_this = std::sqrt(tm[0] / nt);
-		st.mae_this = tm[1] / nt;
-		st.rmse_all = std::sqrt(tm[2] / nt);
-		st.mae_all = tm[3] / nt;
-		st.train_rmse = std::sqrt(tm[4] / (double)c->n_global);
+		if (cls) {   // the sums are (correct_this, ll_this, correct_all, ll_all) and the correct train rows
+			m.cls.n_test_correct_this = (uint64_t)tm[0];
+			m.cls.n_test_correct_all = (uint64_t)tm[2];
+			m.cls.n_train_correct = (uint64_t)tm[4];
+			m.cls.acc_this = tm[0] / nt;
+			m.cls.ll_this = tm[1] / nt;
+			m.cls.acc_all = tm[2] / nt;
+			m.cls.ll_all = tm[3] / nt;
+			m.cls.acc_train = tm[4] / (double)c->n_global;
+			m.cls.nonfinite_rows = (uint32_t)tm[5];
+			m.cls.capped_rows = (uint32_t)tm[6];
+		} else {
+			st.rmse_this = std::sqrt(tm[0] / nt);
+			st.mae_this = tm[1] / nt;
+			st.rmse_all = std::sqrt(tm[2] / nt);
+			st.mae_all = tm[3] / nt;
+			st.train_rmse = std::sqrt(tm[4] / (double)c->n_global);
+		}
 		st.alpha = m.alpha;
 		st.w0 = m.w0;
-		uint32_t h[CNT_N];
-		HIPCHK(hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost));
+		if (!cls) HIPCHK(hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost));
 		st.nan_w = h[CNT_NAN_MU_W]; st.inf_w = h[CNT_INF_MU_W];
 		st.nan_v = h[CNT_NAN_MU_V]; st.inf_v = h[CNT_INF_MU_V];
 		st.rng_skipped = h[CNT_RNG_SKIP];
@@ -697,13 +806,26 @@ int vbfm_mcmc_get_test_pred(vbfm_ctx *c, int32_t num_iter, double *pred)
 		const uint32_t n = c->te.n;
 		std::vector<double> h(n);
 		if (n) HIPCHK(hipMemcpy(h.data(), m.sample ? m.pred_sum : m.pred_this, (size_t)n * 8, hipMemcpyDeviceToHost));
-		const double mn = c->min_target, mx = c->max_target;
+		// task c: probabilities, clipped to [0, 1] (fm_learn_mcmc.h:355-379)
+		const bool cls = c->task == VBFM_TASK_CLASSIFICATION;
+		const double mn = cls ? 0.0 : c->min_target, mx = cls ? 1.0 : c->max_target;
 		for (uint32_t i = 0; i < n; i++) {
 			double p = m.sample ? h[i] / num_iter : h[i];
 			p = std::min(mx, p);
 			p = std::max(mn, p);
 			pred[i] = p;
 		}
+	});
+}
+
+int vbfm_mcmc_class_info(vbfm_ctx *c, vbfm_mcmc_class_stats *o)
+{
+	if (!c || !o) return fail(c, "null argument");
+	return guarded(c, [&] {
+		McState &m = mc(c);
+		if (c->task != VBFM_TASK_CLASSIFICATION)
+			throw std::string("vbfm_mcmc_class_info: a regression context (vbfm_config::task)");
+		*o = m.cls;
 	});
 }
 
@@ -739,7 +861,7 @@ int vbfm_mcmc_factor_sweep(vbfm_ctx *c, double *ms_device)
 namespace vbi {
 
 namespace {
-constexpr size_t MC_RNG_WORDS = 8 + 32;   // {sample, multilevel, rng, seed, iter, 0, 0, 0}, window + pad
+constexpr size_t MC_RNG_WORDS = 8 + 32;   // {sample, multilevel, rng, seed, iter, task, 0, 0}, window + pad
 }
 
 uint64_t mc_state_payload(vbfm_ctx *c)
@@ -755,6 +877,7 @@ void mc_state_write(vbfm_ctx *c, CkptFile &f)
 	if (!m.caches || !m.pred_sum) throw std::string("vbfm_save_state: vbfm_mcmc_init_caches first");
 	uint32_t w[MC_RNG_WORDS] = {};
 	w[0] = (uint32_t)m.sample; w[1] = (uint32_t)m.multilevel; w[2] = (uint32_t)m.rng; w[3] = m.seed; w[4] = m.iter;
+	w[5] = (uint32_t)c->task;   // 0 in files written before task c existed: regression
 	m.stream.chrono_state(w + 8);
 	f.write(w, sizeof(w));
 	dev_to_file(c, f, c->ms_w, (size_t)c->D * sizeof(double2));
@@ -778,12 +901,15 @@ void mc_state_read(vbfm_ctx *c, CkptFile &f)
 	if (w[0] != (uint32_t)m.sample || w[1] != (uint32_t)m.multilevel)
 		throw std::string("checkpoint of another method (mcmc vs als): resume with the same -method");
 	if (w[2] != (uint32_t)m.rng) throw std::string("checkpoint of another RNG mode (VBFM_RNG_REFERENCE / _DEVICE)");
+	if (w[5] != (uint32_t)c->task)
+		throw std::string("checkpoint of another task (regression vs classification): resume with the same -task");
 	if (c->te.n && !c->e_test) throw std::string("no test data set (vbfm_set_test)");
 	if (!m.pred_sum) require_test(c);
 	if (m.col_nonempty.empty()) scan_columns(c);
 	m.seed = w[3];
 	m.iter = w[4];
 	m.stream.set_chrono_state(w + 8);
+	if (c->task == VBFM_TASK_CLASSIFICATION) class_row_offset(c);
 	file_to_dev(c, f, c->ms_w, (size_t)c->D * sizeof(double2));
 	file_to_dev(c, f, c->ms_v, (size_t)c->k * c->D * sizeof(double2));
 	f.read(m.w_mu.data(), G_(c) * 8);

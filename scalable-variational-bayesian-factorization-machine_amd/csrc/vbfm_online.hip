@@ -1188,6 +1188,7 @@ int vbfm_online_init(vbfm_ctx *c, const vbfm_online_config *cfg)
 	if (!c || !cfg) return fail(c, "vbfm_online_init: null argument");
 	return guarded(c, [&] {
 		if (c->mc) throw std::string("an MCMC / ALS context cannot run the online VB learner");
+		require_regression(c);
 		if (c->multi() || c->fs.mode == VBFM_SHARD_FEATURES)
 			throw std::string("the online VB learner runs on one GPU (no communicator, no feature shards)");
 		if (!c->rows) throw std::string("no train data set (vbfm_set_train)");

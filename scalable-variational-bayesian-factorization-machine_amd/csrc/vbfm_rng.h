@@ -85,6 +85,35 @@ public:
 		}
 	}
 	double gamma(double a, double b) { return gamma(a) / b; }   // random.h:150-152 form
+	double exp() { return -std::log(1 - uniform()); }          // random.h:178-180
+	// standard normal truncated to [left, inf) (random.h:72-102): naive rejection for left <= 0,
+	// Robert's translated exponential otherwise. As the reference it never returns for a NaN left:
+	// callers pass finite values only
+	double left_tgaussian(double left)
+	{
+		if (left <= 0.0) {
+			double result;
+			do { result = gaussian(); } while (result < left);
+			return result;
+		}
+		const double alpha_star = 0.5 * (left + std::sqrt(left * left + 4.0));
+		for (;;) {
+			const double z = exp() / alpha_star + left;
+			double d = z - alpha_star;
+			d = std::exp(-(d * d) / 2);
+			const double u = uniform();
+			if (u < d) return z;
+		}
+	}
+	double left_tgaussian(double left, double mean, double stdev)    // random.h:104-106
+	{
+		return mean + stdev * left_tgaussian((left - mean) / stdev);
+	}
+	double right_tgaussian(double right) { return -left_tgaussian(-right); }   // random.h:108-110
+	double right_tgaussian(double right, double mean, double stdev)   // random.h:112-114
+	{
+		return mean + stdev * right_tgaussian((right - mean) / stdev);
+	}
 	// the generator as the recurrence y_n = y_{n-31} + y_{n-3} (mod 2^32), output y_n >> 1:
 	// st[i] = y_{n-31+i}, the 31 sums preceding the next output
 	void chrono_state(uint32_t st[31]) const

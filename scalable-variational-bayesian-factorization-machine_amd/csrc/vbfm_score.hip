@@ -331,6 +331,7 @@ struct vbfm_model {
 	std::string err;
 	int dev = 0;
 	vbfm_model_info info = {};
+	int32_t task = VBFM_TASK_REGRESSION;          // task c: clip = 1 scores are Phi(yhat), clip = 0 the raw yhat
 	double *mw = nullptr, *mv = nullptr;          // means: w [D], v [j*k + f] (ALS / MCMC: the values)
 	double2 *ms_w = nullptr, *ms_v = nullptr;     // VB kinds: the {mu, sigma} pairs
 	hipStream_t s = nullptr, s_copy = nullptr;    // kernels and results; the chunks' copies to the device
@@ -434,6 +435,7 @@ vbfm_model *snapshot(vbfm_ctx *c)
 		in.k0 = c->k0; in.k1 = c->k1; in.num_factor = c->k;
 		in.num_attribute = c->D;
 		in.min_target = c->min_target; in.max_target = c->max_target;
+		m->task = c->task;
 		if (c->mc) {
 			bool sample = false;
 			mc_model_scalars(c, &in.w0_or_mu0, &in.alpha, &sample);
@@ -475,10 +477,17 @@ ScoreArgs score_args(const vbfm_model *m, const vbfm_score_opts &o)
 	a.k = m->info.num_factor; a.k1 = m->info.k1; a.k0 = m->info.k0;
 	a.D = m->info.num_attribute;
 	a.mu0 = m->info.w0_or_mu0; a.s0d = m->info.sigma_0_dash;
-	a.clip = o.clip != 0;
+	a.clip = o.clip != 0 && m->task == VBFM_TASK_REGRESSION;   // task c: the link follows the kernel (score_link)
 	a.mn = m->info.min_target; a.mx = m->info.max_target;
 	a.flags = m->flags;
 	return a;
+}
+
+// task c: the probability Phi(yhat) "as pred_this is" (fm_learn_mcmc_simultaneous.h:178-182) in place
+// of the clip, over the n means a score kernel just left on m->s
+void score_link(const vbfm_model *m, const vbfm_score_opts &o, double *mean, uint32_t n)
+{
+	if (m->task == VBFM_TASK_CLASSIFICATION && o.clip) HIPCHK(vbk::mc_class_link(mean, n, m->s));
 }
 
 // the context's rule (blocked_predict): the reference's order while nnz * k <= 5e7
@@ -546,6 +555,13 @@ int vbfm_model_info_get(const vbfm_model *m, vbfm_model_info *out)
 	return 0;
 }
 
+int vbfm_model_task(const vbfm_model *m, int32_t *task)
+{
+	if (!m || !task) return mfail(nullptr, "vbfm_model_task: null argument");
+	*task = m->task;
+	return 0;
+}
+
 void vbfm_model_destroy(vbfm_model *m) { model_free(m); }
 
 int vbfm_model_from_ctx(vbfm_model **out, vbfm_ctx *c)
@@ -568,7 +584,7 @@ int vbfm_model_save(vbfm_ctx *c, const char *path, uint32_t iter)
 			std::vector<double> w(D * per), v(kd * per);
 			if (D) HIPCHK(hipMemcpy(w.data(), vb ? (const void *)m->ms_w : m->mw, D * per * 8, hipMemcpyDeviceToHost));
 			if (kd) HIPCHK(hipMemcpy(v.data(), vb ? (const void *)m->ms_v : m->mv, kd * per * 8, hipMemcpyDeviceToHost));
-			if (vbfm_host_model_write_raw(path, &m->info, w.data(), v.data()) != 0) throw std::string(vbfm_host_last_error());
+			if (vbfm_host_model_write_raw(path, &m->info, m->task, w.data(), v.data()) != 0) throw std::string(vbfm_host_last_error());
 		} catch (...) {
 			model_free(m);
 			throw;
@@ -597,13 +613,15 @@ int vbfm_model_load(vbfm_model **out, const char *path, int32_t device)
 		*v = t.v.data();
 		return 0;
 	};
-	if (vbfm_host_model_read_raw(path, &info, alloc, &tabs) != 0) return -1;
+	int32_t task = VBFM_TASK_REGRESSION;
+	if (vbfm_host_model_read_raw(path, &info, &task, alloc, &tabs) != 0) return -1;
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return mfail(nullptr, "no HIP device available");
 	if (device < 0 || device >= ndev) return mfail(nullptr, "device ordinal out of range");
 	vbfm_model *m = new vbfm_model();
 	m->dev = device;
 	m->info = info;
+	m->task = task;
 	const int rc = mguarded(nullptr, [&] {
 		model_alloc(m);
 		const size_t D = info.num_attribute, kd = D * (size_t)info.num_factor;
@@ -705,6 +723,7 @@ int vbfm_score(vbfm_model *m, const vbfm_csr *rows, const vbfm_score_opts *opts,
 			a.row0 = r0;
 			HIPCHK(hipEventRecord(sl.ev[SEV_K0], m->s));
 			HIPCHK(launch_score(a, group, var != nullptr, m->s));
+			score_link(m, o, a.mean, nr);
 			HIPCHK(hipEventRecord(sl.ev[SEV_K1], m->s));
 			HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, (size_t)nr * (var ? 2 : 1) * 8, hipMemcpyDeviceToHost, m->s));
 			HIPCHK(hipEventRecord(sl.ev[SEV_DONE], m->s));
@@ -745,6 +764,7 @@ int vbfm_score_device(vbfm_model *m, vbfm_ctx *c, int32_t which, const vbfm_scor
 		vbfm_model::Slot &sl = m->slot[0];
 		HIPCHK(hipEventRecord(sl.ev[SEV_K0], m->s));
 		HIPCHK(launch_score(a, group_order(m, o, d.nnz), var != nullptr, m->s));
+		score_link(m, o, a.mean, d.n);
 		HIPCHK(hipEventRecord(sl.ev[SEV_K1], m->s));
 		const ScoreFlags f = flags_read(m);
 		if (f.first != ~0ull && !o.unknown_ids) throw unknown_msg(m, f.first >> 32, (uint32_t)f.first);

@@ -155,4 +155,24 @@ int vbfm_synth_multihot(vbfm_ctx *c, int32_t which, uint32_t n, uint32_t D, uint
 	});
 }
 
+int vbfm_synth_binarize(vbfm_ctx *c, int32_t which, float threshold, uint64_t *positives)
+{
+	if (!c) return fail(nullptr, "null context");
+	return guarded(c, [&] {
+		if (which != 0 && which != 1) throw std::string("which must be 0 (train) or 1 (test)");
+		DevData &d = which ? c->te : c->tr;
+		if (!d.target) throw std::string("vbfm_synth_binarize: no such data set yet");
+		DevScratch<uint32_t> cnt(1);
+		HIPCHK(hipMemsetAsync(cnt, 0, 4, c->s));
+		HIPCHK(vbk::mc_binarize(d.target, d.n, threshold, cnt, c->s));
+		uint32_t h = 0;
+		HIPCHK(d2h(c, &h, cnt, 4));
+		sync(c);
+		d.min_target = -1.0f;
+		d.max_target = 1.0f;
+		if (which == 0) mc_drop_caches(c);   // e = yhat - target of the old targets is stale
+		if (positives) *positives = h;
+	});
+}
+
 }  // extern "C"

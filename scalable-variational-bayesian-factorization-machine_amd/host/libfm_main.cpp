@@ -8,7 +8,8 @@
 //   * -seed is honoured (the reference seeds with time(NULL) and ignores it, libfm.cpp:123);
 //   * -out writes the clipped test predictions of the last iteration (the reference's VB
 //     predict() body is commented out and leaves the vector uninitialised, fm_learn_vb.h:321);
-//   * -method sgd/sgda/... and -task c are rejected with an error instead of running
+//   * -method sgd/sgda/... are rejected with an error instead of running; -task c (binary
+//     classification, probit link) runs with -method mcmc | als and is refused for vb / vb_online
 //     other learners; -relation is not supported;
 //   * extra flags: -device (HIP ordinal), -vfile 0 (skip writing v_file.txt), -save_state /
 //     -resume (checkpoints), -parity_log (17-digit JSON lines per iteration), and the multi-GPU launch: -devices N | o0,o1,..., -shard
@@ -56,6 +57,9 @@
 #pragma weak vbfm_model_last_error
 #pragma weak vbfm_model_destroy
 #pragma weak vbfm_score
+// ... and so are the entry points of -task c
+#pragma weak vbfm_mcmc_class_info
+#pragma weak vbfm_model_file_task
 
 namespace {
 
@@ -263,6 +267,14 @@ void load(const std::string &fn, Data &d, const char *what)
 	          << "\tmin_target=" << d.h.min_target << "\tmax_target=" << d.h.max_target << std::endl;
 }
 
+// -task c, libfm.cpp:339-340: the two classes are target <= 0 and target > 0; the set's range follows
+static void map_class_targets(vbfm_host_data &h)
+{
+	for (uint32_t i = 0; i < h.num_rows; i++) h.target[i] = h.target[i] <= 0.0f ? -1.0f : 1.0f;
+	h.min_target = -1.0f;
+	h.max_target = 1.0f;
+}
+
 static bool have_scorer()
 {
 	return vbfm_model_save && vbfm_model_load && vbfm_model_info_get && vbfm_model_last_error && vbfm_model_destroy &&
@@ -432,13 +444,16 @@ struct McmcRun {
 	int k0, k1, k;
 	bool vfile;
 	std::string rlog_file, out_file, parity_file, save_file, resume_file, model_file;
+	int32_t task;   // VBFM_TASK_*
 };
 
 static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
 {
 	vbfm_ctx *ctx = nullptr;
 	try {
-		vbfm_config cfg{r.k0, r.k1, r.k, r.D, r.G, r.groups, train.h.min_target, train.h.max_target, rk.device, 0};
+		const bool cls = r.task == VBFM_TASK_CLASSIFICATION;
+		if (cls && !vbfm_mcmc_class_info) throw std::string("this build has no -task c");
+		vbfm_config cfg{r.k0, r.k1, r.k, r.D, r.G, r.groups, train.h.min_target, train.h.max_target, rk.device, r.task};
 		check(vbfm_create(&ctx, &cfg), nullptr);
 		join(ctx, rk);
 		{
@@ -446,7 +461,13 @@ static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
 			check(vbfm_set_train(ctx, &tr.csc), ctx);
 			check(vbfm_set_test(ctx, &te.csc), ctx);
 		}
-		vbfm_mcmc_config mc{r.sample, r.sample, VBFM_RNG_REFERENCE, r.seed, r.init_stdev,
+		// -task c -method mcmc on several ranks: the latent targets cannot follow the reference's
+		// stream (a rank's position in it would depend on the other ranks' rejections), so the run
+		// takes the device generator for every per-attribute and per-row draw
+		const int32_t rng = cls && r.sample && rk.multi() ? VBFM_RNG_DEVICE : VBFM_RNG_REFERENCE;
+		if (rng == VBFM_RNG_DEVICE && rk.lead())
+			std::cout << "-task c -method mcmc on " << rk.nranks << " ranks: draws from the device generator" << std::endl;
+		vbfm_mcmc_config mc{r.sample, r.sample, rng, r.seed, r.init_stdev,
 		                    r.reg.empty() ? nullptr : r.reg.data(), (int32_t)r.reg.size()};
 		check(vbfm_mcmc_init(ctx, &mc), ctx);
 		const size_t kd = (size_t)r.k * r.D, gk = (size_t)r.G * r.k;
@@ -468,9 +489,16 @@ static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
 			if (!rlog_out->is_open()) throw std::string("Unable to open file " + r.rlog_file);
 			std::cout << "logging to " << r.rlog_file << std::endl;
 			rlog = new RLog(rlog_out);
-			for (const char *f : {"rmse", "mae", "time_pred", "time_learn", "time_learn2", "time_learn4", "alpha",
-			                      "rmse_mcmc_this", "rmse_mcmc_all", "rmse_mcmc_all_but5"})
-				rlog->add(f);
+			if (cls) {   // fm_learn.h:85-86, fm_learn_mcmc.h:1129-1135
+				for (const char *f : {"accuracy", "time_pred", "time_learn", "time_learn2", "time_learn4", "alpha",
+				                      "acc_mcmc_this", "acc_mcmc_all", "acc_mcmc_all_but5", "ll_mcmc_this", "ll_mcmc_all",
+				                      "ll_mcmc_all_but5"})
+					rlog->add(f);
+			} else {
+				for (const char *f : {"rmse", "mae", "time_pred", "time_learn", "time_learn2", "time_learn4", "alpha",
+				                      "rmse_mcmc_this", "rmse_mcmc_all", "rmse_mcmc_all_but5"})
+					rlog->add(f);
+			}
 			for (uint32_t g = 0; g < r.G; g++) {
 				std::ostringstream ss;
 				ss << "wmu[" << g << "]"; rlog->add(ss.str()); ss.str("");
@@ -504,6 +532,9 @@ static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
 			const double t_wall = (double)time(NULL);
 			vbfm_mcmc_stats st;
 			check(vbfm_mcmc_iterate(ctx, &st), ctx);
+			vbfm_mcmc_class_stats cs;
+			memset(&cs, 0, sizeof(cs));
+			if (cls) check(vbfm_mcmc_class_info(ctx, &cs), ctx);
 			// :104-127
 			const struct { const char *name; uint32_t nan, inf; } rep[] = {
 				{"alpha", st.nan_alpha, st.inf_alpha}, {"w0", st.nan_w0, st.inf_w0}, {"w", st.nan_w, st.inf_w},
@@ -529,14 +560,32 @@ static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
 				rlog->log("time_learn", usertime() - t_user);
 				rlog->log("time_learn2", (double)(clock() - t_clock) / CLOCKS_PER_SEC);
 				rlog->log("time_learn4", (double)time(NULL) - t_wall);
-				rlog->log("rmse", st.rmse_all);
-				rlog->log("mae", st.mae_all);
-				rlog->log("rmse_mcmc_this", st.rmse_this);
-				rlog->log("rmse_mcmc_all", st.rmse_all);
+				if (cls) {   // :280-286; the three columns the reference leaves uninitialised are written as
+					// 0, ll_mcmc_all (uninitialised there too) as the computed value
+					rlog->log("accuracy", cs.acc_all);
+					rlog->log("acc_mcmc_this", cs.acc_this);
+					rlog->log("acc_mcmc_all", cs.acc_all);
+					rlog->log("acc_mcmc_all_but5", 0.0);
+					rlog->log("ll_mcmc_this", cs.ll_this);
+					rlog->log("ll_mcmc_all", cs.ll_all);
+					rlog->log("ll_mcmc_all_but5", 0.0);
+				} else {
+					rlog->log("rmse", st.rmse_all);
+					rlog->log("mae", st.mae_all);
+					rlog->log("rmse_mcmc_this", st.rmse_this);
+					rlog->log("rmse_mcmc_all", st.rmse_all);
+				}
 				rlog->newline();
 			}
-			std::cout << "#Iter=" << std::setw(3) << it << "\tTrain=" << st.train_rmse << "\tTest=" << st.rmse_all
-			          << std::endl;
+			if (cls) {   // :275 without its MAP@5 field (that reads a fixed side file)
+				std::cout << "#Iter=" << std::setw(3) << it << "\tTrain=" << cs.acc_train << "\tTest=" << cs.acc_all << std::endl;
+				if (cs.nonfinite_rows || cs.capped_rows)
+					std::cout << "#non-finite train predictions:\t" << cs.nonfinite_rows << "\t#draws at the attempt cap:\t"
+					          << cs.capped_rows << std::endl;
+			} else {
+				std::cout << "#Iter=" << std::setw(3) << it << "\tTrain=" << st.train_rmse << "\tTest=" << st.rmse_all
+				          << std::endl;
+			}
 			if (plog.on()) {
 				plog.begin(r.sample ? "mcmc" : "als", it);
 				const double vals[] = {st.train_rmse, st.rmse_all, st.mae_all, st.rmse_this, st.mae_this, st.alpha, st.w0,
@@ -546,13 +595,21 @@ static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
 				for (size_t i = 0; i < sizeof(vals) / sizeof(vals[0]); i++) plog.num(keys[i], vals[i]);
 				plog.num("levels", st.num_levels);
 				plog.num("rng_skipped", st.rng_skipped);
+				if (cls) {
+					const double cv[] = {cs.acc_train, cs.acc_this, cs.acc_all, cs.ll_this, cs.ll_all,
+					                     (double)cs.n_train_correct, (double)cs.n_test_correct_this,
+					                     (double)cs.n_test_correct_all, (double)cs.nonfinite_rows, (double)cs.capped_rows};
+					const char *ck[] = {"acc_train", "acc_this", "acc_all", "ll_this", "ll_all", "n_train_correct",
+					                    "n_test_correct_this", "n_test_correct_all", "nonfinite_rows", "capped_rows"};
+					for (size_t i = 0; i < sizeof(cv) / sizeof(cv[0]); i++) plog.num(ck[i], cv[i]);
+				}
 				plog.sweep(st.ms_v, r.k, train.h.nnz, train.h.num_rows, train.h.num_feature, rk.nranks, true);
 				plog.exchange(ctx);
 				plog.end();
 			}
 			if (rk.lead()) {
 				std::ofstream fr(f_rmse.c_str(), std::ios_base::app);
-				fr << st.rmse_all << "\n";
+				fr << (cls ? cs.acc_all : st.rmse_all) << "\n";
 			}
 		}
 		if (!r.save_file.empty())
@@ -898,6 +955,7 @@ struct ScoreRun {
 	std::string model_file, test_file, out_file, var_file;
 	int32_t device;
 	bool skip_unknown;
+	int32_t task;   // the file's
 };
 
 static void run_score(const ScoreRun &r)
@@ -910,10 +968,12 @@ static void run_score(const ScoreRun &r)
 	try {
 		vbfm_model_info info;
 		if (vbfm_model_info_get(m, &info) != 0) throw std::string(vbfm_last_error(nullptr));
+		const bool cls = r.task == VBFM_TASK_CLASSIFICATION;
+		if (cls) map_class_targets(test.h);   // as training maps them, so a 0 label is the negative class
 		static const char *const kinds[4] = {"vb", "vb_online", "als", "mcmc (last draw)"};
 		std::cout << "model " << r.model_file << ": " << kinds[info.kind] << ", dim " << info.k0 << "," << info.k1 << ","
 		          << info.num_factor << ", num_attribute=" << info.num_attribute << ", after " << info.iter
-		          << " iterations" << std::endl;
+		          << " iterations" << (cls ? ", task c" : "") << std::endl;
 		const uint32_t n = test.h.num_rows;
 		std::vector<double> mean(n), var(r.var_file.empty() ? 0 : n);
 		const vbfm_csr rows{n, test.h.nnz, test.h.row_ptr, test.h.row_ent};
@@ -928,7 +988,12 @@ static void run_score(const ScoreRun &r)
 			s2 += err * err;
 			s1 += std::fabs(err);
 		}
-		if (n) std::cout << "Test RMSE=" << std::sqrt(s2 / n) << "\tMAE=" << s1 / n << std::endl;
+		if (n && cls) {   // the mean is the probability Phi(yhat): accuracy as _evaluate_class counts it
+			uint32_t ok = 0;
+			for (uint32_t i = 0; i < n; i++)
+				ok += (mean[i] >= 0.5 && test.h.target[i] > 0.0f) || (mean[i] < 0.5 && test.h.target[i] < 0.0f);
+			std::cout << "Test accuracy=" << (double)ok / n << std::endl;
+		} else if (n) std::cout << "Test RMSE=" << std::sqrt(s2 / n) << "\tMAE=" << s1 / n << std::endl;
 		{
 			std::ofstream out(r.out_file.c_str());
 			if (!out.is_open()) throw std::string("Unable to open file " + r.out_file);
@@ -1137,12 +1202,24 @@ int main(int argc, char **argv)
 		if (cmd.has(p_loadm)) {   // predict only: the model decides method and dimensions
 			for (const std::string &p : {p_method, p_dim, p_iter})
 				if (cmd.has(p)) throw std::string("-load_model scores with a trained model: -" + p + " does not apply");
-			if (cmd.get(p_task) != "r") throw std::string("unknown task");
 			if (!cmd.has(p_test) || !cmd.has(p_out)) throw std::string("-load_model needs -test and -out");
+			// the task is the file's; a -task that contradicts it is refused
+			int32_t ftask = VBFM_TASK_REGRESSION;
+			if (!have_scorer()) throw std::string("this build has no scorer");
+			if (vbfm_model_file_task) {
+				if (vbfm_model_file_task(cmd.get(p_loadm).c_str(), &ftask) != 0) throw std::string(vbfm_last_error(nullptr));
+			}
+			if (cmd.has(p_task)) {
+				const std::string t = cmd.get(p_task);
+				if (t != "r" && t != "c") throw std::string("unknown task");
+				if ((t == "c") != (ftask == VBFM_TASK_CLASSIFICATION))
+					throw std::string("-task " + t + " contradicts the model file, which is of task " +
+					                  (ftask == VBFM_TASK_CLASSIFICATION ? "c" : "r"));
+			}
 			const std::string unk = cmd.get(p_unknown, "refuse");
 			if (unk != "refuse" && unk != "skip") throw std::string("-unknown_ids: refuse or skip");
 			run_score(ScoreRun{cmd.get(p_loadm), cmd.get(p_test), cmd.get(p_out), cmd.get(p_outvar),
-			                   (int32_t)cmd.geti(p_dev, 0), unk == "skip"});
+			                   (int32_t)cmd.geti(p_dev, 0), unk == "skip", ftask});
 			return 0;
 		}
 		if (cmd.has(p_outvar) || cmd.has(p_unknown)) throw std::string("-out_var and -unknown_ids belong to -load_model");
@@ -1151,7 +1228,11 @@ int main(int argc, char **argv)
 		const std::string method = cmd.get(p_method, "mcmc");
 		if (method != "vb" && method != "vb_online" && method != "mcmc" && method != "als")
 			throw std::string("method " + method + " is not provided by this build (use -method vb, vb_online, mcmc or als)");
-		if (cmd.get(p_task) != "r") throw std::string("unknown task");   // regression only
+		const std::string task_s = cmd.get(p_task);
+		if (task_s != "r" && task_s != "c") throw std::string("unknown task");
+		const int32_t task = task_s == "c" ? VBFM_TASK_CLASSIFICATION : VBFM_TASK_REGRESSION;
+		if (task == VBFM_TASK_CLASSIFICATION && (method == "vb" || method == "vb_online"))   // the library's message
+			throw std::string("task c (binary classification) is provided by the mcmc and als learners, not by vb / vb_online");
 		if (!cmd.list(p_rel).empty()) throw std::string("-relation is not supported by this build");
 
 		// the ranks: -devices N | o0,o1,..., -shard, -transport (checked before the data load)
@@ -1190,6 +1271,9 @@ int main(int argc, char **argv)
 		load(cmd.get(p_train), train, "train");
 		load(cmd.get(p_test), test, "test");
 		g_load_s = wall_now() - t_load;
+		if (task == VBFM_TASK_CLASSIFICATION)   // libfm.cpp:339-340: the two classes are target <= 0 and target > 0
+			for (Data *d : {&train, &test})
+				map_class_targets(d->h);
 		if (cmd.geti(p_verb, 0) > 0) std::cout << "seed=" << seed << std::endl;
 		if (proto.row_shards() && train.h.num_rows < (uint32_t)proto.nranks)
 			throw std::string("-devices: fewer train rows than ranks");
@@ -1235,7 +1319,7 @@ int main(int argc, char **argv)
 		for (const std::string &r : cmd.list(p_reg)) reg.push_back(atof(r.c_str()));
 		job.mc = McmcRun{method == "mcmc", seed, init_stdev, num_iter, reg, gp, G, D, k0, k1, k, vfile, rlog, out, plog,
 		                 cmd.has(p_save) ? cmd.get(p_save) : std::string(), cmd.has(p_resume) ? cmd.get(p_resume) : std::string(),
-		                 cmd.get(p_savem)};
+		                 cmd.get(p_savem), task};
 		job.vb = VbRun{seed, init_stdev, num_iter, gp, G, D, k0, k1, k, vfile, rlog, out,
 		               cmd.has(p_save) ? cmd.get(p_save) : std::string(), cmd.has(p_resume) ? cmd.get(p_resume) : std::string(),
 		               plog, cmd.get(p_savem)};

@@ -134,6 +134,18 @@ class McmcStats(C.Structure):
 ONLINE_INIT_HOST, ONLINE_INIT_REPLAY = 0, 1
 
 
+class McmcClassStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("acc_train", "acc_this", "acc_all", "ll_this", "ll_all")] + \
+               [(n, C.c_uint64) for n in ("n_train_correct", "n_test_correct_this", "n_test_correct_all")] + \
+               [("nonfinite_rows", C.c_uint32), ("capped_rows", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+TASKS = {"r": 0, "c": 1}
+
+
 class OnlineConfig(C.Structure):
     _fields_ = [("num_batch", C.c_uint32), ("seed", C.c_uint32), ("init_stdev", C.c_double),
                 ("init_mode", C.c_int32), ("fm_v", P_f64)]
@@ -209,7 +221,9 @@ EXPORTS = ["vbfm_abi_version", "vbfm_last_error", "vbfm_create", "vbfm_destroy",
            "vbfm_online_init", "vbfm_online_epoch", "vbfm_online_get_state", "vbfm_save_state", "vbfm_load_state",
            "vbfm_model_file_info", "vbfm_model_write_host", "vbfm_model_read_host", "vbfm_model_save",
            "vbfm_model_from_ctx", "vbfm_model_load", "vbfm_model_info_get", "vbfm_model_last_error",
-           "vbfm_model_destroy", "vbfm_score", "vbfm_score_device"]
+           "vbfm_model_destroy", "vbfm_score", "vbfm_score_device",
+           "vbfm_synth_binarize", "vbfm_mcmc_class_info", "vbfm_model_file_task", "vbfm_model_write_host_task",
+           "vbfm_model_task"]
 
 # vbfm_exchange_fn: int fn(void *user, void *buf, uint64_t count, int32_t dtype, int32_t op)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32)
@@ -286,6 +300,8 @@ def lib():
         L.vbfm_mcmc_iterate.argtypes = [V, C.POINTER(McmcStats)]
         L.vbfm_mcmc_get_test_pred.argtypes = [V, C.c_int32, P_f64]
         L.vbfm_mcmc_factor_sweep.argtypes = [V, P_f64]
+        L.vbfm_mcmc_class_info.argtypes = [V, C.POINTER(McmcClassStats)]
+        L.vbfm_synth_binarize.argtypes = [V, C.c_int32, C.c_float, C.POINTER(C.c_uint64)]
         L.vbfm_online_init.argtypes = [V, C.POINTER(OnlineConfig)]
         L.vbfm_online_epoch.argtypes = [V, C.POINTER(OnlineStats)]
         L.vbfm_online_get_state.argtypes = [V, P_f64, P_f64, P_f64, P_f64, P_f64, P_f64, P_f64]
@@ -294,6 +310,10 @@ def lib():
         L.vbfm_model_file_info.argtypes = [C.c_char_p, C.POINTER(ModelInfo)]
         L.vbfm_model_write_host.argtypes = [C.c_char_p, C.POINTER(ModelInfo), C.POINTER(Params), C.POINTER(McmcParams)]
         L.vbfm_model_read_host.argtypes = [C.c_char_p, C.POINTER(ModelInfo), C.POINTER(Params), C.POINTER(McmcParams)]
+        L.vbfm_model_write_host_task.argtypes = [C.c_char_p, C.POINTER(ModelInfo), C.POINTER(Params),
+                                                 C.POINTER(McmcParams), C.c_int32]
+        L.vbfm_model_file_task.argtypes = [C.c_char_p, C.POINTER(C.c_int32)]
+        L.vbfm_model_task.argtypes = [V, C.POINTER(C.c_int32)]
         L.vbfm_model_save.argtypes = [V, C.c_char_p, C.c_uint32]
         L.vbfm_model_from_ctx.argtypes = [C.POINTER(V), V]
         L.vbfm_model_load.argtypes = [C.POINTER(V), C.c_char_p, C.c_int32]
@@ -415,14 +435,17 @@ class FMLearnVB:
 
     def __init__(self, k0=1, k1=1, num_factor=8, num_attribute=0, attr_group=None,
                  min_target=1.0, max_target=5.0, device=0, layout="auto", place_candidates=0,
-                 place_budget_bytes=0):
+                 place_budget_bytes=0, task="r"):
+        if task not in TASKS:
+            raise VbfmError("task must be r (regression) or c (binary classification)")
+        self.task = task
         self.k0, self.k1, self.k, self.D = int(bool(k0)), int(bool(k1)), int(num_factor), int(num_attribute)
         self.attr_group = None if attr_group is None else np.ascontiguousarray(attr_group, dtype=np.uint32)
         self.G = 1 if self.attr_group is None else int(self.attr_group.max()) + 1 if self.D else 1
         # place_candidates / place_budget_bytes: the store's record-buffer placement search
         # (include/vbfm.h vbfm_config; 0 = the library's defaults, place_candidates=1: no search)
         cfg = Config(self.k0, self.k1, self.k, self.D, self.G, _ptr(self.attr_group, P_u32),
-                     min_target, max_target, device, 0, int(place_candidates), int(place_budget_bytes))
+                     min_target, max_target, device, TASKS[task], int(place_candidates), int(place_budget_bytes))
         self._ctx = C.c_void_p()
         _check(lib().vbfm_create(C.byref(self._ctx), C.byref(cfg)))
         _check(lib().vbfm_set_layout(self._ctx, LAYOUTS[layout]), self._ctx)
@@ -529,6 +552,13 @@ class FMLearnVB:
             self.n_train = num_rows
         else:
             self.n_test = num_rows
+
+    def synth_binarize(self, which, threshold):
+        """Binary targets from a device-generated set: target = +1 where target >= threshold, else
+        -1, on the device. Returns the number of +1 rows."""
+        pos = C.c_uint64()
+        _check(lib().vbfm_synth_binarize(self._ctx, which, float(threshold), C.byref(pos)), self._ctx)
+        return pos.value
 
     def shape(self, which):
         n, nf, z = C.c_uint32(), C.c_uint32(), C.c_uint64()
@@ -731,10 +761,11 @@ class FMLearnMCMC(FMLearnVB):
     normals from a counter-based generator on the device (bench scale)."""
 
     def __init__(self, k0=1, k1=1, num_factor=8, num_attribute=0, attr_group=None,
-                 min_target=1.0, max_target=5.0, device=0, method="mcmc", layout="auto"):
+                 min_target=1.0, max_target=5.0, device=0, method="mcmc", layout="auto", task="r"):
         if method not in ("mcmc", "als"):
             raise VbfmError("method must be mcmc or als")
-        super().__init__(k0, k1, num_factor, num_attribute, attr_group, min_target, max_target, device, layout)
+        super().__init__(k0, k1, num_factor, num_attribute, attr_group, min_target, max_target, device, layout,
+                         task=task)
         self.method = method
 
     def init(self, seed, init_stdev=0.1, regular=(), rng=RNG_REFERENCE):
@@ -775,8 +806,15 @@ class FMLearnMCMC(FMLearnVB):
         self.num_iter_done += 1
         return st
 
+    def class_info(self):
+        """task "c": the last iteration's accuracies, log-likelihoods, correct counts and the rows the
+        latent-target step could not draw (vbfm_mcmc_class_stats) as a dict."""
+        st = McmcClassStats()
+        _check(lib().vbfm_mcmc_class_info(self._ctx, C.byref(st)), self._ctx)
+        return st.as_dict()
+
     def predict(self, num_iter=None):
-        """fm_learn_mcmc::predict (fm_learn_mcmc.h:355-381)."""
+        """fm_learn_mcmc::predict (fm_learn_mcmc.h:355-381); task "c": probabilities in [0, 1]."""
         out = np.zeros(self.n_test)
         n = self.num_iter_done if num_iter is None else num_iter
         _check(lib().vbfm_mcmc_get_test_pred(self._ctx, n, _ptr(out, P_f64)), self._ctx)
@@ -799,9 +837,9 @@ class FMLearnVBOnline(FMLearnVB):
     """
 
     def __init__(self, k0=1, k1=1, num_factor=8, num_attribute=0, attr_group=None,
-                 min_target=1.0, max_target=5.0, device=0):
+                 min_target=1.0, max_target=5.0, device=0, task="r"):
         super().__init__(k0, k1, num_factor, num_attribute, attr_group, min_target, max_target, device,
-                         layout="auto")
+                         layout="auto", task=task)
 
     def init(self, seed, init_stdev=0.1, num_batch=50, replay=False):
         """srand(seed); the VB learner's initial draws; fm_learn_vb_online::init (needs set_data first)."""
@@ -856,6 +894,9 @@ class Model:
         inf = ModelInfo()
         _check(lib().vbfm_model_info_get(self._m, C.byref(inf)))
         self.info = inf.as_dict()
+        t = C.c_int32()
+        _check(lib().vbfm_model_task(self._m, C.byref(t)))
+        self.task = {v: k for k, v in TASKS.items()}[t.value]   # "r" or "c"
 
     @classmethod
     def load(cls, path, device=0):
@@ -878,6 +919,13 @@ class Model:
         return inf.as_dict()
 
     @staticmethod
+    def file_task(path):
+        """The task of a model file ("r" or "c"), after validating the whole file. No GPU."""
+        t = C.c_int32()
+        _check(lib().vbfm_model_file_task(os.fsencode(path), C.byref(t)))
+        return {v: k for k, v in TASKS.items()}[t.value]
+
+    @staticmethod
     def read_params(path):
         """A model file's parameters as numpy arrays (v as [f][j], like get_params). No GPU."""
         info = Model.file_info(path)
@@ -897,18 +945,18 @@ class Model:
         return p
 
     @staticmethod
-    def write_params(path, info, params):
+    def write_params(path, info, params, task="r"):
         """Write a model file from host arrays (info: the ModelInfo fields as a dict; params as
-        read_params returns them). No GPU."""
+        read_params returns them; task "c" for the ALS / MCMC kinds only). No GPU."""
         inf = ModelInfo(**{k: info[k] for k, _ in ModelInfo._fields_ if k in info})
         a = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in params.items() if isinstance(v, np.ndarray)}
         if inf.kind in (0, 1):
             ps = Params(_ptr(a.get("mu_w"), P_f64), _ptr(a.get("sigma_w"), P_f64), _ptr(a.get("mu_v"), P_f64),
                         _ptr(a.get("sigma_v"), P_f64), None, None, 0.0, 0.0, 0.0, 0.0)
-            _check(lib().vbfm_model_write_host(os.fsencode(path), C.byref(inf), C.byref(ps), None))
+            _check(lib().vbfm_model_write_host_task(os.fsencode(path), C.byref(inf), C.byref(ps), None, TASKS[task]))
         else:
             ps = McmcParams(_ptr(a.get("w"), P_f64), _ptr(a.get("v"), P_f64), None, None, None, None, 0.0, 0.0, 0.0)
-            _check(lib().vbfm_model_write_host(os.fsencode(path), C.byref(inf), None, C.byref(ps)))
+            _check(lib().vbfm_model_write_host_task(os.fsencode(path), C.byref(inf), None, C.byref(ps), TASKS[task]))
 
     @property
     def alpha(self):

@@ -1,0 +1,96 @@
+// class_math_check.cpp -- csrc/vbfm_class_math.h and vbrng::Glibc's truncated normals compiled for
+// the host alone (its own main; tests/test_class_cpu.py builds it with g++ under ASan + UBSan and
+// compares what it prints with restatements written from the reference's lines).
+//   grid                        x, Phi, left expectation, right expectation on x in [-4, 4]
+//   sampler SEED                moments of the keyed (device-mode) sampler at five means, both sides
+//   edge                        non-finite yhat, and the fallback with the attempt cap forced to 0
+//   glibc SEED MU               1000 left_tgaussian(0, MU, 1) draws, the uniforms they came from
+#include "../scalable-variational-bayesian-factorization-machine_amd/csrc/vbfm_class_math.h"
+#include "../scalable-variational-bayesian-factorization-machine_amd/csrc/vbfm_rng.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+
+static int grid()
+{
+	for (int i = 0; i <= 800; i++) {
+		const double x = -4.0 + 0.01 * i;
+		printf("%.17g %.17g %.17g %.17g\n", x, vbcm::Phi(x), vbcm::expect_left(x), vbcm::expect_right(x));
+	}
+	return 0;
+}
+
+static int sampler(uint64_t seed)
+{
+	const double mus[5] = {-3.0, -0.5, 0.0, 0.5, 3.0};
+	const int N = 1000000;
+	for (int side = 0; side < 2; side++)
+		for (int m = 0; m < 5; m++) {
+			const double mu = mus[m];
+			const bool positive = side == 0;
+			double sum = 0.0, sq = 0.0, lo = std::numeric_limits<double>::infinity(), hi = -lo;
+			long attempts = 0, capped = 0, nonfinite = 0;
+			// centre the accumulation near the truncated mean so the variance does not cancel
+			const double c = positive ? vbcm::expect_left(mu) : vbcm::expect_right(mu);
+			for (int i = 0; i < N; i++) {
+				const vbcm::RowKey key(seed, vbcm::CLASS_STREAM | (uint64_t)(side * 5 + m), (uint64_t)i);
+				int a = 0, flag = 0;
+				const double s = vbcm::class_sample_target(mu, positive, key, vbcm::CLASS_MAX_ATTEMPTS, &a, &flag);
+				attempts += a;
+				capped += flag == vbcm::CLASS_CAPPED;
+				nonfinite += flag == vbcm::CLASS_NONFINITE;
+				sum += s - c;
+				sq += (s - c) * (s - c);
+				if (s < lo) lo = s;
+				if (s > hi) hi = s;
+			}
+			const double mean = c + sum / N, var = sq / N - (sum / N) * (sum / N);
+			printf("%d %.17g %d %.17g %.17g %.17g %.17g %ld %ld %ld\n", positive ? 1 : 0, mu, N, mean, var, lo, hi, attempts,
+			       capped, nonfinite);
+		}
+	return 0;
+}
+
+static int edge()
+{
+	const double inf = std::numeric_limits<double>::infinity();
+	const double bad[3] = {std::numeric_limits<double>::quiet_NaN(), inf, -inf};
+	const vbcm::RowKey key(1, vbcm::CLASS_STREAM, 0);
+	for (int side = 0; side < 2; side++)
+		for (int i = 0; i < 3; i++) {
+			int a = 0, flag = -1;
+			const double s = vbcm::class_sample_target(bad[i], side == 0, key, vbcm::CLASS_MAX_ATTEMPTS, &a, &flag);
+			printf("nonfinite %d %d %d %d\n", side, a, flag, s != s ? 1 : 0);
+		}
+	const double mus[5] = {-3.0, -0.5, 0.0, 0.5, 3.0};
+	for (int side = 0; side < 2; side++)
+		for (int m = 0; m < 5; m++) {
+			int a = 0, flag = -1;
+			const double s = vbcm::class_sample_target(mus[m], side == 0, key, 0, &a, &flag);
+			const double want = side == 0 ? vbcm::expect_left(mus[m]) : vbcm::expect_right(mus[m]);
+			printf("cap0 %d %.17g %d %d %.17g %.17g\n", side, mus[m], a, flag, s, want);
+		}
+	return 0;
+}
+
+static int glibc(uint32_t seed, double mu)
+{
+	vbrng::Glibc g(seed), u(seed);
+	for (int i = 0; i < 1000; i++) printf("draw %.17g\n", g.left_tgaussian(0.0, mu, 1.0));
+	for (int i = 0; i < 1000; i++) printf("rdraw %.17g\n", g.right_tgaussian(0.0, mu, 1.0));
+	printf("next %.17g\n", g.uniform());
+	for (int i = 0; i < 40000; i++) printf("u %.17g\n", u.uniform());
+	return 0;
+}
+
+int main(int argc, char **argv)
+{
+	if (argc >= 2 && !strcmp(argv[1], "grid")) return grid();
+	if (argc >= 3 && !strcmp(argv[1], "sampler")) return sampler(strtoull(argv[2], nullptr, 10));
+	if (argc >= 2 && !strcmp(argv[1], "edge")) return edge();
+	if (argc >= 4 && !strcmp(argv[1], "glibc")) return glibc((uint32_t)strtoul(argv[2], nullptr, 10), atof(argv[3]));
+	fprintf(stderr, "usage: class_math_check grid | sampler SEED | edge | glibc SEED MU\n");
+	return 2;
+}
