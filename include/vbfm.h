@@ -619,6 +619,55 @@ int vbfm_score(vbfm_model *m, const vbfm_csr *rows, const vbfm_score_opts *o, do
 int vbfm_score_device(vbfm_model *m, vbfm_ctx *ctx, int32_t which, const vbfm_score_opts *o, double *mean,
                       double *var, vbfm_score_stats *st);
 
+/* ---- candidate sets and recommendation (additive to ABI 4: new functions and structs only) ----
+ * No reference counterpart. The best topn of M candidate rows for each of B context rows, a pair
+ * (c, j) valued as the model's mean of ONE row that holds c's entries and j's entries -- without
+ * building that row. With base_r the unclipped mean of row r alone (vbfm_score's, clip = 0, lane-group
+ * order) and Q_r[f] the per-factor sum of row r (entries in ascending id, as vbfm_score orders them):
+ *     dot = 0;  for f = 0 .. k - 1:  dot = fma(Q_c[f], Q_j[f], dot)
+ *     raw(c, j) = (base_c + base_j - (k0 ? w0 : 0)) + dot          (w0 = mu_0_dash for the VB kinds)
+ * VB kinds use the means, ALS / MCMC the point values (MCMC_DRAW: the last draw). Every pair is
+ * computed by exactly this expression and the ranking is a total order -- larger raw first, equal raw
+ * by smaller candidate index -- so idx, score and count are bit-identical whatever the chunk size and
+ * the launch geometry. A pair whose raw is not finite is never returned (nonfinite_pairs counts them).
+ * The returned score is raw; with clip = 1 what vbfm_score would return for the model's task (clipped
+ * to the target range; a model of task c: Phi(raw)), applied to the survivors only; the ranking is
+ * always on raw. The identity holds for any entries (repeated ids, ids shared by c and j); raw differs
+ * from vbfm_score of the merged row by the rounding of a reordered fp64 sum. Variances (T_n) are not
+ * ranked. Limits: topn <= VBFM_REC_MAX_TOPN, num_factor <= 256; anything beyond is refused. */
+#define VBFM_REC_MAX_TOPN 128
+/* The candidates' sums on the model's device, prepared once and reused across vbfm_recommend calls.
+ * unknown_ids as vbfm_score_opts. A candidate set belongs to the model handle it was made from
+ * (another handle is refused) and must be destroyed before that model: destroying the model first is
+ * the caller's error. Failures are in vbfm_model_last_error(m). */
+typedef struct vbfm_candidates vbfm_candidates;
+int vbfm_candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids);
+uint32_t vbfm_candidates_count(const vbfm_candidates *c);
+void vbfm_candidates_destroy(vbfm_candidates *c);
+typedef struct {
+	int32_t topn;          /* 1 .. VBFM_REC_MAX_TOPN */
+	int32_t clip;          /* as vbfm_score_opts::clip, on the returned scores only */
+	int32_t unknown_ids;   /* of the context rows: 0 refuse, 1 skip the entry */
+	uint64_t chunk_bytes;  /* device memory per staged chunk of context rows, 0 = VBFM_SCORE_CHUNK_DEFAULT */
+} vbfm_recommend_opts;
+typedef struct {
+	uint32_t n_chunks;
+	uint64_t pairs;             /* B * M */
+	uint64_t nonfinite_pairs;   /* pairs whose raw was NaN or +-inf */
+	uint64_t excluded_hits;     /* pairs that beat their context's N-th best when met and were on its exclusion
+	                               list (the other excluded pairs are never looked up; depends on the geometry) */
+	double ms_prepare, ms_pairs, ms_merge;   /* device time of the chunks' row preparation, pair and merge kernels, summed */
+	double ms_total;            /* host wall time of the call */
+} vbfm_recommend_stats;
+/* contexts: host CSR, staged in chunks of whole rows as vbfm_score stages its rows. exclude: excl_ptr
+ * NULL, or per context a sorted (ascending) list of candidate indices never to return: context r's
+ * are excl_idx[excl_ptr[r] .. excl_ptr[r + 1]); an index >= the candidate count or an unsorted list
+ * fails the call, naming the row. Results: idx [B * topn] (-1 beyond count), score [B * topn] (NaN
+ * beyond count), count [B]: the entries returned for each context, best first. */
+int vbfm_recommend(vbfm_model *m, const vbfm_candidates *c, const vbfm_csr *contexts, const uint64_t *excl_ptr,
+                   const uint32_t *excl_idx, const vbfm_recommend_opts *o, int32_t *idx, double *score,
+                   uint32_t *count, vbfm_recommend_stats *st);
+
 #ifdef __cplusplus
 }
 #endif

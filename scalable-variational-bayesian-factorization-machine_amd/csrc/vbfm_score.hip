@@ -8,53 +8,13 @@
 // Kernels: k_score_exact (the reference's summation order, the bodies of k_predict_e / k_predict_t)
 // and k_score (lane groups, the structure of k_predict_e_wave / k_predict_et_wave). Both skip an
 // entry whose id is not in the model and report it (ScoreFlags); the training path's kernels
-// (vbfm_kernels.hip) trust their ids and stay as they are.
-#include "vbfm_ctx.h"
-#include "vbfm_math.h"
+// (vbfm_kernels.hip) trust their ids and stay as they are. The handle, k_score and the chunk staging
+// are in vbfm_score.h, shared with vbfm_recommend.hip.
+#include "vbfm_score.h"
 
-#include <algorithm>
-
-using namespace vbi;
+using namespace vbs;
 
 namespace {
-
-// ids >= num_attribute met by a launch: the smallest (row << 32 | id) -- the first such row and its
-// smallest unknown id -- and the number of such entries (each counted once, where the row's entries
-// are loaded)
-struct ScoreFlags {
-	unsigned long long first;     // ~0: none
-	unsigned long long skipped;
-};
-
-struct ScoreArgs {
-	const uint64_t *row_ptr;      // [n + 1] entry positions (of the whole call)
-	const uint2 *ent;             // entry p of the call is ent[p - ent_base]
-	uint64_t ent_base;
-	const double *mw, *mv;        // means: w [D], v [j*k + f]
-	const double2 *ms_w, *ms_v;   // {mu, sigma} pairs (VAR only)
-	int k, k1, k0;
-	uint32_t D;
-	double mu0, s0d;
-	int clip;
-	double mn, mx;
-	double *mean, *var;           // [n]
-	uint32_t n;
-	uint32_t row0;                // the call's index of row 0 of this launch (ScoreFlags::first)
-	ScoreFlags *flags;
-};
-
-DEVI double clip(double p, double mn, double mx)
-{
-	p = (p < mx) ? p : mx;
-	p = (mn < p) ? p : mn;
-	return p;
-}
-
-DEVI void flag_unknown(const ScoreArgs &a, uint32_t r, uint32_t id)
-{
-	atomicAdd(&a.flags->skipped, 1ull);
-	atomicMin(&a.flags->first, ((unsigned long long)(a.row0 + r) << 32) | (unsigned long long)id);
-}
 
 // Exact order: one thread per row, k_predict_e's and k_predict_t's bodies expression by expression
 // (factor-major sums, each over the row's entries in order), entries with an unknown id left out.
@@ -134,168 +94,11 @@ __global__ __launch_bounds__(256) void k_score_exact(const ScoreArgs a)
 	}
 }
 
-// entries whose factors a group loads before accumulating them in entry order (as the wave kernels)
-constexpr int score_pu(int KP) { return KP >= 4 ? 2 : (KP == 2 ? 4 : 8); }
-
-template <int G> DEVI double group_sum(double v)
-{
-	// the low log2(G) steps of wave_sum's butterfly: with zeros on the lanes of factors >= k a
-	// 64-lane butterfly adds the same values in the same order
-#pragma unroll
-	for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-	return v;
-}
-
-// Lane-group form: a group of G lanes of a wave scores one row (256 / G rows per workgroup,
-// grid-stride), factor f on lane f % G of the group (pass f / 64 when k > 64: then G = 64). The
-// structure and, accumulator by accumulator, the expressions of k_predict_e_wave /
-// k_predict_et_wave with the group in place of the wave: up to G entries loaded per step, one per
-// lane, id and x broadcast by a width-G shuffle, every lane summing its factor(s) over the row's
-// entries in entry order, the group's butterfly, then the linear term in entry order. For k <= G
-// that is the wave kernels' result bit for bit, from 64 / G times as many rows per wave.
-// VAR = false reads the means ([j*k + f], 8 B per factor); VAR = true the {mu, sigma} pairs, once
-// for both outputs.
-template <int G, int KP, bool VAR>
-__global__ __launch_bounds__(256) void k_score(const ScoreArgs a)
-{
-	static_assert(KP == 1 || G == 64, "several passes only with whole waves");
-	const uint32_t lane = threadIdx.x & 63, gl = lane & (G - 1), gbase = lane & ~(uint32_t)(G - 1);
-	const uint32_t ngroups = gridDim.x * (256u / G);
-	const int k = a.k;
-	const uint32_t D = a.D;
-	for (uint32_t r = (blockIdx.x * 256u + threadIdx.x) / G; r < a.n; r += ngroups) {
-		const uint64_t b = a.row_ptr[r] - a.ent_base, en = a.row_ptr[r + 1] - a.ent_base;
-		double qe[KP], q[KP], z[KP];
-#pragma unroll
-		for (int c = 0; c < KP; ++c) { qe[c] = 0.0; q[c] = 0.0; z[c] = 0.0; }
-		double qqe = 0.0, qq = 0.0;
-		constexpr int PU = score_pu(KP);
-		for (uint64_t p0 = b; p0 < en; p0 += G) {
-			const uint32_t cnt = (uint32_t)min<uint64_t>(G, en - p0);
-			const uint2 mine = gl < cnt ? a.ent[p0 + gl] : make_uint2(0u, 0u);
-			const bool unknown = gl < cnt && mine.x >= D;
-			if (unknown) flag_unknown(a, r, mine.x);
-			const uint64_t okm = __ballot(!unknown) >> gbase;   // bit i: entry i of this step is in the model
-			if (k <= 0) continue;
-			for (uint32_t i0 = 0; i0 < cnt; i0 += PU) {
-				// PU entries' factors in flight at once, then accumulated in entry order
-				double vm[PU][KP], vs[PU][KP];
-				float xs[PU];
-				bool ok[PU];
-#pragma unroll
-				for (int u = 0; u < PU; ++u) {
-					const int i = (int)min(i0 + u, cnt - 1);
-					const uint32_t j = __shfl(mine.x, i, G);
-					xs[u] = __uint_as_float(__shfl(mine.y, i, G));
-					ok[u] = i0 + u < cnt && ((okm >> i) & 1);
-#pragma unroll
-					for (int c = 0; c < KP; ++c) {
-						const int f = (int)gl + 64 * c;
-						vm[u][c] = 0.0;
-						vs[u][c] = 0.0;
-						if (f < k && ok[u]) {
-							if constexpr (VAR) {
-								const double2 m = a.ms_v[(size_t)j * k + f];
-								vm[u][c] = m.x;
-								vs[u][c] = m.y;
-							} else {
-								vm[u][c] = a.mv[(size_t)j * k + f];
-							}
-						}
-					}
-				}
-#pragma unroll
-				for (int u = 0; u < PU; ++u) {
-					if (i0 + u >= cnt) break;
-					if (!ok[u]) continue;
-					const float x = xs[u];
-#pragma unroll
-					for (int c = 0; c < KP; ++c)
-						if ((int)gl + 64 * c < k) {
-							const double m = vm[u][c];
-							qe[c] += m * x;                            // fm_learn_vb.h:93-133
-							qqe -= 0.5 * m * m * x * x;                // :136-163
-							if constexpr (VAR) {
-								const double s = vs[u][c];
-								q[c] += m * x * m * x;                 // :222-254
-								z[c] += s * x * x;
-								qq -= (m * m * x * x * x * x * s + 0.5 * x * x * x * x * s * s);   // :257-281
-							}
-						}
-				}
-			}
-		}
-		double e = 0.0, t = 0.0;
-#pragma unroll
-		for (int c = 0; c < KP; ++c)
-			if ((int)gl + 64 * c < k) {
-				e += 0.5 * qe[c] * qe[c];
-				if constexpr (VAR) t += (0.5 * z[c] * z[c] + z[c] * q[c]);
-			}
-		e = group_sum<G>(e);
-		qqe = group_sum<G>(qqe);
-		if constexpr (VAR) {
-			t = group_sum<G>(t);
-			qq = group_sum<G>(qq);
-		}
-		if (a.k1) {                                             // :166-188 / :284-301
-			// every lane gathers one entry's w, the group adds them in entry order
-			for (uint64_t p0 = b; p0 < en; p0 += G) {
-				const uint32_t cnt = (uint32_t)min<uint64_t>(G, en - p0);
-				double pe = 0.0, pt = 0.0;
-				bool known = false;
-				if (gl < cnt) {
-					const uint2 ent = a.ent[p0 + gl];
-					known = ent.x < D;
-					if (known) {
-						const float x = ent_x(ent);
-						if constexpr (VAR) {
-							const double2 w = a.ms_w[ent.x];
-							pe = w.x * x;
-							pt = w.y * x * x;
-						} else {
-							pe = a.mw[ent.x] * x;
-						}
-					}
-				}
-				const uint64_t okm = __ballot(known) >> gbase;
-				for (uint32_t i = 0; i < cnt; ++i) {
-					const double ve = __shfl(pe, (int)i, G);
-					const double vt = VAR ? __shfl(pt, (int)i, G) : 0.0;
-					if ((okm >> i) & 1) {
-						qqe += ve;
-						if constexpr (VAR) qq += vt;
-					}
-				}
-			}
-		}
-		e = e + qqe;
-		if (a.k0) e += a.mu0;
-		if constexpr (VAR) {
-			t = t + qq;                                         // :304-311
-			if (a.k0) t += a.s0d;
-		}
-		if (gl == 0) {
-			a.mean[r] = a.clip ? clip(e, a.mn, a.mx) : e;
-			if constexpr (VAR) a.var[r] = t;
-		}
-	}
-}
-
 // the means of {mu, sigma} pairs (or of an MCMC / ALS context's {value, 0} pairs)
 __global__ void k_score_means(const double2 *__restrict__ ms, double *__restrict__ out, size_t n)
 {
 	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
 	if (i < n) out[i] = ms[i].x;
-}
-
-template <int G, int KP> hipError_t launch_group(const ScoreArgs &a, bool var, hipStream_t s)
-{
-	const uint32_t per = 256u / G;   // rows per workgroup
-	const unsigned wg = (unsigned)std::min<uint64_t>(((uint64_t)a.n + per - 1) / per, 8192);
-	if (var) k_score<G, KP, true><<<wg, 256, 0, s>>>(a);
-	else k_score<G, KP, false><<<wg, 256, 0, s>>>(a);
-	return hipGetLastError();
 }
 
 // group: G the smallest of {8, 16, 32, 64} >= min(k, 64), ceil(k / 64) passes beyond; k > 256 (no
@@ -308,12 +111,7 @@ hipError_t launch_score(const ScoreArgs &a, bool group, bool var, hipStream_t s)
 		// wave-per-row form. Any G >= k gives the same bits.
 		const char *env = getenv("VBFM_SCORE_G");
 		const int gmin = env ? atoi(env) : 0;
-		if (a.k <= 8 && gmin <= 8) return launch_group<8, 1>(a, var, s);
-		if (a.k <= 16 && gmin <= 16) return launch_group<16, 1>(a, var, s);
-		if (a.k <= 32 && gmin <= 32) return launch_group<32, 1>(a, var, s);
-		if (a.k <= 64) return launch_group<64, 1>(a, var, s);
-		if (a.k <= 128) return launch_group<64, 2>(a, var, s);
-		return launch_group<64, 4>(a, var, s);
+		return var ? launch_group<true, false>(a, gmin, s) : launch_group<false, false>(a, gmin, s);
 	}
 	const unsigned wg = (unsigned)(((uint64_t)a.n + 255) / 256);
 	if (var) k_score_exact<true><<<wg, 256, 0, s>>>(a);
@@ -322,67 +120,6 @@ hipError_t launch_score(const ScoreArgs &a, bool group, bool var, hipStream_t s)
 }
 
 bool kind_vb(int32_t kind) { return kind == VBFM_MODEL_VB || kind == VBFM_MODEL_VB_ONLINE; }
-
-enum { SEV_C0, SEV_C1, SEV_K0, SEV_K1, SEV_DONE, SEV_N };
-
-}  // namespace
-
-struct vbfm_model {
-	std::string err;
-	int dev = 0;
-	vbfm_model_info info = {};
-	int32_t task = VBFM_TASK_REGRESSION;          // task c: clip = 1 scores are Phi(yhat), clip = 0 the raw yhat
-	double *mw = nullptr, *mv = nullptr;          // means: w [D], v [j*k + f] (ALS / MCMC: the values)
-	double2 *ms_w = nullptr, *ms_v = nullptr;     // VB kinds: the {mu, sigma} pairs
-	hipStream_t s = nullptr, s_copy = nullptr;    // kernels and results; the chunks' copies to the device
-	ScoreFlags *flags = nullptr;
-	// vbfm_score's staging, kept between calls: two pinned host and two device buffers for the
-	// chunks ([row_ptr slice | entries]) and for their results ([mean | var])
-	struct Slot {
-		uint8_t *h_in = nullptr, *d_in = nullptr;
-		double *h_out = nullptr, *d_out = nullptr;
-		hipEvent_t ev[SEV_N] = {};
-	} slot[2];
-	size_t cap_in = 0, cap_out = 0;               // bytes of every h_in / d_in; doubles of every h_out / d_out
-};
-
-namespace {
-
-int mfail(vbfm_model *m, const std::string &msg)
-{
-	if (m) m->err = msg; else vbfm_host_set_error(msg.c_str());
-	return -1;
-}
-
-template <class F> int mguarded(vbfm_model *m, F &&fn)
-{
-	try {
-		if (m) HIPCHK(hipSetDevice(m->dev));
-		fn();
-		return 0;
-	} catch (const HipError &e) {
-		return mfail(m, std::string("HIP error ") + hipGetErrorString(e.e) + " in " + e.what);
-	} catch (const std::string &msg) {
-		return mfail(m, msg);
-	} catch (const char *msg) {
-		return mfail(m, msg);
-	} catch (const std::bad_alloc &) {
-		return mfail(m, "host out of memory");
-	}
-}
-
-void staging_free(vbfm_model *m)
-{
-	for (auto &sl : m->slot) {
-		if (sl.h_in) (void)hipHostFree(sl.h_in);
-		if (sl.h_out) (void)hipHostFree(sl.h_out);
-		sl.h_in = nullptr;
-		sl.h_out = nullptr;
-		dfree(sl.d_in);
-		dfree(sl.d_out);
-	}
-	m->cap_in = m->cap_out = 0;
-}
 
 void model_free(vbfm_model *m)
 {
@@ -470,19 +207,6 @@ void require_opts(const vbfm_model *m, const vbfm_score_opts &o, const double *m
 		throw std::string("the model holds no variances (an ALS / MCMC kind): T_n cannot be scored");
 }
 
-ScoreArgs score_args(const vbfm_model *m, const vbfm_score_opts &o)
-{
-	ScoreArgs a = {};
-	a.mw = m->mw; a.mv = m->mv; a.ms_w = m->ms_w; a.ms_v = m->ms_v;
-	a.k = m->info.num_factor; a.k1 = m->info.k1; a.k0 = m->info.k0;
-	a.D = m->info.num_attribute;
-	a.mu0 = m->info.w0_or_mu0; a.s0d = m->info.sigma_0_dash;
-	a.clip = o.clip != 0 && m->task == VBFM_TASK_REGRESSION;   // task c: the link follows the kernel (score_link)
-	a.mn = m->info.min_target; a.mx = m->info.max_target;
-	a.flags = m->flags;
-	return a;
-}
-
 // task c: the probability Phi(yhat) "as pred_this is" (fm_learn_mcmc_simultaneous.h:178-182) in place
 // of the clip, over the n means a score kernel just left on m->s
 void score_link(const vbfm_model *m, const vbfm_score_opts &o, double *mean, uint32_t n)
@@ -495,51 +219,6 @@ bool group_order(const vbfm_model *m, const vbfm_score_opts &o, uint64_t nnz)
 {
 	if (o.order != VBFM_ORDER_AUTO) return o.order == VBFM_ORDER_GROUP;
 	return (double)nnz * m->info.num_factor > 5e7;
-}
-
-void flags_reset(vbfm_model *m)
-{
-	const ScoreFlags z = {~0ull, 0ull};
-	HIPCHK(hipMemcpyAsync(m->flags, &z, sizeof(z), hipMemcpyHostToDevice, m->s));
-	HIPCHK(hipStreamSynchronize(m->s));
-}
-
-ScoreFlags flags_read(vbfm_model *m)
-{
-	ScoreFlags f;
-	HIPCHK(hipMemcpyAsync(&f, m->flags, sizeof(f), hipMemcpyDeviceToHost, m->s));
-	HIPCHK(hipStreamSynchronize(m->s));
-	return f;
-}
-
-std::string unknown_msg(const vbfm_model *m, uint64_t row, uint32_t id)
-{
-	return "row " + std::to_string(row) + " holds feature id " + std::to_string(id) + ", but the model has num_attribute = " +
-	       std::to_string(m->info.num_attribute) + " (unknown_ids = skip scores such a row without the entry)";
-}
-
-double elapsed(hipEvent_t a, hipEvent_t b)
-{
-	float ms = 0.f;
-	HIPCHK(hipEventElapsedTime(&ms, a, b));
-	return ms;
-}
-
-struct ChunkPlan { uint32_t r0, r1; };
-
-// The reference sums a row's terms over data_t, i.e. in ascending feature id, entries of one id in
-// file order (Data::create_data_t, Data.h:457-509) -- the order of the device CSR a context builds.
-// Rows handed over in another order are put into it in the staging buffer (a stable sort of the
-// row; rows already ascending, the usual case, are only scanned).
-void stage_sort(vbfm_entry *ent, const uint64_t *row_ptr, uint32_t nr)
-{
-	const uint64_t e0 = row_ptr[0];
-	for (uint32_t r = 0; r < nr; r++) {
-		vbfm_entry *b = ent + (row_ptr[r] - e0), *e = ent + (row_ptr[r + 1] - e0);
-		bool sorted = true;
-		for (vbfm_entry *p = b; sorted && p + 1 < e; p++) sorted = p[0].id <= p[1].id;
-		if (!sorted) std::stable_sort(b, e, [](const vbfm_entry &x, const vbfm_entry &y) { return x.id < y.id; });
-	}
 }
 
 }  // namespace
@@ -650,43 +329,12 @@ int vbfm_score(vbfm_model *m, const vbfm_csr *rows, const vbfm_score_opts *opts,
 		const double t_begin = wall_s();
 		const vbfm_score_opts o = opts ? *opts : vbfm_score_opts{VBFM_ORDER_AUTO, 1, 0, 0};
 		require_opts(m, o, mean, var);
-		const uint32_t n = rows->num_rows;
 		vbfm_score_stats out = {};
-		if (n && !rows->row_ptr) throw std::string("vbfm_score: rows without row_ptr");
-		if (rows->nnz && !rows->row_ent) throw std::string("vbfm_score: rows without entries");
-		if (n && (rows->row_ptr[0] != 0 || rows->row_ptr[n] != rows->nnz))
-			throw std::string("vbfm_score: row_ptr does not run from 0 to nnz");
 		// whole rows per chunk, at most chunk_bytes of [row_ptr slice | entries]; a larger row alone
-		const uint64_t budget = o.chunk_bytes ? o.chunk_bytes : VBFM_SCORE_CHUNK_DEFAULT;
-		std::vector<ChunkPlan> plan;
 		size_t need_in = 0, need_rows = 0;
-		for (uint32_t r0 = 0; r0 < n;) {
-			uint32_t r1 = r0;
-			uint64_t bytes = 8;
-			while (r1 < n) {
-				if (rows->row_ptr[r1 + 1] < rows->row_ptr[r1]) throw std::string("vbfm_score: row_ptr is not monotone");
-				const uint64_t add = 8 + (rows->row_ptr[r1 + 1] - rows->row_ptr[r1]) * 8;
-				if (r1 > r0 && bytes + add > budget) break;
-				bytes += add;
-				r1++;
-			}
-			plan.push_back(ChunkPlan{r0, r1});
-			need_in = std::max<size_t>(need_in, bytes);
-			need_rows = std::max<size_t>(need_rows, r1 - r0);
-			r0 = r1;
-		}
-		const size_t need_out = need_rows * (var ? 2 : 1);
-		if (need_in > m->cap_in || need_out > m->cap_out) {
-			staging_free(m);
-			for (auto &sl : m->slot) {
-				HIPCHK(hipHostMalloc((void **)&sl.h_in, need_in, hipHostMallocDefault));
-				HIPCHK(hipHostMalloc((void **)&sl.h_out, std::max<size_t>(need_out, 1) * 8, hipHostMallocDefault));
-				sl.d_in = dalloc<uint8_t>(need_in);
-				sl.d_out = dalloc<double>(need_out);
-			}
-			m->cap_in = need_in;
-			m->cap_out = need_out;
-		}
+		const std::vector<ChunkPlan> plan = plan_chunks(rows, o.chunk_bytes ? o.chunk_bytes : VBFM_SCORE_CHUNK_DEFAULT,
+		                                                "vbfm_score", &need_in, &need_rows);
+		staging_reserve(m, need_in, need_rows * (var ? 2 : 1));
 		flags_reset(m);
 		const bool group = group_order(m, o, rows->nnz);
 		// chunk i's results back in the caller's arrays, its times added
@@ -703,17 +351,15 @@ int vbfm_score(vbfm_model *m, const vbfm_csr *rows, const vbfm_score_opts *opts,
 			vbfm_model::Slot &sl = m->slot[i & 1];
 			if (i >= 2) drain(i - 2);   // the slot's previous chunk has left both of its buffers
 			const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
-			const uint64_t e0 = rows->row_ptr[r0], ne = rows->row_ptr[r0 + nr] - e0;
+			const uint64_t e0 = rows->row_ptr[r0];
 			const size_t ptr_bytes = ((size_t)nr + 1) * 8;
-			memcpy(sl.h_in, rows->row_ptr + r0, ptr_bytes);
-			if (ne) memcpy(sl.h_in + ptr_bytes, rows->row_ent + e0, ne * 8);
-			stage_sort((vbfm_entry *)(sl.h_in + ptr_bytes), rows->row_ptr + r0, nr);
+			const size_t in_bytes = stage_rows(sl.h_in, rows, r0, nr);
 			// the copy runs on its own stream, under the kernel of the chunk before
 			HIPCHK(hipEventRecord(sl.ev[SEV_C0], m->s_copy));
-			HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, ptr_bytes + ne * 8, hipMemcpyHostToDevice, m->s_copy));
+			HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, in_bytes, hipMemcpyHostToDevice, m->s_copy));
 			HIPCHK(hipEventRecord(sl.ev[SEV_C1], m->s_copy));
 			HIPCHK(hipStreamWaitEvent(m->s, sl.ev[SEV_C1], 0));
-			ScoreArgs a = score_args(m, o);
+			ScoreArgs a = score_args(m, o.clip);
 			a.row_ptr = (const uint64_t *)sl.d_in;
 			a.ent = (const uint2 *)(sl.d_in + ptr_bytes);
 			a.ent_base = e0;
@@ -755,7 +401,7 @@ int vbfm_score_device(vbfm_model *m, vbfm_ctx *c, int32_t which, const vbfm_scor
 		vbfm_score_stats out = {};
 		DevScratch<double> res((size_t)d.n * (var ? 2 : 1));
 		flags_reset(m);
-		ScoreArgs a = score_args(m, o);
+		ScoreArgs a = score_args(m, o.clip);
 		a.row_ptr = d.row_ptr;
 		a.ent = d.csr;
 		a.mean = res;

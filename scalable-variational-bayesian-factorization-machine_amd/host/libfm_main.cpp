@@ -16,7 +16,8 @@
 //     rows|features, -transport rccl|host, -plan 1 (print the ranks' shard plan, no GPU);
 //   * -save_model FILE (every method: the parameters alone, after the last iteration) and the
 //     predict-only mode -load_model FILE -test T -out P [-out_var V] (no -train; no reference
-//     counterpart: the reference predicts only the test set attached while training).
+//     counterpart: the reference predicts only the test set attached while training); with
+//     -candidates ITEMS -topn N [-exclude X] that mode ranks the rows of ITEMS for every row of T.
 //
 // Multi-GPU (-devices): the reference is one process on one core. Here this process parses the
 // flags and loads the data (host code only, no HIP call), then forks one rank process per GPU
@@ -60,6 +61,11 @@
 // ... and so are the entry points of -task c
 #pragma weak vbfm_mcmc_class_info
 #pragma weak vbfm_model_file_task
+// ... and those of -candidates
+#pragma weak vbfm_candidates_create
+#pragma weak vbfm_candidates_count
+#pragma weak vbfm_candidates_destroy
+#pragma weak vbfm_recommend
 
 namespace {
 
@@ -1012,6 +1018,91 @@ static void run_score(const ScoreRun &r)
 	}
 }
 
+// -load_model FILE -test CONTEXTS -candidates ITEMS -topn N -out P [-exclude X]: the best N rows of
+// ITEMS for every row of CONTEXTS (vbfm_recommend; the targets of both files are read and ignored).
+// Line r of P: the context's "index:score" pairs, best first, scores at 17 digits and as -out of a
+// scoring run would print them (clipped; task c: probabilities); an empty line when nothing is
+// returned. Line r of X: candidate indices (0-based rows of ITEMS) never to return, in any order.
+struct RecommendRun {
+	std::string model_file, context_file, item_file, out_file, exclude_file;
+	int32_t device, topn;
+	bool skip_unknown;
+};
+
+static bool have_recommender()
+{
+	return have_scorer() && vbfm_candidates_create && vbfm_candidates_count && vbfm_candidates_destroy && vbfm_recommend;
+}
+
+static void run_recommend(const RecommendRun &r)
+{
+	if (!have_recommender()) throw std::string("this build has no scorer");
+	Data ctx, items;
+	load(r.context_file, ctx, "contexts");
+	load(r.item_file, items, "candidates");
+	const uint32_t B = ctx.h.num_rows;
+	std::vector<uint64_t> xptr;
+	std::vector<uint32_t> xidx;
+	if (!r.exclude_file.empty()) {   // sorted and without duplicates, as the library takes them
+		std::ifstream in(r.exclude_file.c_str());
+		if (!in.is_open()) throw std::string("Unable to open file " + r.exclude_file);
+		xptr.push_back(0);
+		std::string line;
+		for (uint32_t row = 0; row < B; row++) {
+			if (!std::getline(in, line)) throw std::string("-exclude: " + r.exclude_file + " has fewer lines than -test has rows");
+			std::vector<uint32_t> ids;
+			std::istringstream ls(line);
+			long long v;
+			while (ls >> v) {
+				if (v < 0 || v > 0xffffffffll) throw std::string("-exclude: line " + std::to_string(row + 1) + " holds an index out of range");
+				ids.push_back((uint32_t)v);
+			}
+			if (!ls.eof()) throw std::string("-exclude: line " + std::to_string(row + 1) + " is not a list of indices");
+			std::sort(ids.begin(), ids.end());
+			ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+			xidx.insert(xidx.end(), ids.begin(), ids.end());
+			xptr.push_back(xidx.size());
+		}
+		if (xidx.empty()) xidx.push_back(0);
+	}
+	vbfm_model *m = nullptr;
+	if (vbfm_model_load(&m, r.model_file.c_str(), r.device) != 0) throw std::string(vbfm_last_error(nullptr));
+	vbfm_candidates *cs = nullptr;
+	try {
+		const vbfm_csr item_rows{items.h.num_rows, items.h.nnz, items.h.row_ptr, items.h.row_ent};
+		if (vbfm_candidates_create(&cs, m, &item_rows, r.skip_unknown ? 1 : 0) != 0) throw std::string(vbfm_model_last_error(m));
+		const vbfm_csr rows{B, ctx.h.nnz, ctx.h.row_ptr, ctx.h.row_ent};
+		const vbfm_recommend_opts o{r.topn, 1, r.skip_unknown ? 1 : 0, 0};
+		const size_t n = (size_t)B * (size_t)std::max(r.topn, 0);
+		std::vector<int32_t> idx(n);
+		std::vector<double> score(n);
+		std::vector<uint32_t> count(B);
+		vbfm_recommend_stats st;
+		if (vbfm_recommend(m, cs, &rows, xptr.empty() ? nullptr : xptr.data(), xptr.empty() ? nullptr : xidx.data(), &o,
+		                   idx.data(), score.data(), count.data(), &st) != 0)
+			throw std::string(vbfm_model_last_error(m));
+		std::cout << "ranked " << st.pairs << " pairs (" << B << " contexts x " << vbfm_candidates_count(cs) << " candidates) in "
+		          << st.ms_total << " ms: prepare " << st.ms_prepare << ", pairs " << st.ms_pairs << ", merge " << st.ms_merge
+		          << " ms on the device";
+		if (st.nonfinite_pairs) std::cout << "; " << st.nonfinite_pairs << " pairs were not finite";
+		std::cout << std::endl;
+		FILE *f = fopen(r.out_file.c_str(), "w");
+		if (!f) throw std::string("Unable to open file " + r.out_file);
+		for (uint32_t c = 0; c < B; c++) {
+			for (uint32_t e = 0; e < count[c]; e++)
+				fprintf(f, "%s%d:%.17g", e ? " " : "", idx[(size_t)c * r.topn + e], score[(size_t)c * r.topn + e]);
+			fputc('\n', f);
+		}
+		fclose(f);
+		vbfm_candidates_destroy(cs);
+		vbfm_model_destroy(m);
+	} catch (...) {
+		if (cs) vbfm_candidates_destroy(cs);
+		vbfm_model_destroy(m);
+		throw;
+	}
+}
+
 // everything one rank runs, given the parsed command line
 struct Job {
 	std::string method;
@@ -1196,6 +1287,9 @@ int main(int argc, char **argv)
 		const std::string p_loadm = cmd.reg("load_model", "predict only: score -test with this -save_model file and write -out (no -train; not with -method, -dim, -iter)");
 		const std::string p_outvar = cmd.reg("out_var", "with -load_model: one variance term T_n per line at 17 digits (vb and vb_online models; var(y) = T_n + 1/alpha)");
 		const std::string p_unknown = cmd.reg("unknown_ids", "with -load_model: refuse (default) or skip entries whose feature id the model does not have");
+		const std::string p_cand = cmd.reg("candidates", "with -load_model: rank the rows of this file for every row of -test and write the best -topn per row to -out as index:score pairs (targets are ignored)");
+		const std::string p_topn = cmd.reg("topn", "with -candidates: entries to return per row of -test (1..128)");
+		const std::string p_excl = cmd.reg("exclude", "with -candidates: line r lists the candidate indices (0-based rows of -candidates) never to return for row r of -test");
 		if (cmd.has(p_help) || argc == 1) { cmd.print_help(); return 0; }
 		cmd.check();
 
@@ -1203,6 +1297,10 @@ int main(int argc, char **argv)
 			for (const std::string &p : {p_method, p_dim, p_iter})
 				if (cmd.has(p)) throw std::string("-load_model scores with a trained model: -" + p + " does not apply");
 			if (!cmd.has(p_test) || !cmd.has(p_out)) throw std::string("-load_model needs -test and -out");
+			if (cmd.has(p_topn) && !cmd.has(p_cand)) throw std::string("-topn needs -candidates");
+			if (cmd.has(p_excl) && !cmd.has(p_cand)) throw std::string("-exclude needs -candidates");
+			if (cmd.has(p_cand) && !cmd.has(p_topn)) throw std::string("-candidates needs -topn");
+			if (cmd.has(p_cand) && cmd.has(p_outvar)) throw std::string("-out_var does not apply to -candidates (variances are not ranked)");
 			// the task is the file's; a -task that contradicts it is refused
 			int32_t ftask = VBFM_TASK_REGRESSION;
 			if (!have_scorer()) throw std::string("this build has no scorer");
@@ -1218,11 +1316,18 @@ int main(int argc, char **argv)
 			}
 			const std::string unk = cmd.get(p_unknown, "refuse");
 			if (unk != "refuse" && unk != "skip") throw std::string("-unknown_ids: refuse or skip");
+			if (cmd.has(p_cand)) {
+				run_recommend(RecommendRun{cmd.get(p_loadm), cmd.get(p_test), cmd.get(p_cand), cmd.get(p_out), cmd.get(p_excl),
+				                           (int32_t)cmd.geti(p_dev, 0), (int32_t)cmd.geti(p_topn, 0), unk == "skip"});
+				return 0;
+			}
 			run_score(ScoreRun{cmd.get(p_loadm), cmd.get(p_test), cmd.get(p_out), cmd.get(p_outvar),
 			                   (int32_t)cmd.geti(p_dev, 0), unk == "skip", ftask});
 			return 0;
 		}
 		if (cmd.has(p_outvar) || cmd.has(p_unknown)) throw std::string("-out_var and -unknown_ids belong to -load_model");
+		if (cmd.has(p_cand) || cmd.has(p_topn) || cmd.has(p_excl))
+			throw std::string("-candidates, -topn and -exclude belong to -load_model");
 
 		const uint32_t seed = cmd.has(p_seed) ? (uint32_t)cmd.geti(p_seed, 0) : (uint32_t)time(NULL);
 		const std::string method = cmd.get(p_method, "mcmc");

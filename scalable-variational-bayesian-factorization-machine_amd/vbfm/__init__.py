@@ -207,6 +207,22 @@ class ScoreStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+REC_MAX_TOPN = 128   # VBFM_REC_MAX_TOPN
+
+
+class RecommendOpts(C.Structure):
+    _fields_ = [("topn", C.c_int32), ("clip", C.c_int32), ("unknown_ids", C.c_int32), ("chunk_bytes", C.c_uint64)]
+
+
+class RecommendStats(C.Structure):
+    _fields_ = [("n_chunks", C.c_uint32), ("pairs", C.c_uint64), ("nonfinite_pairs", C.c_uint64),
+                ("excluded_hits", C.c_uint64), ("ms_prepare", C.c_double), ("ms_pairs", C.c_double),
+                ("ms_merge", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/vbfm.h declares (checked by tests/test_capi_cpu.py)
 EXPORTS = ["vbfm_abi_version", "vbfm_last_error", "vbfm_create", "vbfm_destroy", "vbfm_set_train",
            "vbfm_set_test", "vbfm_synth_generate", "vbfm_synth_multihot", "vbfm_get_csc", "vbfm_get_shape", "vbfm_get_levels",
@@ -223,7 +239,8 @@ EXPORTS = ["vbfm_abi_version", "vbfm_last_error", "vbfm_create", "vbfm_destroy",
            "vbfm_model_from_ctx", "vbfm_model_load", "vbfm_model_info_get", "vbfm_model_last_error",
            "vbfm_model_destroy", "vbfm_score", "vbfm_score_device",
            "vbfm_synth_binarize", "vbfm_mcmc_class_info", "vbfm_model_file_task", "vbfm_model_write_host_task",
-           "vbfm_model_task"]
+           "vbfm_model_task", "vbfm_candidates_create", "vbfm_candidates_count", "vbfm_candidates_destroy",
+           "vbfm_recommend"]
 
 # vbfm_exchange_fn: int fn(void *user, void *buf, uint64_t count, int32_t dtype, int32_t op)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32)
@@ -324,6 +341,13 @@ def lib():
         L.vbfm_model_destroy.restype = None
         L.vbfm_score.argtypes = [V, C.POINTER(Csr), C.POINTER(ScoreOpts), P_f64, P_f64, C.POINTER(ScoreStats)]
         L.vbfm_score_device.argtypes = [V, V, C.c_int32, C.POINTER(ScoreOpts), P_f64, P_f64, C.POINTER(ScoreStats)]
+        L.vbfm_candidates_create.argtypes = [C.POINTER(V), V, C.POINTER(Csr), C.c_int32]
+        L.vbfm_candidates_count.argtypes = [V]
+        L.vbfm_candidates_count.restype = C.c_uint32
+        L.vbfm_candidates_destroy.argtypes = [V]
+        L.vbfm_candidates_destroy.restype = None
+        L.vbfm_recommend.argtypes = [V, V, C.POINTER(Csr), P_u64, P_u32, C.POINTER(RecommendOpts),
+                                     C.POINTER(C.c_int32), P_f64, P_u32, C.POINTER(RecommendStats)]
         _lib = L
     return _lib
 
@@ -891,6 +915,7 @@ class Model:
     def __init__(self, handle):
         self._m = handle
         self.last_stats = None
+        self.last_recommend_stats = None
         inf = ModelInfo()
         _check(lib().vbfm_model_info_get(self._m, C.byref(inf)))
         self.info = inf.as_dict()
@@ -971,10 +996,10 @@ class Model:
     def _opts(order, clip, unknown_ids, chunk_bytes):
         return ScoreOpts(ORDERS[order], int(bool(clip)), UNKNOWN_IDS[unknown_ids], int(chunk_bytes))
 
-    def score(self, data, variance=False, order="auto", clip=True, unknown_ids="refuse", chunk_bytes=0):
-        """Mean prediction of every row of `data` -- a DataSubset that holds its rows (from
-        DataSubset.load) or a (row_ptr, feat, val) triple -- and with variance=True the pair
-        (mean, T). The rows stay in host memory and are staged in chunks of chunk_bytes."""
+    @staticmethod
+    def _rows(data):
+        """vbfm_csr of a DataSubset that holds its rows or of a (row_ptr, feat, val) triple, and the
+        arrays it points into (keep them alive while the struct is in use)."""
         if isinstance(data, DataSubset):
             if data.row_ptr is None:
                 raise VbfmError("score needs the rows (a data set from DataSubset.load, or a (row_ptr, feat, val) triple)")
@@ -987,7 +1012,14 @@ class Model:
             ent["id"] = feat
             ent["value"] = val
         n = len(rp) - 1 if len(rp) else 0
-        rows = Csr(n, len(ent), _ptr(rp, P_u64), ent.ctypes.data if len(ent) else None)
+        return Csr(n, len(ent), _ptr(rp, P_u64), ent.ctypes.data if len(ent) else None), (rp, ent)
+
+    def score(self, data, variance=False, order="auto", clip=True, unknown_ids="refuse", chunk_bytes=0):
+        """Mean prediction of every row of `data` -- a DataSubset that holds its rows (from
+        DataSubset.load) or a (row_ptr, feat, val) triple -- and with variance=True the pair
+        (mean, T). The rows stay in host memory and are staged in chunks of chunk_bytes."""
+        rows, _keep = self._rows(data)
+        n = rows.num_rows
         mean = np.zeros(n)
         var = np.zeros(n) if variance else None
         st = ScoreStats()
@@ -1009,10 +1041,79 @@ class Model:
         self.last_stats = st.as_dict()
         return (mean, var) if variance else mean
 
+    def candidates(self, data, unknown_ids="refuse"):
+        """The rows of `data` (as score takes them) prepared once on the device as a candidate set
+        for recommend. Close it before the model."""
+        rows, _keep = self._rows(data)
+        h = C.c_void_p()
+        self._mcheck(lib().vbfm_candidates_create(C.byref(h), self._m, C.byref(rows), UNKNOWN_IDS[unknown_ids]))
+        return Candidates(h, self)
+
+    def recommend(self, contexts, candidates, topn, exclude=None, clip=True, unknown_ids="refuse", chunk_bytes=0):
+        """The best `topn` candidates for every context row (include/vbfm.h "candidate sets and
+        recommendation"): (idx [B, topn] int32, -1 beyond count; score [B, topn] float64, NaN beyond
+        count; count [B] uint32), best first. A pair is valued as the mean of one row holding the
+        context's and the candidate's entries. exclude: None, a list with one integer array of
+        candidate indices (ascending) per context, or a (ptr, idx) pair."""
+        rows, _keep = self._rows(contexts)
+        B, topn = rows.num_rows, int(topn)
+        xp = xi = None
+        if exclude is not None:
+            if isinstance(exclude, tuple) and len(exclude) == 2:
+                xp = np.ascontiguousarray(exclude[0], dtype=np.uint64)
+                xi = np.ascontiguousarray(exclude[1], dtype=np.uint32)
+            else:
+                if len(exclude) != B:
+                    raise VbfmError("exclude holds %d lists for %d contexts" % (len(exclude), B))
+                xp = np.zeros(B + 1, dtype=np.uint64)
+                np.cumsum([len(e) for e in exclude], out=xp[1:])
+                xi = (np.concatenate([np.asarray(e, dtype=np.uint32).ravel() for e in exclude])
+                      if B else np.zeros(0, dtype=np.uint32))
+                xi = np.ascontiguousarray(xi, dtype=np.uint32)
+            if len(xp) != B + 1 or int(xp[-1]) != len(xi):
+                raise VbfmError("exclude: ptr must hold B + 1 positions ending at len(idx)")
+            if len(xi) == 0:
+                xi = np.zeros(1, dtype=np.uint32)
+        shape = max(topn, 0)
+        idx = np.full((B, shape), -1, dtype=np.int32)
+        score = np.full((B, shape), np.nan)
+        count = np.zeros(B, dtype=np.uint32)
+        st = RecommendStats()
+        o = RecommendOpts(topn, int(bool(clip)), UNKNOWN_IDS[unknown_ids], int(chunk_bytes))
+        self._mcheck(lib().vbfm_recommend(self._m, candidates._c, C.byref(rows), _ptr(xp, P_u64), _ptr(xi, P_u32),
+                                          C.byref(o), idx.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(score, P_f64),
+                                          _ptr(count, P_u32), C.byref(st)))
+        self.last_recommend_stats = st.as_dict()
+        return idx, score, count
+
     def close(self):
         if self._m:
             lib().vbfm_model_destroy(self._m)
             self._m = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Candidates:
+    """A candidate set of one Model (Model.candidates): the rows' sums on the device, reused across
+    Model.recommend calls. It keeps its model alive; close it before closing the model."""
+
+    def __init__(self, handle, model):
+        self._c = handle
+        self.model = model
+        self.count = int(lib().vbfm_candidates_count(handle))
+
+    def __len__(self):
+        return self.count
+
+    def close(self):
+        if self._c:
+            lib().vbfm_candidates_destroy(self._c)
+            self._c = C.c_void_p()
 
     def __del__(self):
         try:
