@@ -531,8 +531,10 @@ int vbfm_init_params_host(uint32_t seed, double init_stdev, int32_t num_factor, 
 #define VBFM_MODEL_VB 0
 #define VBFM_MODEL_VB_ONLINE 1
 #define VBFM_MODEL_ALS 2
-#define VBFM_MODEL_MCMC_DRAW 3   /* the LAST draw of the chain (fm.w0 / fm.w / fm.v after the last
-                                    iteration), not the chain average the MCMC learner's -out reports */
+#define VBFM_MODEL_MCMC_DRAW 3   /* ONE draw of the chain (fm.w0 / fm.w / fm.v as they are when the model is taken:
+                                    the last draw after the last iteration), not the chain average the MCMC
+                                    learner's -out reports: that is VBFM_MODEL_MCMC_CHAIN ("chains of draws" below) */
+#define VBFM_MODEL_MCMC_CHAIN 4  /* S draws of the chain in one model: scored as their average, with the spread */
 typedef struct {
 	int32_t kind, k0, k1, num_factor;
 	uint32_t num_attribute;
@@ -561,6 +563,26 @@ int vbfm_model_read_host(const char *path, vbfm_model_info *info, vbfm_params *v
 int vbfm_model_file_task(const char *path, int32_t *task);   /* host-only; validates the whole file */
 int vbfm_model_write_host_task(const char *path, const vbfm_model_info *info, const vbfm_params *vb,
                                const vbfm_mcmc_params *mc, int32_t task);
+/* A chain file (VBFM_MODEL_MCMC_CHAIN, either task) holds S >= 1 draws. vbfm_model_info cannot grow, so
+ * the draw count travels beside it, as the task does: in the file it is an 8-byte extension of the
+ * header (draw count, a reserved word), and the file has format version 4, which an earlier library
+ * refuses rather than reading it as one draw; every file of the other kinds stays byte for byte what
+ * it was. In the info of a chain w0_or_mu0 and alpha are the LAST draw's, has_variance is 0 (the file
+ * holds no sigma; the spread across draws is scored, see vbfm_score). Payload, as the library stores
+ * it: the S {w0, alpha} pairs in draw order, then cw [j*S + s], then cv [(j*S + s)*k + f] (feature-
+ * major, the draws of one feature adjacent). The reader checks magic, version, kind, S >= 1, that
+ * the reserved word is 0, that
+ * S * D * (k + 1) * 8 does not overflow 64 bits, that the sizes equal the file's size exactly and the
+ * checksum before any allocation that grows with the header. vbfm_model_file_info and
+ * vbfm_model_file_task accept a chain file; vbfm_model_read_host refuses it and names
+ * vbfm_model_read_host_draw; vbfm_model_write_host(_task) refuses the kind. */
+int vbfm_model_file_draws(const char *path, uint32_t *draws);   /* host-only; validates the whole file; 1 for every other kind */
+/* draws[s], s = 0 .. S-1 in chain order: w [D], v [k*D] as [f][j], w0, alpha (the other fields are not read) */
+int vbfm_model_write_host_chain(const char *path, const vbfm_model_info *info, int32_t task, uint32_t S,
+                                const vbfm_mcmc_params *draws /*[S]*/);
+/* draw s of a chain file into mc (NULL arrays skipped; v as [f][j]; w0 and alpha are the draw's); s >= S
+ * and a file of another kind are refused */
+int vbfm_model_read_host_draw(const char *path, uint32_t s, vbfm_model_info *info, vbfm_mcmc_params *mc);
 
 /* A model on a device: the tables the scoring kernels read. Failures of a call that has a model
  * are in vbfm_model_last_error(m), those without in vbfm_last_error(NULL). */
@@ -572,6 +594,10 @@ int vbfm_model_from_ctx(vbfm_model **out, vbfm_ctx *ctx);   /* device-to-device 
 int vbfm_model_load(vbfm_model **out, const char *path, int32_t device);
 int vbfm_model_info_get(const vbfm_model *m, vbfm_model_info *out);
 int vbfm_model_task(const vbfm_model *m, int32_t *task);
+int vbfm_model_num_draws(const vbfm_model *m, uint32_t *draws);   /* S of a chain model, 1 for every other kind */
+/* w0 and alpha of draw s (s < vbfm_model_num_draws; NULL pointers skipped); a model of another kind: s = 0,
+ * the info's w0_or_mu0 and alpha */
+int vbfm_model_draw_scalars(const vbfm_model *m, uint32_t s, double *w0, double *alpha);
 const char *vbfm_model_last_error(const vbfm_model *m);
 void vbfm_model_destroy(vbfm_model *m);
 
@@ -604,11 +630,12 @@ typedef struct {
 	double ms_total;             /* host wall time of the call */
 } vbfm_score_stats;
 /* mean[r] = predict_data_and_write_to_eterms (fm_learn_vb.h:70-203) of row r on the model's
- * parameters -- for ALS / MCMC kinds on the point values (MCMC_DRAW: the last draw's prediction,
- * not the chain average). var (NULL, or [rows]) = the reference's T_n
- * (predict_t_and_write_to_qterms, fm_learn_vb.h:207-312), refused for ALS / MCMC kinds; the
- * predictive variance of y is T_n + 1 / alpha (alpha is in the info; the addition is the
- * caller's). o == NULL: all defaults (auto order, clipped, refuse). vbfm_score never needs the
+ * parameters -- for ALS / MCMC kinds on the point values (MCMC_DRAW: that one draw's prediction,
+ * not the chain average: a MCMC_CHAIN model scores that, see "chains of draws" below). var (NULL, or
+ * [rows]) = the reference's T_n (predict_t_and_write_to_qterms, fm_learn_vb.h:207-312), refused for the
+ * ALS and MCMC_DRAW kinds, for a MCMC_CHAIN model the spread across its draws; the predictive variance of
+ * y is T_n + 1 / alpha (alpha is in the info; the addition is the caller's). o == NULL: all defaults
+ * (auto order, clipped, refuse). vbfm_score never needs the
  * rows in device memory at once: it cuts them into chunks of whole rows of at most chunk_bytes (a
  * larger row is a chunk by itself), staged through two pinned host and two device buffers, chunk
  * i + 1's copy under chunk i's kernel; results are bit-identical whatever the chunk size. */
@@ -619,6 +646,55 @@ int vbfm_score(vbfm_model *m, const vbfm_csr *rows, const vbfm_score_opts *o, do
 int vbfm_score_device(vbfm_model *m, vbfm_ctx *ctx, int32_t which, const vbfm_score_opts *o, double *mean,
                       double *var, vbfm_score_stats *st);
 
+/* ---- chains of draws (additive to ABI 4: new functions and opaque structs only) -------------------
+ * The MCMC learner reports pred_sum_all / num_iter, the mean over its draws of the per-draw predictions
+ * (fm_learn_mcmc_simultaneous.h:152-186, 238-245; fm_learn_mcmc.h:355-381); no reference counterpart
+ * keeps the draws. A chain collector keeps S draws of a sampling MCMC context in device memory,
+ * feature-major with the draws of a feature adjacent (cw [j*S + s], cv [(j*S + s)*k + f], and w0 [s],
+ * alpha [s] beside them), and turns them into a model of kind VBFM_MODEL_MCMC_CHAIN or into its file.
+ *
+ * vbfm_score / vbfm_score_device of a chain model (signatures and options as for every kind). For draw
+ * s, in the order added, yhat_s(r) is exactly -- bit for bit: the same expressions, summation order and
+ * skip of unknown ids -- what vbfm_score returns with clip = 0 for a MCMC_DRAW model holding draw s under
+ * the same order, and
+ *     p_s = clip(yhat_s, min_target, max_target)   regression, clip = 1
+ *     p_s = Phi(yhat_s)                            task c, clip = 1 (the learner's link)
+ *     p_s = yhat_s                                 clip = 0
+ *     sum = 0;  for s = 0 .. S-1: sum = sum + p_s;                      mean[r] = sum / S
+ *        (clip = 1: then min / max to [min_target, max_target], task c [0, 1], as vbfm_mcmc_get_test_pred)
+ *     m = 0; M2 = 0;  for s = 0 .. S-1: d = p_s - m;  m = m + d / (s + 1);  M2 = M2 + d * (p_s - m)
+ *                                                                       var[r] = M2 / S
+ * both loops in draw order, every operation rounded on its own (no contraction), so a plain float64
+ * restatement reproduces mean and var bit for bit from the per-draw scores, whatever the chunk size and
+ * the launch geometry. var is 0 for S = 1. With every iteration of a run kept, scoring the attached
+ * test rows reproduces vbfm_mcmc_get_test_pred bit for bit. The predictive variance of y in regression
+ * is var + mean_s(1 / alpha_s); the addition is the caller's (vbfm_model_draw_scalars has the alphas).
+ * vbfm_candidates_create / vbfm_recommend refuse a chain model.
+ *
+ * vbfm_chain_create: capacity draws of ctx's shape on ctx's device; only a sampling MCMC context
+ * (vbfm_mcmc_config::do_sample = 1) is accepted -- ALS is deterministic, a chain of it is one point.
+ * The bytes needed, capacity * D * (k + 1) * 8 plus the scalars, are checked against the device's free
+ * memory before anything is allocated; the refusal names both figures. vbfm_chain_add copies the
+ * context's fm.w0 / fm.w / fm.v and alpha as they are now into the next slot (one kernel on the
+ * context's stream); it is refused beyond the capacity and from a context of another (D, k, k0, k1,
+ * task). With several ranks the parameters are replicated: every rank may collect, vbfm_chain_save
+ * writes on rank 0 only and returns 0 on the others, as vbfm_model_save does; it takes no further
+ * device memory that grows with the draws (a full collector is read as it is, a partly filled one
+ * through a 64 MiB piece), only host memory for the payload. vbfm_model_from_chain copies the draws
+ * collected so far device to device into a model that does not depend on the collector afterwards:
+ * a SECOND copy of them, n * D * (k + 1) * 8 bytes more, checked against the free memory before it is
+ * allocated and refused with both figures -- a collector of more than half the free memory is saved,
+ * destroyed and loaded instead. Failures of a call that has a chain are in vbfm_chain_last_error(ch), those
+ * without in vbfm_last_error(NULL). */
+typedef struct vbfm_chain vbfm_chain;
+int vbfm_chain_create(vbfm_chain **out, vbfm_ctx *ctx, uint32_t capacity);
+int vbfm_chain_add(vbfm_chain *ch, vbfm_ctx *ctx);
+int vbfm_chain_count(const vbfm_chain *ch, uint32_t *n);
+int vbfm_chain_save(vbfm_chain *ch, const char *path, uint32_t iter);
+int vbfm_model_from_chain(vbfm_model **out, const vbfm_chain *ch);
+void vbfm_chain_destroy(vbfm_chain *ch);
+const char *vbfm_chain_last_error(const vbfm_chain *ch);
+
 /* ---- candidate sets and recommendation (additive to ABI 4: new functions and structs only) ----
  * No reference counterpart. The best topn of M candidate rows for each of B context rows, a pair
  * (c, j) valued as the model's mean of ONE row that holds c's entries and j's entries -- without
@@ -626,7 +702,8 @@ int vbfm_score_device(vbfm_model *m, vbfm_ctx *ctx, int32_t which, const vbfm_sc
  * order) and Q_r[f] the per-factor sum of row r (entries in ascending id, as vbfm_score orders them):
  *     dot = 0;  for f = 0 .. k - 1:  dot = fma(Q_c[f], Q_j[f], dot)
  *     raw(c, j) = (base_c + base_j - (k0 ? w0 : 0)) + dot          (w0 = mu_0_dash for the VB kinds)
- * VB kinds use the means, ALS / MCMC the point values (MCMC_DRAW: the last draw). Every pair is
+ * VB kinds use the means, ALS / MCMC the point values (MCMC_DRAW: that draw; a MCMC_CHAIN model is
+ * refused). Every pair is
  * computed by exactly this expression and the ranking is a total order -- larger raw first, equal raw
  * by smaller candidate index -- so idx, score and count are bit-identical whatever the chunk size and
  * the launch geometry. A pair whose raw is not finite is never returned (nonfinite_pairs counts them).

@@ -20,13 +20,15 @@
 extern "C" const char *vbfm_host_last_error(void);
 extern "C" void vbfm_host_set_error(const char *msg);
 // model files with the payload as the library stores it (vbfm_host.cpp): the w table, then the v
-// table [j*k + f]; {mu, sigma} pairs for the VB kinds, plain values for ALS / MCMC
-extern "C" int vbfm_host_model_write_raw(const char *path, const vbfm_model_info *info, int32_t task,
-                                         const double *w_tab, const double *v_tab);
+// table [j*k + f]; {mu, sigma} pairs for the VB kinds, plain values for ALS / MCMC; a chain of S
+// draws: its 2 * S scalars {w0, alpha} (scal), cw [j*S + s], cv [(j*S + s)*k + f] (S = 1, scal unused
+// for every other kind)
+extern "C" int vbfm_host_model_write_raw(const char *path, const vbfm_model_info *info, int32_t task, uint32_t S,
+                                         const double *scal, const double *w_tab, const double *v_tab);
 // alloc provides the tables once the file has proved sound (magic, sizes, checksum)
-extern "C" int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info, int32_t *task,
-                                        int (*alloc)(void *user, const vbfm_model_info *info, double **w_tab,
-                                                     double **v_tab),
+extern "C" int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info, int32_t *task, uint32_t *draws,
+                                        int (*alloc)(void *user, const vbfm_model_info *info, uint32_t S, double **scal,
+                                                     double **w_tab, double **v_tab),
                                         void *user);
 
 struct McState;   // vbfm_mcmc_capi.hip

@@ -7,7 +7,9 @@
 //                           a private copy of that generator (vbfm_rng.h).
 //   * vbfm_model_*_host /   model files (no reference counterpart): the parameters a prediction reads
 //     vbfm_model_file_info  behind a checked header; the device side (vbfm_score.hip) reads and writes
-//                           them through vbfm_host_model_{read,write}_raw.
+//                           them through vbfm_host_model_{read,write}_raw. A chain of S draws
+//                           (vbfm_model_write_host_chain / _read_host_draw / _file_draws) is one such
+//                           file with a header extension and a format version of its own.
 // Plain C++; built with -ffp-contract=off like the reference's x86-64 build (no FMA).
 #include "../../include/vbfm.h"
 #include "vbfm_rng.h"
@@ -366,7 +368,7 @@ int write_sparse(const std::string &fn, uint32_t nrows, uint32_t ncols, uint64_t
 // ---- model files (include/vbfm.h "model files and scoring") --------------------------------------
 struct ModelHeader {
 	char magic[8];            // "VBFMMD01"
-	uint32_t version;         // 1; 3 for a file whose task is not regression
+	uint32_t version;         // 1; 3 for a file whose task is not regression; 4 for a chain (ChainExt follows)
 	int32_t kind, k0, k1, k;
 	uint32_t D;
 	float min_target, max_target;
@@ -382,6 +384,16 @@ constexpr char MODEL_MAGIC[8] = {'V', 'B', 'F', 'M', 'M', 'D', '0', '1'};
 // Regression files stay version 1, byte for byte. The later version is 3: version 2 was never
 // written and stays refused (the model tests use it as their example of a future version).
 constexpr uint32_t MODEL_VERSION = 1, MODEL_VERSION_TASK = 3;
+// A chain of S draws (VBFM_MODEL_MCMC_CHAIN) is version 4, of either task: an earlier library refuses
+// it rather than reading the first D * (k + 1) doubles as one draw. Its header is the 88 bytes above
+// plus ChainExt; s0 / alpha hold the last draw's w0 / alpha. Payload: the S {w0, alpha} pairs, then
+// cw [j*S + s], then cv [(j*S + s)*k + f] -- the tables as the device keeps them.
+constexpr uint32_t MODEL_VERSION_CHAIN = 4;
+struct ChainExt {
+	uint32_t draws;           // S >= 1
+	uint32_t reserved;        // 0
+};
+static_assert(sizeof(ChainExt) == 8, "chain header extension layout");
 constexpr size_t MODEL_BUF = 1 << 15;   // doubles per I/O piece (256 KiB): the only buffer of both passes
 
 // 64-bit checksum over the payload's 8-byte words in file order (the payload is doubles only)
@@ -398,16 +410,22 @@ struct Sum64 {
 };
 
 bool model_vb(int32_t kind) { return kind == VBFM_MODEL_VB || kind == VBFM_MODEL_VB_ONLINE; }
+bool model_chain(int32_t kind) { return kind == VBFM_MODEL_MCMC_CHAIN; }
+bool model_point(int32_t kind) { return kind == VBFM_MODEL_ALS || kind == VBFM_MODEL_MCMC_DRAW || model_chain(kind); }
 
-// doubles of the w table and of the v table; false when D * (k + 1) * entry size overflows
-bool model_sizes(int32_t kind, int32_t k, uint32_t D, uint64_t *nw, uint64_t *nv, uint64_t *bytes)
+// doubles of the scalars in front (a chain's S {w0, alpha} pairs; 0 otherwise), of the w table and of
+// the v table, S = 1 for every kind but a chain; false when S * D * (k + 1) * entry size overflows
+bool model_sizes(int32_t kind, int32_t k, uint32_t D, uint32_t S, uint64_t *ns, uint64_t *nw, uint64_t *nv, uint64_t *bytes)
 {
-	const uint64_t per = model_vb(kind) ? 2 : 1;
+	const uint64_t per = model_vb(kind) ? 2 : (model_chain(kind) ? (uint64_t)S : 1);
+	*ns = model_chain(kind) ? 2 * (uint64_t)S : 0;
 	*nw = (uint64_t)D * per;
 	uint64_t kd;
 	if (__builtin_mul_overflow((uint64_t)D, (uint64_t)k, &kd) || __builtin_mul_overflow(kd, per, nv)) return false;
 	uint64_t n;
-	if (__builtin_add_overflow(*nw, *nv, &n) || __builtin_mul_overflow(n, (uint64_t)8, bytes)) return false;
+	if (__builtin_add_overflow(*nw, *nv, &n) || __builtin_add_overflow(n, *ns, &n) ||
+	    __builtin_mul_overflow(n, (uint64_t)8, bytes))
+		return false;
 	return true;
 }
 
@@ -416,7 +434,7 @@ ModelHeader model_header(const vbfm_model_info &in, int32_t task)
 	ModelHeader h;
 	memset(&h, 0, sizeof(h));
 	memcpy(h.magic, MODEL_MAGIC, 8);
-	h.version = task == VBFM_TASK_REGRESSION ? MODEL_VERSION : MODEL_VERSION_TASK;
+	h.version = model_chain(in.kind) ? MODEL_VERSION_CHAIN : task == VBFM_TASK_REGRESSION ? MODEL_VERSION : MODEL_VERSION_TASK;
 	h.task = (uint32_t)task;
 	h.kind = in.kind; h.k0 = in.k0 != 0; h.k1 = in.k1 != 0; h.k = in.num_factor;
 	h.D = in.num_attribute;
@@ -445,30 +463,33 @@ struct FileCloser {
 };
 
 // header + payload to <path>.tmp, fsync, rename (as checkpoints are written); get(i) is the i-th
-// double of the payload
-template <class Get> int model_write(const char *path, const vbfm_model_info *info, int32_t task, Get get)
+// double of the payload; S: a chain's draws (1 for every other kind)
+template <class Get> int model_write(const char *path, const vbfm_model_info *info, int32_t task, uint32_t S, Get get)
 {
 	if (!path || !info) { g_host_err = "model file: null argument"; return -1; }
 	if (task != VBFM_TASK_REGRESSION && task != VBFM_TASK_CLASSIFICATION) { g_host_err = "model file: unknown task"; return -1; }
-	if (task == VBFM_TASK_CLASSIFICATION && info->kind != VBFM_MODEL_ALS && info->kind != VBFM_MODEL_MCMC_DRAW) {
+	if (task == VBFM_TASK_CLASSIFICATION && !model_point(info->kind)) {
 		g_host_err = "model file: task c is provided by the ALS / MCMC kinds only";
 		return -1;
 	}
-	if (info->kind < VBFM_MODEL_VB || info->kind > VBFM_MODEL_MCMC_DRAW) { g_host_err = "model file: unknown kind"; return -1; }
+	if (info->kind < VBFM_MODEL_VB || info->kind > VBFM_MODEL_MCMC_CHAIN) { g_host_err = "model file: unknown kind"; return -1; }
 	if (info->num_factor < 0) { g_host_err = "model file: negative number of factors"; return -1; }
+	const bool chain = model_chain(info->kind);
+	if (chain && S < 1) { g_host_err = "model file: a chain holds at least one draw"; return -1; }
 	ModelHeader h = model_header(*info, task);
-	uint64_t nw, nv;
-	if (!model_sizes(h.kind, h.k, h.D, &nw, &nv, &h.payload)) {
-		g_host_err = "model file: num_attribute * (num_factor + 1) * entry size overflows 64 bits";
+	uint64_t ns, nw, nv;
+	if (!model_sizes(h.kind, h.k, h.D, S, &ns, &nw, &nv, &h.payload)) {
+		g_host_err = "model file: draws * num_attribute * (num_factor + 1) * entry size overflows 64 bits";
 		return -1;
 	}
 	const std::string tmp = std::string(path) + ".tmp";
 	FileCloser fc{fopen(tmp.c_str(), "wb")};
 	if (!fc.f) { g_host_err = "cannot open model file " + tmp; return -1; }
-	bool ok = fwrite(&h, sizeof(h), 1, fc.f) == 1;
+	const ChainExt ext{S, 0u};
+	bool ok = fwrite(&h, sizeof(h), 1, fc.f) == 1 && (!chain || fwrite(&ext, sizeof(ext), 1, fc.f) == 1);
 	std::vector<double> buf(MODEL_BUF);
 	Sum64 sum;
-	const uint64_t n = nw + nv;
+	const uint64_t n = ns + nw + nv;
 	for (uint64_t o = 0; ok && o < n; o += MODEL_BUF) {
 		const size_t m = (size_t)std::min<uint64_t>(MODEL_BUF, n - o);
 		for (size_t i = 0; i < m; i++) buf[i] = get(o + i);
@@ -485,10 +506,11 @@ template <class Get> int model_write(const char *path, const vbfm_model_info *in
 	return 0;
 }
 
-// Validate the whole file -- magic, version, kind, sizes without overflow, header sizes == file size,
-// checksum -- reading through one MODEL_BUF piece; then, with put, a second pass hands every double
-// of the payload to put(i, value). Nothing that grows with the file is allocated here.
-template <class Put> int model_read(const char *path, ModelHeader *hout, Put put, bool want)
+// Validate the whole file -- magic, version, kind, a chain's draw count, sizes without overflow,
+// header sizes == file size, checksum -- reading through one MODEL_BUF piece; then, with put, a
+// second pass hands every double of the payload to put(i, value). Nothing that grows with the file
+// is allocated here. *sout: a chain's draws (1 for every other kind).
+template <class Put> int model_read(const char *path, ModelHeader *hout, uint32_t *sout, Put put, bool want)
 {
 	if (!path) { g_host_err = "model file: null path"; return -1; }
 	const std::string p(path);
@@ -504,9 +526,10 @@ template <class Put> int model_read(const char *path, ModelHeader *hout, Put put
 		return -1;
 	}
 	if (memcmp(h.magic, MODEL_MAGIC, 8) != 0) { g_host_err = "not a libvbfm model file (bad magic): " + p; return -1; }
-	if (h.version != MODEL_VERSION && h.version != MODEL_VERSION_TASK) {
+	if (h.version != MODEL_VERSION && h.version != MODEL_VERSION_TASK && h.version != MODEL_VERSION_CHAIN) {
 		g_host_err = "model file of format version " + std::to_string(h.version) + ", this library reads version " +
-		             std::to_string(MODEL_VERSION) + " (and " + std::to_string(MODEL_VERSION_TASK) + ", a model of task c): " + p;
+		             std::to_string(MODEL_VERSION) + " (and " + std::to_string(MODEL_VERSION_TASK) + ", a model of task c, and " +
+		             std::to_string(MODEL_VERSION_CHAIN) + ", a chain of draws): " + p;
 		return -1;
 	}
 	if (h.version == MODEL_VERSION) h.task = VBFM_TASK_REGRESSION;   // the word was reserved
@@ -514,18 +537,41 @@ template <class Put> int model_read(const char *path, ModelHeader *hout, Put put
 		g_host_err = "model file of unknown task " + std::to_string(h.task) + ": " + p;
 		return -1;
 	}
-	if (h.kind < VBFM_MODEL_VB || h.kind > VBFM_MODEL_MCMC_DRAW) {
+	if (h.kind < VBFM_MODEL_VB || h.kind > VBFM_MODEL_MCMC_CHAIN) {
 		g_host_err = "model file of unknown kind " + std::to_string(h.kind) + ": " + p;
 		return -1;
 	}
-	if (h.task == VBFM_TASK_CLASSIFICATION && h.kind != VBFM_MODEL_ALS && h.kind != VBFM_MODEL_MCMC_DRAW) {
+	if (model_chain(h.kind) != (h.version == MODEL_VERSION_CHAIN)) {
+		g_host_err = "model file of kind " + std::to_string(h.kind) + " with format version " + std::to_string(h.version) +
+		             " (a chain of draws is kind " + std::to_string(VBFM_MODEL_MCMC_CHAIN) + " and version " +
+		             std::to_string(MODEL_VERSION_CHAIN) + "): " + p;
+		return -1;
+	}
+	if (h.task == VBFM_TASK_CLASSIFICATION && !model_point(h.kind)) {
 		g_host_err = "model file of task c with a kind other than ALS / MCMC: " + p;
 		return -1;
 	}
 	if (h.k < 0) { g_host_err = "model file with a negative number of factors: " + p; return -1; }
-	uint64_t nw, nv, bytes;
-	if (!model_sizes(h.kind, h.k, h.D, &nw, &nv, &bytes)) {
-		g_host_err = "model file header: num_attribute * (num_factor + 1) * entry size overflows 64 bits: " + p;
+	uint64_t hsize = sizeof(h);
+	uint32_t S = 1;
+	if (model_chain(h.kind)) {
+		ChainExt ext;
+		hsize += sizeof(ext);
+		if (fsize < hsize || fread(&ext, sizeof(ext), 1, fc.f) != 1) {
+			g_host_err = "model file truncated inside its header (" + std::to_string(fsize) + " of " + std::to_string(hsize) +
+			             " bytes): " + p;
+			return -1;
+		}
+		if (ext.draws < 1) { g_host_err = "model file of a chain with 0 draws: " + p; return -1; }
+		if (ext.reserved != 0) {   // the writer leaves it 0: a later meaning must not pass for none
+			g_host_err = "model file of a chain with a non-zero reserved header word (" + std::to_string(ext.reserved) + "): " + p;
+			return -1;
+		}
+		S = ext.draws;
+	}
+	uint64_t ns, nw, nv, bytes;
+	if (!model_sizes(h.kind, h.k, h.D, S, &ns, &nw, &nv, &bytes)) {
+		g_host_err = "model file header: draws * num_attribute * (num_factor + 1) * entry size overflows 64 bits: " + p;
 		return -1;
 	}
 	if (h.payload != bytes) {
@@ -533,20 +579,21 @@ template <class Put> int model_read(const char *path, ModelHeader *hout, Put put
 		             std::to_string(bytes) + "): " + p;
 		return -1;
 	}
-	if (fsize - sizeof(h) < bytes) {
-		g_host_err = "model file truncated inside its payload (" + std::to_string(fsize - sizeof(h)) + " of " +
+	if (fsize - hsize < bytes) {
+		g_host_err = "model file truncated inside its payload (" + std::to_string(fsize - hsize) + " of " +
 		             std::to_string(bytes) + " bytes): " + p;
 		return -1;
 	}
-	if (fsize - sizeof(h) > bytes) {
-		g_host_err = "model file has " + std::to_string(fsize - sizeof(h) - bytes) + " trailing bytes: " + p;
+	if (fsize - hsize > bytes) {
+		g_host_err = "model file has " + std::to_string(fsize - hsize - bytes) + " trailing bytes: " + p;
 		return -1;
 	}
-	if (hout) *hout = h;   // (put may read it: the header is sound from here on)
+	if (hout) *hout = h;   // (put may read them: the header is sound from here on)
+	if (sout) *sout = S;
 	std::vector<double> buf(MODEL_BUF);
-	const uint64_t n = nw + nv;
+	const uint64_t n = ns + nw + nv;
 	for (int pass = 0; pass < (want ? 2 : 1); pass++) {
-		if (fseek(fc.f, (long)sizeof(h), SEEK_SET) != 0) { g_host_err = "cannot seek in model file " + p; return -1; }
+		if (fseek(fc.f, (long)hsize, SEEK_SET) != 0) { g_host_err = "cannot seek in model file " + p; return -1; }
 		Sum64 sum;
 		for (uint64_t o = 0; o < n; o += MODEL_BUF) {
 			const size_t m = (size_t)std::min<uint64_t>(MODEL_BUF, n - o);
@@ -580,15 +627,24 @@ extern "C" {
 int vbfm_model_file_info(const char *path, vbfm_model_info *out)
 {
 	ModelHeader h;
-	if (model_read(path, &h, [](uint64_t, double) {}, false)) return -1;
+	if (model_read(path, &h, nullptr, [](uint64_t, double) {}, false)) return -1;
 	if (out) *out = model_info(h);
+	return 0;
+}
+
+int vbfm_model_file_draws(const char *path, uint32_t *draws)
+{
+	ModelHeader h;
+	uint32_t S = 1;
+	if (model_read(path, &h, &S, [](uint64_t, double) {}, false)) return -1;
+	if (draws) *draws = S;
 	return 0;
 }
 
 int vbfm_model_file_task(const char *path, int32_t *task)
 {
 	ModelHeader h;
-	if (model_read(path, &h, [](uint64_t, double) {}, false)) return -1;
+	if (model_read(path, &h, nullptr, [](uint64_t, double) {}, false)) return -1;
 	if (task) *task = (int32_t)h.task;
 	return 0;
 }
@@ -603,6 +659,10 @@ int vbfm_model_write_host_task(const char *path, const vbfm_model_info *info, co
                                const vbfm_mcmc_params *mc, int32_t task)
 {
 	if (!path || !info) { g_host_err = "vbfm_model_write_host: null argument"; return -1; }
+	if (model_chain(info->kind)) {
+		g_host_err = "vbfm_model_write_host: a chain of draws is written by vbfm_model_write_host_chain";
+		return -1;
+	}
 	const bool isvb = model_vb(info->kind);
 	const uint64_t D = info->num_attribute, k = (uint64_t)std::max(info->num_factor, 0);
 	const double *a[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -613,9 +673,33 @@ int vbfm_model_write_host_task(const char *path, const vbfm_model_info *info, co
 		                  : "vbfm_model_write_host: an ALS / MCMC kind needs w and v (vbfm_mcmc_params)";
 		return -1;
 	}
-	return model_write(path, info, task, [&](uint64_t i) {
+	return model_write(path, info, task, 1, [&](uint64_t i) {
 		const ModelSlot s = model_slot(isvb, D, k, i);
 		return a[s.arr][s.idx];
+	});
+}
+
+int vbfm_model_write_host_chain(const char *path, const vbfm_model_info *info, int32_t task, uint32_t S,
+                                const vbfm_mcmc_params *draws)
+{
+	if (!path || !info) { g_host_err = "vbfm_model_write_host_chain: null argument"; return -1; }
+	if (!model_chain(info->kind)) { g_host_err = "vbfm_model_write_host_chain: the kind must be VBFM_MODEL_MCMC_CHAIN"; return -1; }
+	if (S < 1 || !draws) { g_host_err = "vbfm_model_write_host_chain: a chain holds at least one draw"; return -1; }
+	const uint64_t D = info->num_attribute, k = (uint64_t)std::max(info->num_factor, 0);
+	for (uint32_t s = 0; s < S; s++)
+		if ((D && !draws[s].w) || (D && k && !draws[s].v)) {
+			g_host_err = "vbfm_model_write_host_chain: draw " + std::to_string(s) + " needs w and v (vbfm_mcmc_params)";
+			return -1;
+		}
+	vbfm_model_info in = *info;   // the header's scalars are the last draw's
+	in.w0_or_mu0 = draws[S - 1].w0;
+	in.alpha = draws[S - 1].alpha;
+	const uint64_t ns = 2 * (uint64_t)S, nw = D * S;
+	return model_write(path, &in, task, S, [&](uint64_t i) {
+		if (i < ns) return (i & 1) ? draws[i >> 1].alpha : draws[i >> 1].w0;
+		if (i < ns + nw) return draws[(i - ns) % S].w[(i - ns) / S];            // cw [j*S + s]
+		const uint64_t q = i - ns - nw, f = q % k, t = q / k;                      // cv [(j*S + s)*k + f]
+		return draws[t % S].v[f * D + t / S];
 	});
 }
 
@@ -626,54 +710,105 @@ int vbfm_model_read_host(const char *path, vbfm_model_info *info, vbfm_params *v
 	if (vb) { avb[0] = vb->mu_w; avb[1] = vb->sigma_w; avb[2] = vb->mu_v; avb[3] = vb->sigma_v; }
 	if (mc) { amc[0] = mc->w; amc[2] = mc->v; }
 	// one call: the first pass proves the whole file sound before the second stores a value
-	if (model_read(path, &h, [&](uint64_t i, double v) {
+	if (model_read(path, &h, nullptr, [&](uint64_t i, double v) {
+		    if (model_chain(h.kind)) return;   // refused below
 		    const bool isvb = model_vb(h.kind);
 		    const ModelSlot s = model_slot(isvb, h.D, (uint64_t)h.k, i);
 		    double *a = (isvb ? avb : amc)[s.arr];
 		    if (a) a[s.idx] = v;
 	    }, vb || mc))
 		return -1;
+	if (model_chain(h.kind)) {
+		g_host_err = "model file holds a chain of draws: vbfm_model_read_host_draw reads one of them (vbfm_model_file_draws "
+		             "counts them): " + std::string(path);
+		return -1;
+	}
 	if (model_vb(h.kind) && vb) { vb->mu_0_dash = h.s0; vb->sigma_0_dash = h.s1; vb->alpha = h.alpha; }
 	if (!model_vb(h.kind) && mc) { mc->w0 = h.s0; mc->alpha = h.alpha; }
 	if (info) *info = model_info(h);
 	return 0;
 }
 
-// the payload as the library stores it (internal: vbfm_score.hip): w_tab then v_tab, pairs for the
-// VB kinds
-int vbfm_host_model_write_raw(const char *path, const vbfm_model_info *info, int32_t task, const double *w_tab,
-                              const double *v_tab)
+int vbfm_model_read_host_draw(const char *path, uint32_t s, vbfm_model_info *info, vbfm_mcmc_params *mc)
 {
-	if (!info) { g_host_err = "model file: null argument"; return -1; }
-	const uint64_t nw = (uint64_t)info->num_attribute * (model_vb(info->kind) ? 2 : 1);
-	return model_write(path, info, task, [&](uint64_t i) { return i < nw ? w_tab[i] : v_tab[i - nw]; });
+	ModelHeader h;
+	uint32_t S = 1;
+	double w0 = 0.0, alpha = 0.0;
+	if (model_read(path, &h, &S, [&](uint64_t i, double v) {
+		    if (!model_chain(h.kind) || s >= S) return;   // refused below
+		    const uint64_t ns = 2 * (uint64_t)S, nw = (uint64_t)h.D * S, k = (uint64_t)h.k;
+		    if (i < ns) {
+			    if ((i >> 1) == s) ((i & 1) ? alpha : w0) = v;
+		    } else if (i < ns + nw) {
+			    if ((i - ns) % S == s && mc->w) mc->w[(i - ns) / S] = v;
+		    } else {
+			    const uint64_t q = i - ns - nw, f = q % k, t = q / k;
+			    if (t % S == s && mc->v) mc->v[f * h.D + t / S] = v;
+		    }
+	    }, mc != nullptr))
+		return -1;
+	if (!model_chain(h.kind)) {
+		g_host_err = "model file holds one set of parameters, not a chain of draws (vbfm_model_read_host reads it): " +
+		             std::string(path);
+		return -1;
+	}
+	if (s >= S) {
+		g_host_err = "draw " + std::to_string(s) + " of a chain of " + std::to_string(S) + " draws: " + std::string(path);
+		return -1;
+	}
+	if (mc) { mc->w0 = w0; mc->alpha = alpha; }
+	if (info) *info = model_info(h);
+	return 0;
 }
 
-// ... and read back: alloc(user, info, &w_tab, &v_tab) is called once the whole file has proved
-// sound (never for a refused file), then the tables are filled
-int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info, int32_t *task,
-                             int (*alloc)(void *user, const vbfm_model_info *info, double **w_tab, double **v_tab),
+// the payload as the library stores it (internal: vbfm_score.hip, vbfm_chain.hip): a chain's S
+// {w0, alpha} pairs (scal; S = 1 and no scalars for every other kind), then w_tab, then v_tab --
+// pairs for the VB kinds, the interleaved cw / cv for a chain
+int vbfm_host_model_write_raw(const char *path, const vbfm_model_info *info, int32_t task, uint32_t S, const double *scal,
+                              const double *w_tab, const double *v_tab)
+{
+	if (!info) { g_host_err = "model file: null argument"; return -1; }
+	const bool chain = model_chain(info->kind);
+	const uint64_t ns = chain ? 2 * (uint64_t)S : 0;
+	const uint64_t nw = (uint64_t)info->num_attribute * (model_vb(info->kind) ? 2 : (chain ? (uint64_t)S : 1));
+	return model_write(path, info, task, S, [&](uint64_t i) {
+		return i < ns ? scal[i] : i < ns + nw ? w_tab[i - ns] : v_tab[i - ns - nw];
+	});
+}
+
+// ... and read back: alloc(user, info, S, &scal, &w_tab, &v_tab) is called once the whole file has
+// proved sound (never for a refused file), then the tables are filled (scal: 2 * S doubles of a
+// chain, not touched otherwise)
+int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info, int32_t *task, uint32_t *draws,
+                             int (*alloc)(void *user, const vbfm_model_info *info, uint32_t S, double **scal,
+                                          double **w_tab, double **v_tab),
                              void *user)
 {
 	ModelHeader h;
-	double *w_tab = nullptr, *v_tab = nullptr;
+	uint32_t S = 1;
+	double *scal = nullptr, *w_tab = nullptr, *v_tab = nullptr;
 	bool ready = false, failed = false;
 	auto prepare = [&] {
 		const vbfm_model_info in = model_info(h);
-		failed = alloc(user, &in, &w_tab, &v_tab) != 0;
+		failed = alloc(user, &in, S, &scal, &w_tab, &v_tab) != 0;
 		ready = true;
 	};
-	if (model_read(path, &h, [&](uint64_t i, double v) {
+	if (model_read(path, &h, &S, [&](uint64_t i, double v) {
 		    if (!ready) prepare();
 		    if (failed) return;
-		    const uint64_t nw = (uint64_t)h.D * (model_vb(h.kind) ? 2 : 1);
-		    if (i < nw) w_tab[i] = v; else v_tab[i - nw] = v;
+		    const bool chain = model_chain(h.kind);
+		    const uint64_t ns = chain ? 2 * (uint64_t)S : 0;
+		    const uint64_t nw = (uint64_t)h.D * (model_vb(h.kind) ? 2 : (chain ? (uint64_t)S : 1));
+		    if (i < ns) scal[i] = v;
+		    else if (i < ns + nw) w_tab[i - ns] = v;
+		    else v_tab[i - ns - nw] = v;
 	    }, true))
 		return -1;
 	if (!ready) prepare();   // an empty payload
 	if (failed) { g_host_err = "model file: out of memory for the tables: " + std::string(path); return -1; }
 	if (info) *info = model_info(h);
 	if (task) *task = (int32_t)h.task;
+	if (draws) *draws = S;
 	return 0;
 }
 

@@ -421,6 +421,9 @@ int vbfm_candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr 
 	if (!m) return mfail(nullptr, "vbfm_candidates_create: null model");
 	if (!out || !rows) return mfail(m, "vbfm_candidates_create: null argument");
 	*out = nullptr;
+	if (m->info.kind == VBFM_MODEL_MCMC_CHAIN)
+		return mfail(m, "vbfm_candidates_create: a chain of draws (VBFM_MODEL_MCMC_CHAIN) is scored, not ranked: "
+		                "recommendation takes a model of one set of parameters");
 	vbfm_candidates *c = nullptr;
 	const int rc = mguarded(m, [&] {
 		if (unknown_ids != 0 && unknown_ids != 1)
@@ -467,6 +470,9 @@ int vbfm_recommend(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *con
 {
 	if (!m) return mfail(nullptr, "vbfm_recommend: null model");
 	if (!cs || !contexts || !opts) return mfail(m, "vbfm_recommend: null argument");
+	if (m->info.kind == VBFM_MODEL_MCMC_CHAIN)
+		return mfail(m, "vbfm_recommend: a chain of draws (VBFM_MODEL_MCMC_CHAIN) is scored, not ranked: "
+		                "recommendation takes a model of one set of parameters");
 	return mguarded(m, [&] {
 		const double t_begin = wall_s();
 		const vbfm_recommend_opts o = *opts;

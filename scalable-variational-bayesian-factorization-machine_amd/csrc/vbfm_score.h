@@ -1,10 +1,12 @@
 // vbfm_score.h -- what the two users of a model handle share: vbfm_score.hip (models and per-row
 // scoring) and vbfm_recommend.hip (candidate sets and top-N ranking). The handle itself, the
 // lane-group scoring kernel k_score with its unknown-id flags, and the host staging of caller rows
-// in chunks. Internal to libvbfm; not part of the ABI.
+// in chunks; and what vbfm_chain.hip (chains of draws: the collector and the chain scoring kernels)
+// shares with vbfm_score.hip. Internal to libvbfm; not part of the ABI.
 #pragma once
 #include "vbfm_ctx.h"
 #include "vbfm_math.h"
+#include "vbfm_class_math.h"
 
 #include <algorithm>
 
@@ -52,6 +54,45 @@ DEVI void flag_unknown(const ScoreArgs &a, uint32_t r, uint32_t id)
 {
 	atomicAdd(&a.flags->skipped, 1ull);
 	atomicMin(&a.flags->first, ((unsigned long long)(a.row0 + r) << 32) | (unsigned long long)id);
+}
+
+// Exact order: the mean of the row whose entries are a.ent[b .. en), k_predict_e's body expression by
+// expression (factor-major sums, each over the row's entries in order), entries with an unknown id
+// left out; v(id, f) / w(id) read the tables (one model's, or one draw's of a chain)
+template <class V, class W>
+DEVI double exact_mean(const ScoreArgs &a, uint64_t b, uint64_t en, V v, W w, double w0)
+{
+	const int k = a.k;
+	const uint32_t D = a.D;
+	double e = 0.0;
+	for (int f = 0; f < k; ++f) {                          // (1) fm_learn_vb.h:93-133
+		double q = 0.0;
+		for (uint64_t p = b; p < en; ++p) {
+			const uint2 ent = a.ent[p];
+			if (ent.x >= D) continue;
+			q += v(ent.x, f) * ent_x(ent);
+		}
+		e += 0.5 * q * q;
+	}
+	double q = 0.0;
+	for (int f = 0; f < k; ++f) {                          // (2) :136-163
+		for (uint64_t p = b; p < en; ++p) {
+			const uint2 ent = a.ent[p];
+			if (ent.x >= D) continue;
+			const double m = v(ent.x, f);
+			const float x = ent_x(ent);
+			q -= 0.5 * m * m * x * x;
+		}
+	}
+	if (a.k1)                                              // (3) :166-188
+		for (uint64_t p = b; p < en; ++p) {
+			const uint2 ent = a.ent[p];
+			if (ent.x >= D) continue;
+			q += w(ent.x) * ent_x(ent);
+		}
+	e = e + q;                                             // merge :190-202
+	if (a.k0) e += w0;
+	return e;
 }
 
 // entries whose factors a group loads before accumulating them in entry order (as the wave kernels)
@@ -234,12 +275,17 @@ enum { SEV_C0, SEV_C1, SEV_K0, SEV_K1, SEV_DONE, SEV_N };
 }  // namespace vbs
 
 struct vbfm_model {
-	std::string err;
+	mutable std::string err;                      // (mutable: the getters that take a const model report here too)
 	int dev = 0;
 	vbfm_model_info info = {};
 	int32_t task = VBFM_TASK_REGRESSION;          // task c: clip = 1 scores are Phi(yhat), clip = 0 the raw yhat
 	double *mw = nullptr, *mv = nullptr;          // means: w [D], v [j*k + f] (ALS / MCMC: the values)
 	double2 *ms_w = nullptr, *ms_v = nullptr;     // VB kinds: the {mu, sigma} pairs
+	// VBFM_MODEL_MCMC_CHAIN: S draws, feature-major with the draws of a feature adjacent (mw / mv are
+	// not allocated): cw [j*S + s], cv [(j*S + s)*k + f], cw0 = w0 [s] then alpha [S + s]; the draws' scalars also on the host
+	uint32_t S = 1;
+	double *cw = nullptr, *cv = nullptr, *cw0 = nullptr;
+	std::vector<double> draw_w0, draw_alpha;
 	hipStream_t s = nullptr, s_copy = nullptr;    // kernels and results; the chunks' copies to the device
 	vbs::ScoreFlags *flags = nullptr;
 	// the staging of caller rows, kept between calls: two pinned host and two device buffers for the
@@ -348,6 +394,24 @@ inline double elapsed(hipEvent_t a, hipEvent_t b)
 	HIPCHK(hipEventElapsedTime(&ms, a, b));
 	return ms;
 }
+
+// ---- vbfm_score.hip ---------------------------------------------------------------------------
+void model_alloc(vbfm_model *m);   // streams, events, the flag word and the tables of m->info's shape (and m->S)
+void model_free(vbfm_model *m);
+
+// ---- vbfm_chain.hip ---------------------------------------------------------------------------
+// a chain model's scores of a.n rows (a.mean, a.var or NULL) on its interleaved tables: the mean over
+// the draws of link(yhat_s) and its spread (include/vbfm.h "chains of draws"). link: 0 none, 1 the
+// clip to [a.mn, a.mx], 2 Phi; fin: the mean is then clipped to [lo, hi]. a.clip is not read.
+struct ChainArgs {
+	ScoreArgs a;
+	const double *cw, *cv, *w0;
+	uint32_t S;
+	uint32_t gpr;     // lane groups per row (k_score_chain): min(64 / G, the power of two >= S)
+	int link, fin;
+	double lo, hi;
+};
+hipError_t launch_score_chain(const vbfm_model *m, const ScoreArgs &a, int clip, bool group, hipStream_t s);
 
 struct ChunkPlan { uint32_t r0, r1; };
 

@@ -9,7 +9,8 @@
 // and k_score (lane groups, the structure of k_predict_e_wave / k_predict_et_wave). Both skip an
 // entry whose id is not in the model and report it (ScoreFlags); the training path's kernels
 // (vbfm_kernels.hip) trust their ids and stay as they are. The handle, k_score and the chunk staging
-// are in vbfm_score.h, shared with vbfm_recommend.hip.
+// are in vbfm_score.h, shared with vbfm_recommend.hip. A model of kind VBFM_MODEL_MCMC_CHAIN (S draws
+// in interleaved tables) is loaded here and scored by vbfm_chain.hip's kernels (score_rows).
 #include "vbfm_score.h"
 
 using namespace vbs;
@@ -28,34 +29,8 @@ __global__ __launch_bounds__(256) void k_score_exact(const ScoreArgs a)
 	const uint32_t D = a.D;
 	for (uint64_t p = b; p < en; ++p)
 		if (a.ent[p].x >= D) flag_unknown(a, r, a.ent[p].x);
-	double e = 0.0;
-	for (int f = 0; f < k; ++f) {                          // (1) fm_learn_vb.h:93-133
-		double q = 0.0;
-		for (uint64_t p = b; p < en; ++p) {
-			const uint2 ent = a.ent[p];
-			if (ent.x >= D) continue;
-			q += a.mv[(size_t)ent.x * k + f] * ent_x(ent);
-		}
-		e += 0.5 * q * q;
-	}
-	double q = 0.0;
-	for (int f = 0; f < k; ++f) {                          // (2) :136-163
-		for (uint64_t p = b; p < en; ++p) {
-			const uint2 ent = a.ent[p];
-			if (ent.x >= D) continue;
-			const double v = a.mv[(size_t)ent.x * k + f];
-			const float x = ent_x(ent);
-			q -= 0.5 * v * v * x * x;
-		}
-	}
-	if (a.k1)                                              // (3) :166-188
-		for (uint64_t p = b; p < en; ++p) {
-			const uint2 ent = a.ent[p];
-			if (ent.x >= D) continue;
-			q += a.mw[ent.x] * ent_x(ent);
-		}
-	e = e + q;                                             // merge :190-202
-	if (a.k0) e += a.mu0;
+	const double e = exact_mean(
+	    a, b, en, [&](uint32_t j, int f) { return a.mv[(size_t)j * k + f]; }, [&](uint32_t j) { return a.mw[j]; }, a.mu0);
 	a.mean[r] = a.clip ? clip(e, a.mn, a.mx) : e;
 	if constexpr (VAR) {
 		double t = 0.0;
@@ -120,6 +95,11 @@ hipError_t launch_score(const ScoreArgs &a, bool group, bool var, hipStream_t s)
 }
 
 bool kind_vb(int32_t kind) { return kind == VBFM_MODEL_VB || kind == VBFM_MODEL_VB_ONLINE; }
+bool kind_chain(int32_t kind) { return kind == VBFM_MODEL_MCMC_CHAIN; }
+
+}  // namespace
+
+namespace vbs {
 
 void model_free(vbfm_model *m)
 {
@@ -130,6 +110,7 @@ void model_free(vbfm_model *m)
 		for (hipEvent_t &e : sl.ev)
 			if (e) (void)hipEventDestroy(e);
 	dfree(m->mw); dfree(m->mv); dfree(m->ms_w); dfree(m->ms_v); dfree(m->flags);
+	dfree(m->cw); dfree(m->cv); dfree(m->cw0);
 	if (m->s) (void)hipStreamDestroy(m->s);
 	if (m->s_copy) (void)hipStreamDestroy(m->s_copy);
 	delete m;
@@ -145,6 +126,12 @@ void model_alloc(vbfm_model *m)
 		for (hipEvent_t &e : sl.ev) HIPCHK(hipEventCreate(&e));
 	m->flags = dalloc<ScoreFlags>(1);
 	const size_t D = m->info.num_attribute, kd = D * (size_t)m->info.num_factor;
+	if (kind_chain(m->info.kind)) {
+		m->cw = dalloc<double>(D * m->S);
+		m->cv = dalloc<double>(kd * m->S);
+		m->cw0 = dalloc<double>(2 * (size_t)m->S);   // w0 [s], then alpha [S + s]
+		return;
+	}
 	m->mw = dalloc<double>(D);
 	m->mv = dalloc<double>(kd);
 	if (kind_vb(m->info.kind)) {
@@ -152,6 +139,10 @@ void model_alloc(vbfm_model *m)
 		m->ms_v = dalloc<double2>(kd);
 	}
 }
+
+}  // namespace vbs
+
+namespace {
 
 void means_of(const double2 *ms, double *out, size_t n, hipStream_t s)
 {
@@ -203,15 +194,20 @@ void require_opts(const vbfm_model *m, const vbfm_score_opts &o, const double *m
 	if (!mean) throw std::string("vbfm_score: null mean array");
 	if (o.order < VBFM_ORDER_AUTO || o.order > VBFM_ORDER_GROUP) throw std::string("vbfm_score: unknown order");
 	if (o.unknown_ids != 0 && o.unknown_ids != 1) throw std::string("vbfm_score: unknown_ids is 0 (refuse) or 1 (skip)");
-	if (var && !m->info.has_variance)
+	if (var && !m->info.has_variance && !kind_chain(m->info.kind))
 		throw std::string("the model holds no variances (an ALS / MCMC kind): T_n cannot be scored");
 }
 
-// task c: the probability Phi(yhat) "as pred_this is" (fm_learn_mcmc_simultaneous.h:178-182) in place
-// of the clip, over the n means a score kernel just left on m->s
-void score_link(const vbfm_model *m, const vbfm_score_opts &o, double *mean, uint32_t n)
+// the kernels of one launch over a.n rows left on s: a chain model's average over its draws (link and
+// final clip inside), or the one-table forms followed by the link of task c
+void score_rows(const vbfm_model *m, const vbfm_score_opts &o, const ScoreArgs &a, bool group, hipStream_t s)
 {
-	if (m->task == VBFM_TASK_CLASSIFICATION && o.clip) HIPCHK(vbk::mc_class_link(mean, n, m->s));
+	if (kind_chain(m->info.kind)) {
+		HIPCHK(launch_score_chain(m, a, o.clip, group, s));
+		return;
+	}
+	HIPCHK(launch_score(a, group, a.var != nullptr, s));
+	if (m->task == VBFM_TASK_CLASSIFICATION && o.clip) HIPCHK(vbk::mc_class_link(a.mean, a.n, s));
 }
 
 // the context's rule (blocked_predict): the reference's order while nnz * k <= 5e7
@@ -241,6 +237,27 @@ int vbfm_model_task(const vbfm_model *m, int32_t *task)
 	return 0;
 }
 
+int vbfm_model_num_draws(const vbfm_model *m, uint32_t *draws)
+{
+	if (!m) return mfail(nullptr, "vbfm_model_num_draws: null model");
+	if (!draws) { m->err = "vbfm_model_num_draws: null argument"; return -1; }
+	*draws = m->S;
+	return 0;
+}
+
+int vbfm_model_draw_scalars(const vbfm_model *m, uint32_t s, double *w0, double *alpha)
+{
+	if (!m) return mfail(nullptr, "vbfm_model_draw_scalars: null model");
+	if (s >= m->S) {
+		m->err = "vbfm_model_draw_scalars: draw " + std::to_string(s) + " of a model of " + std::to_string(m->S) + " draw(s)";
+		return -1;
+	}
+	const bool chain = kind_chain(m->info.kind);
+	if (w0) *w0 = chain ? m->draw_w0[s] : m->info.w0_or_mu0;
+	if (alpha) *alpha = chain ? m->draw_alpha[s] : m->info.alpha;
+	return 0;
+}
+
 void vbfm_model_destroy(vbfm_model *m) { model_free(m); }
 
 int vbfm_model_from_ctx(vbfm_model **out, vbfm_ctx *c)
@@ -263,7 +280,8 @@ int vbfm_model_save(vbfm_ctx *c, const char *path, uint32_t iter)
 			std::vector<double> w(D * per), v(kd * per);
 			if (D) HIPCHK(hipMemcpy(w.data(), vb ? (const void *)m->ms_w : m->mw, D * per * 8, hipMemcpyDeviceToHost));
 			if (kd) HIPCHK(hipMemcpy(v.data(), vb ? (const void *)m->ms_v : m->mv, kd * per * 8, hipMemcpyDeviceToHost));
-			if (vbfm_host_model_write_raw(path, &m->info, m->task, w.data(), v.data()) != 0) throw std::string(vbfm_host_last_error());
+			if (vbfm_host_model_write_raw(path, &m->info, m->task, 1, nullptr, w.data(), v.data()) != 0)
+				throw std::string(vbfm_host_last_error());
 		} catch (...) {
 			model_free(m);
 			throw;
@@ -277,23 +295,27 @@ int vbfm_model_load(vbfm_model **out, const char *path, int32_t device)
 	if (!out || !path) return mfail(nullptr, "vbfm_model_load: null argument");
 	*out = nullptr;
 	// the file first (host only): a refused file allocates nothing and touches no device
-	struct Tabs { std::vector<double> w, v; } tabs;
+	struct Tabs { std::vector<double> scal, w, v; } tabs;
 	vbfm_model_info info;
-	auto alloc = [](void *user, const vbfm_model_info *in, double **w, double **v) -> int {
+	auto alloc = [](void *user, const vbfm_model_info *in, uint32_t S, double **scal, double **w, double **v) -> int {
 		Tabs &t = *(Tabs *)user;
-		const size_t per = in->has_variance ? 2 : 1, D = in->num_attribute;
+		const bool chain = kind_chain(in->kind);
+		const size_t per = in->has_variance ? 2 : (chain ? (size_t)S : 1), D = in->num_attribute;
 		try {
+			if (chain) t.scal.resize(2 * (size_t)S);
 			t.w.resize(D * per);
 			t.v.resize(D * (size_t)in->num_factor * per);
 		} catch (const std::bad_alloc &) {
 			return -1;
 		}
+		*scal = t.scal.data();
 		*w = t.w.data();
 		*v = t.v.data();
 		return 0;
 	};
 	int32_t task = VBFM_TASK_REGRESSION;
-	if (vbfm_host_model_read_raw(path, &info, &task, alloc, &tabs) != 0) return -1;
+	uint32_t S = 1;
+	if (vbfm_host_model_read_raw(path, &info, &task, &S, alloc, &tabs) != 0) return -1;
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return mfail(nullptr, "no HIP device available");
 	if (device < 0 || device >= ndev) return mfail(nullptr, "device ordinal out of range");
@@ -301,10 +323,19 @@ int vbfm_model_load(vbfm_model **out, const char *path, int32_t device)
 	m->dev = device;
 	m->info = info;
 	m->task = task;
+	m->S = S;
 	const int rc = mguarded(nullptr, [&] {
 		model_alloc(m);
 		const size_t D = info.num_attribute, kd = D * (size_t)info.num_factor;
-		if (m->ms_w) {
+		if (kind_chain(info.kind)) {
+			m->draw_w0.resize(S);
+			m->draw_alpha.resize(S);
+			for (uint32_t s = 0; s < S; s++) { m->draw_w0[s] = tabs.scal[2 * s]; m->draw_alpha[s] = tabs.scal[2 * s + 1]; }
+			HIPCHK(hipMemcpy(m->cw0, m->draw_w0.data(), (size_t)S * 8, hipMemcpyHostToDevice));
+			HIPCHK(hipMemcpy(m->cw0 + S, m->draw_alpha.data(), (size_t)S * 8, hipMemcpyHostToDevice));
+			if (D) HIPCHK(hipMemcpy(m->cw, tabs.w.data(), D * S * 8, hipMemcpyHostToDevice));
+			if (kd) HIPCHK(hipMemcpy(m->cv, tabs.v.data(), kd * S * 8, hipMemcpyHostToDevice));
+		} else if (m->ms_w) {
 			if (D) HIPCHK(hipMemcpy(m->ms_w, tabs.w.data(), D * 16, hipMemcpyHostToDevice));
 			if (kd) HIPCHK(hipMemcpy(m->ms_v, tabs.v.data(), kd * 16, hipMemcpyHostToDevice));
 			means_of(m->ms_w, m->mw, D, m->s);
@@ -368,8 +399,7 @@ int vbfm_score(vbfm_model *m, const vbfm_csr *rows, const vbfm_score_opts *opts,
 			a.n = nr;
 			a.row0 = r0;
 			HIPCHK(hipEventRecord(sl.ev[SEV_K0], m->s));
-			HIPCHK(launch_score(a, group, var != nullptr, m->s));
-			score_link(m, o, a.mean, nr);
+			score_rows(m, o, a, group, m->s);
 			HIPCHK(hipEventRecord(sl.ev[SEV_K1], m->s));
 			HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, (size_t)nr * (var ? 2 : 1) * 8, hipMemcpyDeviceToHost, m->s));
 			HIPCHK(hipEventRecord(sl.ev[SEV_DONE], m->s));
@@ -409,8 +439,7 @@ int vbfm_score_device(vbfm_model *m, vbfm_ctx *c, int32_t which, const vbfm_scor
 		a.n = d.n;
 		vbfm_model::Slot &sl = m->slot[0];
 		HIPCHK(hipEventRecord(sl.ev[SEV_K0], m->s));
-		HIPCHK(launch_score(a, group_order(m, o, d.nnz), var != nullptr, m->s));
-		score_link(m, o, a.mean, d.n);
+		score_rows(m, o, a, group_order(m, o, d.nnz), m->s);
 		HIPCHK(hipEventRecord(sl.ev[SEV_K1], m->s));
 		const ScoreFlags f = flags_read(m);
 		if (f.first != ~0ull && !o.unknown_ids) throw unknown_msg(m, f.first >> 32, (uint32_t)f.first);

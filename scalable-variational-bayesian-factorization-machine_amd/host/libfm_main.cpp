@@ -17,7 +17,10 @@
 //   * -save_model FILE (every method: the parameters alone, after the last iteration) and the
 //     predict-only mode -load_model FILE -test T -out P [-out_var V] (no -train; no reference
 //     counterpart: the reference predicts only the test set attached while training); with
-//     -candidates ITEMS -topn N [-exclude X] that mode ranks the rows of ITEMS for every row of T.
+//     -candidates ITEMS -topn N [-exclude X] that mode ranks the rows of ITEMS for every row of T;
+//   * -method mcmc -save_model FILE -chain B,T keeps the draws of iterations B, B + T, ... and writes
+//     them as one model whose -load_model scores are the chain average (what -out reports), -out_var
+//     the spread across the draws.
 //
 // Multi-GPU (-devices): the reference is one process on one core. Here this process parses the
 // flags and loads the data (host code only, no HIP call), then forks one rank process per GPU
@@ -66,6 +69,13 @@
 #pragma weak vbfm_candidates_count
 #pragma weak vbfm_candidates_destroy
 #pragma weak vbfm_recommend
+#pragma weak vbfm_chain_create
+#pragma weak vbfm_chain_add
+#pragma weak vbfm_chain_count
+#pragma weak vbfm_chain_save
+#pragma weak vbfm_chain_destroy
+#pragma weak vbfm_chain_last_error
+#pragma weak vbfm_model_num_draws
 
 namespace {
 
@@ -295,6 +305,18 @@ static void save_model(vbfm_ctx *ctx, const std::string &file, uint32_t iter)
 	check(vbfm_model_save(ctx, file.c_str(), iter), ctx);
 }
 
+static bool have_chain()
+{
+	return have_scorer() && vbfm_chain_create && vbfm_chain_add && vbfm_chain_count && vbfm_chain_save &&
+	       vbfm_chain_destroy && vbfm_chain_last_error;
+}
+
+// -chain B,T: iteration i (0-based) is kept iff i >= B and (i - B) % T == 0
+static uint32_t chain_kept(uint32_t num_iter, uint32_t burn, uint32_t thin)
+{
+	return num_iter > burn ? (num_iter - burn + thin - 1) / thin : 0;
+}
+
 // ---- ranks ------------------------------------------------------------------------------
 // The shared-memory page the forked ranks use: a process-shared barrier, rank 0's RCCL
 // unique id, one slot per rank for the host all-reduce, and the gathered test predictions
@@ -451,11 +473,13 @@ struct McmcRun {
 	bool vfile;
 	std::string rlog_file, out_file, parity_file, save_file, resume_file, model_file;
 	int32_t task;   // VBFM_TASK_*
+	uint32_t chain_burn, chain_thin;   // -chain B,T (chain_thin = 0: no chain, -save_model writes the last draw)
 };
 
 static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
 {
 	vbfm_ctx *ctx = nullptr;
+	vbfm_chain *chain = nullptr;
 	try {
 		const bool cls = r.task == VBFM_TASK_CLASSIFICATION;
 		if (cls && !vbfm_mcmc_class_info) throw std::string("this build has no -task c");
@@ -532,6 +556,14 @@ static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
 		if (rk.lead() && !resume) { std::ofstream a(f_rmse.c_str()); }   // truncate (:52-62); a resumed run appends
 		ParityLog plog(r.parity_file, rk.lead());
 		plog_setup(plog, ctx, r.sample ? "mcmc" : "als");
+		if (r.chain_thin) {   // -chain: the kept draws stay on the device; every rank collects, rank 0 writes
+			if (!have_chain()) throw std::string("this build has no scorer");
+			const uint32_t kept = chain_kept(r.num_iter, r.chain_burn, r.chain_thin);
+			check(vbfm_chain_create(&chain, ctx, kept), ctx);
+			if (rk.lead())
+				std::cout << "-chain " << r.chain_burn << "," << r.chain_thin << ": keeping " << kept << " of " << r.num_iter
+				          << " draws" << std::endl;
+		}
 		for (uint32_t it = it0; it < it0 + r.num_iter; it++) {
 			const double t_user = usertime();
 			const clock_t t_clock = clock();
@@ -617,10 +649,18 @@ static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
 				std::ofstream fr(f_rmse.c_str(), std::ios_base::app);
 				fr << (cls ? cs.acc_all : st.rmse_all) << "\n";
 			}
+			if (chain && it >= r.chain_burn && (it - r.chain_burn) % r.chain_thin == 0 && vbfm_chain_add(chain, ctx) != 0)
+				throw std::string(vbfm_chain_last_error(chain));
 		}
 		if (!r.save_file.empty())
 			check(vbfm_save_state(ctx, rk.rank_file(r.save_file).c_str(), it0 + r.num_iter), ctx);
-		save_model(ctx, r.model_file, it0 + r.num_iter);
+		if (chain) {
+			if (vbfm_chain_save(chain, r.model_file.c_str(), it0 + r.num_iter) != 0) throw std::string(vbfm_chain_last_error(chain));
+			vbfm_chain_destroy(chain);
+			chain = nullptr;
+		} else {
+			save_model(ctx, r.model_file, it0 + r.num_iter);
+		}
 		std::cout << "after learn" << std::endl;   // libfm.cpp:507; no Final line for mcmc (:509)
 		if (!r.out_file.empty()) {                 // libfm.cpp:514-519
 			uint32_t lo, hi;
@@ -637,6 +677,7 @@ static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
 		delete rlog_out;
 		vbfm_destroy(ctx);
 	} catch (...) {
+		if (chain) vbfm_chain_destroy(chain);
 		if (ctx) vbfm_destroy(ctx);
 		throw;
 	}
@@ -956,7 +997,8 @@ static void run_vb(const VbRun &r, Data &train, Data &test, const Rank &rk)
 }
 
 // -load_model FILE -test T -out P [-out_var V]: score T's rows with a saved model, no training. P
-// has the format and clipping of a training run's -out, V one T_n per line at 17 digits (VB kinds).
+// has the format and clipping of a training run's -out, V one T_n per line at 17 digits (VB kinds; a
+// chain of draws: the spread of the per-draw predictions).
 struct ScoreRun {
 	std::string model_file, test_file, out_file, var_file;
 	int32_t device;
@@ -976,10 +1018,17 @@ static void run_score(const ScoreRun &r)
 		if (vbfm_model_info_get(m, &info) != 0) throw std::string(vbfm_last_error(nullptr));
 		const bool cls = r.task == VBFM_TASK_CLASSIFICATION;
 		if (cls) map_class_targets(test.h);   // as training maps them, so a 0 label is the negative class
-		static const char *const kinds[4] = {"vb", "vb_online", "als", "mcmc (last draw)"};
+		static const char *const kinds[5] = {"vb", "vb_online", "als", "mcmc (last draw)", "mcmc (chain average)"};
+		uint32_t draws = 1;
+		if (info.kind == VBFM_MODEL_MCMC_CHAIN) {
+			if (!vbfm_model_num_draws) throw std::string("this build has no scorer");
+			if (vbfm_model_num_draws(m, &draws) != 0) throw std::string(vbfm_last_error(nullptr));
+		}
 		std::cout << "model " << r.model_file << ": " << kinds[info.kind] << ", dim " << info.k0 << "," << info.k1 << ","
 		          << info.num_factor << ", num_attribute=" << info.num_attribute << ", after " << info.iter
-		          << " iterations" << (cls ? ", task c" : "") << std::endl;
+		          << " iterations" << (cls ? ", task c" : "");
+		if (info.kind == VBFM_MODEL_MCMC_CHAIN) std::cout << ", " << draws << " draws";
+		std::cout << std::endl;
 		const uint32_t n = test.h.num_rows;
 		std::vector<double> mean(n), var(r.var_file.empty() ? 0 : n);
 		const vbfm_csr rows{n, test.h.nnz, test.h.row_ptr, test.h.row_ent};
@@ -1285,7 +1334,8 @@ int main(int argc, char **argv)
 		const std::string p_resume = cmd.reg("resume", "vb, vb_online, mcmc, als: continue from a -save_state file (same data and -dim) instead of the initial draws");
 		const std::string p_savem = cmd.reg("save_model", "every method: write the model's parameters to this file after the last iteration (rank 0 with -devices); -load_model scores with it");
 		const std::string p_loadm = cmd.reg("load_model", "predict only: score -test with this -save_model file and write -out (no -train; not with -method, -dim, -iter)");
-		const std::string p_outvar = cmd.reg("out_var", "with -load_model: one variance term T_n per line at 17 digits (vb and vb_online models; var(y) = T_n + 1/alpha)");
+		const std::string p_outvar = cmd.reg("out_var", "with -load_model: one variance term T_n per line at 17 digits (vb and vb_online models; var(y) = T_n + 1/alpha; a -chain model: the spread across its draws)");
+		const std::string p_chain = cmd.reg("chain", "with -method mcmc -save_model: B,T keeps the draw of iteration i (0-based) iff i >= B and (i - B) % T == 0 and writes them as one model that scores the chain average (0,1: every draw); not with -resume");
 		const std::string p_unknown = cmd.reg("unknown_ids", "with -load_model: refuse (default) or skip entries whose feature id the model does not have");
 		const std::string p_cand = cmd.reg("candidates", "with -load_model: rank the rows of this file for every row of -test and write the best -topn per row to -out as index:score pairs (targets are ignored)");
 		const std::string p_topn = cmd.reg("topn", "with -candidates: entries to return per row of -test (1..128)");
@@ -1294,7 +1344,7 @@ int main(int argc, char **argv)
 		cmd.check();
 
 		if (cmd.has(p_loadm)) {   // predict only: the model decides method and dimensions
-			for (const std::string &p : {p_method, p_dim, p_iter})
+			for (const std::string &p : {p_method, p_dim, p_iter, p_chain})
 				if (cmd.has(p)) throw std::string("-load_model scores with a trained model: -" + p + " does not apply");
 			if (!cmd.has(p_test) || !cmd.has(p_out)) throw std::string("-load_model needs -test and -out");
 			if (cmd.has(p_topn) && !cmd.has(p_cand)) throw std::string("-topn needs -candidates");
@@ -1339,6 +1389,24 @@ int main(int argc, char **argv)
 		if (task == VBFM_TASK_CLASSIFICATION && (method == "vb" || method == "vb_online"))   // the library's message
 			throw std::string("task c (binary classification) is provided by the mcmc and als learners, not by vb / vb_online");
 		if (!cmd.list(p_rel).empty()) throw std::string("-relation is not supported by this build");
+		// -chain B,T (checked before the data load): the draws to keep follow from -iter
+		uint32_t chain_burn = 0, chain_thin = 0;
+		if (cmd.has(p_chain)) {
+			const std::vector<std::string> bt = cmd.list(p_chain);
+			if (bt.size() != 2 || atol(bt[0].c_str()) < 0 || atol(bt[1].c_str()) < 1)
+				throw std::string("-chain needs B,T: a burn-in B >= 0 and a thinning interval T >= 1");
+			if (!cmd.has(p_savem)) throw std::string("-chain keeps draws for -save_model: give the model file");
+			if (method != "mcmc")
+				throw std::string("-chain keeps the draws of -method mcmc (" + method + " has no chain of draws: -save_model alone writes its model)");
+			if (cmd.has(p_resume))
+				throw std::string("-chain does not combine with -resume (the collected draws are not part of a checkpoint)");
+			chain_burn = (uint32_t)atol(bt[0].c_str());
+			chain_thin = (uint32_t)atol(bt[1].c_str());
+			const uint32_t iters = (uint32_t)cmd.geti(p_iter, 100);
+			if (chain_kept(iters, chain_burn, chain_thin) == 0)
+				throw std::string("-chain " + bt[0] + "," + bt[1] + " keeps no draw of -iter " + std::to_string(iters));
+			if (!have_chain()) throw std::string("this build has no scorer");
+		}
 
 		// the ranks: -devices N | o0,o1,..., -shard, -transport (checked before the data load)
 		Rank proto;
@@ -1424,7 +1492,7 @@ int main(int argc, char **argv)
 		for (const std::string &r : cmd.list(p_reg)) reg.push_back(atof(r.c_str()));
 		job.mc = McmcRun{method == "mcmc", seed, init_stdev, num_iter, reg, gp, G, D, k0, k1, k, vfile, rlog, out, plog,
 		                 cmd.has(p_save) ? cmd.get(p_save) : std::string(), cmd.has(p_resume) ? cmd.get(p_resume) : std::string(),
-		                 cmd.get(p_savem), task};
+		                 cmd.get(p_savem), task, chain_burn, chain_thin};
 		job.vb = VbRun{seed, init_stdev, num_iter, gp, G, D, k0, k1, k, vfile, rlog, out,
 		               cmd.has(p_save) ? cmd.get(p_save) : std::string(), cmd.has(p_resume) ? cmd.get(p_resume) : std::string(),
 		               plog, cmd.get(p_savem)};

@@ -173,7 +173,7 @@ class HostData(C.Structure):
                 ("row_ptr", P_u64), ("row_ent", C.c_void_p), ("col_ptr", P_u64), ("col_ent", C.c_void_p)]
 
 
-MODEL_KINDS = {0: "vb", 1: "vb_online", 2: "als", 3: "mcmc_draw"}   # VBFM_MODEL_* (include/vbfm.h)
+MODEL_KINDS = {0: "vb", 1: "vb_online", 2: "als", 3: "mcmc_draw", 4: "mcmc_chain"}   # VBFM_MODEL_* (include/vbfm.h)
 ORDERS = {"auto": 0, "exact": 1, "group": 2}                         # VBFM_ORDER_*
 UNKNOWN_IDS = {"refuse": 0, "skip": 1}
 
@@ -240,7 +240,10 @@ EXPORTS = ["vbfm_abi_version", "vbfm_last_error", "vbfm_create", "vbfm_destroy",
            "vbfm_model_destroy", "vbfm_score", "vbfm_score_device",
            "vbfm_synth_binarize", "vbfm_mcmc_class_info", "vbfm_model_file_task", "vbfm_model_write_host_task",
            "vbfm_model_task", "vbfm_candidates_create", "vbfm_candidates_count", "vbfm_candidates_destroy",
-           "vbfm_recommend"]
+           "vbfm_recommend",
+           "vbfm_model_file_draws", "vbfm_model_write_host_chain", "vbfm_model_read_host_draw", "vbfm_model_num_draws",
+           "vbfm_model_draw_scalars", "vbfm_chain_create", "vbfm_chain_add", "vbfm_chain_count", "vbfm_chain_save",
+           "vbfm_model_from_chain", "vbfm_chain_destroy", "vbfm_chain_last_error"]
 
 # vbfm_exchange_fn: int fn(void *user, void *buf, uint64_t count, int32_t dtype, int32_t op)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32)
@@ -348,6 +351,21 @@ def lib():
         L.vbfm_candidates_destroy.restype = None
         L.vbfm_recommend.argtypes = [V, V, C.POINTER(Csr), P_u64, P_u32, C.POINTER(RecommendOpts),
                                      C.POINTER(C.c_int32), P_f64, P_u32, C.POINTER(RecommendStats)]
+        L.vbfm_model_file_draws.argtypes = [C.c_char_p, P_u32]
+        L.vbfm_model_write_host_chain.argtypes = [C.c_char_p, C.POINTER(ModelInfo), C.c_int32, C.c_uint32,
+                                                  C.POINTER(McmcParams)]
+        L.vbfm_model_read_host_draw.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(ModelInfo), C.POINTER(McmcParams)]
+        L.vbfm_model_num_draws.argtypes = [V, P_u32]
+        L.vbfm_model_draw_scalars.argtypes = [V, C.c_uint32, P_f64, P_f64]
+        L.vbfm_chain_create.argtypes = [C.POINTER(V), V, C.c_uint32]
+        L.vbfm_chain_add.argtypes = [V, V]
+        L.vbfm_chain_count.argtypes = [V, P_u32]
+        L.vbfm_chain_save.argtypes = [V, C.c_char_p, C.c_uint32]
+        L.vbfm_model_from_chain.argtypes = [C.POINTER(V), V]
+        L.vbfm_chain_destroy.argtypes = [V]
+        L.vbfm_chain_destroy.restype = None
+        L.vbfm_chain_last_error.argtypes = [V]
+        L.vbfm_chain_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -849,6 +867,66 @@ class FMLearnMCMC(FMLearnVB):
         _check(lib().vbfm_mcmc_factor_sweep(self._ctx, C.byref(ms)), self._ctx)
         return ms.value
 
+    def chain(self, capacity):
+        """A collector of up to `capacity` draws of this sampling learner, kept on its device
+        (include/vbfm.h "chains of draws"): call add() after the iterations to keep, then model() or
+        save(). method "als" is refused."""
+        h = C.c_void_p()
+        _check(lib().vbfm_chain_create(C.byref(h), self._ctx, int(capacity)), self._ctx)
+        return Chain(h, self)
+
+
+class Chain:
+    """Draws of one FMLearnMCMC kept on the device (FMLearnMCMC.chain): the model made from them
+    scores the chain average -- what the learner's predict() reports -- and the spread across draws.
+
+        ch = fml.chain(num_iter)
+        for _ in range(num_iter):
+            fml.iterate(); ch.add()
+        mean, var = ch.model().score(rows, variance=True)
+    """
+
+    def __init__(self, handle, fml):
+        self._h = handle
+        self.fml = fml
+
+    def _chcheck(self, rc):
+        if rc != 0:
+            msg = lib().vbfm_chain_last_error(self._h)
+            raise VbfmError(msg.decode() if msg else "libvbfm error %d" % rc)
+
+    def add(self, fml=None):
+        """Keep the learner's parameters as they are now as the next draw."""
+        self._chcheck(lib().vbfm_chain_add(self._h, (fml or self.fml)._ctx))
+
+    def __len__(self):
+        n = C.c_uint32()
+        self._chcheck(lib().vbfm_chain_count(self._h, C.byref(n)))
+        return n.value
+
+    def save(self, path, num_iter=None):
+        """The draws kept so far as one model file of kind mcmc_chain. With several ranks only rank 0
+        writes."""
+        it = self.fml.num_iter_done if num_iter is None else num_iter
+        self._chcheck(lib().vbfm_chain_save(self._h, os.fsencode(path), int(it)))
+
+    def model(self):
+        """The draws kept so far as a Model (a device-to-device copy, independent of this collector)."""
+        h = C.c_void_p()
+        self._chcheck(lib().vbfm_model_from_chain(C.byref(h), self._h))
+        return Model(h)
+
+    def close(self):
+        if self._h:
+            lib().vbfm_chain_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class FMLearnVBOnline(FMLearnVB):
     """fm_learn_vb_online_simultaneous on one MI355X (src/libfm/src/fm_learn_vb_online.h,
@@ -922,6 +1000,9 @@ class Model:
         t = C.c_int32()
         _check(lib().vbfm_model_task(self._m, C.byref(t)))
         self.task = {v: k for k, v in TASKS.items()}[t.value]   # "r" or "c"
+        n = C.c_uint32()
+        _check(lib().vbfm_model_num_draws(self._m, C.byref(n)))
+        self.num_draws = n.value                                # S of a chain model, else 1
 
     @classmethod
     def load(cls, path, device=0):
@@ -983,6 +1064,49 @@ class Model:
             ps = McmcParams(_ptr(a.get("w"), P_f64), _ptr(a.get("v"), P_f64), None, None, None, None, 0.0, 0.0, 0.0)
             _check(lib().vbfm_model_write_host_task(os.fsencode(path), C.byref(inf), None, C.byref(ps), TASKS[task]))
 
+    @staticmethod
+    def file_draws(path):
+        """The draws a model file holds (1 unless its kind is mcmc_chain), after validating the whole
+        file. No GPU."""
+        n = C.c_uint32()
+        _check(lib().vbfm_model_file_draws(os.fsencode(path), C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def write_chain(path, info, draws, task="r"):
+        """Write a chain file from host arrays: info as write_params takes it (kind 4), draws a list
+        of dicts with w [D], v [k*D] as [f][j], w0 and alpha, in chain order. No GPU."""
+        inf = ModelInfo(**{k: info[k] for k, _ in ModelInfo._fields_ if k in info})
+        keep = []
+        arr = (McmcParams * max(len(draws), 1))()
+        for i, d in enumerate(draws):
+            a = {k: np.ascontiguousarray(d[k], dtype=np.float64) for k in ("w", "v") if d.get(k) is not None}
+            keep.append(a)
+            arr[i] = McmcParams(_ptr(a.get("w"), P_f64), _ptr(a.get("v"), P_f64), None, None, None, None,
+                                float(d.get("w0", 0.0)), float(d.get("alpha", 1.0)), 0.0)
+        _check(lib().vbfm_model_write_host_chain(os.fsencode(path), C.byref(inf), TASKS[task], len(draws), arr))
+
+    @staticmethod
+    def read_draw(path, s):
+        """Draw s of a chain file as read_params returns an ALS / MCMC model's parameters. No GPU."""
+        info = Model.file_info(path)
+        D, kd = info["num_attribute"], info["num_attribute"] * info["num_factor"]
+        p = {"w": np.zeros(D), "v": np.zeros(kd)}
+        ps = McmcParams(_ptr(p["w"], P_f64), _ptr(p["v"], P_f64), None, None, None, None, 0.0, 0.0, 0.0)
+        _check(lib().vbfm_model_read_host_draw(os.fsencode(path), int(s), None, C.byref(ps)))
+        p.update(w0=ps.w0, alpha=ps.alpha, info=info)
+        return p
+
+    def draw_scalars(self):
+        """(w0, alpha) of every draw as two arrays of num_draws values (a model of one set of
+        parameters: its own)."""
+        w0, alpha = np.zeros(self.num_draws), np.zeros(self.num_draws)
+        a, b = C.c_double(), C.c_double()
+        for s in range(self.num_draws):
+            self._mcheck(lib().vbfm_model_draw_scalars(self._m, s, C.byref(a), C.byref(b)))
+            w0[s], alpha[s] = a.value, b.value
+        return w0, alpha
+
     @property
     def alpha(self):
         return self.info["alpha"]
@@ -1017,7 +1141,8 @@ class Model:
     def score(self, data, variance=False, order="auto", clip=True, unknown_ids="refuse", chunk_bytes=0):
         """Mean prediction of every row of `data` -- a DataSubset that holds its rows (from
         DataSubset.load) or a (row_ptr, feat, val) triple -- and with variance=True the pair
-        (mean, T). The rows stay in host memory and are staged in chunks of chunk_bytes."""
+        (mean, T); a chain model (kind mcmc_chain) scores the average over its draws and, as T, their
+        spread. The rows stay in host memory and are staged in chunks of chunk_bytes."""
         rows, _keep = self._rows(data)
         n = rows.num_rows
         mean = np.zeros(n)
