@@ -244,6 +244,93 @@ def generate_multihot(n_rows, n_features, lo, hi, seed, xmode=0, model_seed=MODE
     return row_ptr, feat, val, y
 
 
+# ---- field data with prescribed column lengths (tests/test_shapes_cpu.py, test_shapes_gpu.py) ----
+# The level kernels' workgroup shapes, restated from dispatch_shape (csrc/vbfm_device.h): a level
+# whose mean column length (floor) is at most `upto` runs BLOCK x R; the last row takes the rest.
+SHAPE_TABLE = ((128, 64, 2), (200, 256, 1), (384, 128, 3), (640, 256, 2), (None, 512, 2))
+
+# One column-length list per shape, CAP = BLOCK x R: CAP (a full resident run), CAP + 1 (streamed,
+# a last chunk of one record), 2 CAP + 1 (three chunks), 1, CAP - 1, CAP / 2, and for 256 x 1 two
+# fillers that keep the mean under 200.
+SHAPE_COLUMNS = {
+    (64, 2): (128, 129, 257, 1, 127, 64),
+    (256, 1): (256, 257, 513, 1, 255, 128, 60, 60),
+    (128, 3): (384, 385, 769, 1, 383, 192),
+    (256, 2): (512, 513, 1025, 1, 511, 256),
+    (512, 2): (1024, 1025, 2049, 1, 1023, 512),
+}
+SEG_MIN = 1024       # build_long_segs (csrc/vbfm_store.hip): a column is cut into segments beyond
+SEG_MEANS = 4        # max(SEG_MIN, SEG_MEANS x the level's mean column length)
+
+
+def shape_of_mean(mean):
+    """(BLOCK, R) of a level whose mean column length is `mean` (SHAPE_TABLE)."""
+    for upto, block, r in SHAPE_TABLE:
+        if upto is None or int(mean) <= upto:
+            return block, r
+
+
+def level_means(level, num_levels, col_ptr):
+    """[(floor of the mean column length, longest column)] of the levels 1..num_levels, from a
+    learner's levels() and its train CSC's col_ptr, as build_schedule computes them."""
+    lens = np.diff(np.asarray(col_ptr).astype(np.int64))
+    out = []
+    for l in range(1, num_levels + 1):
+        m = lens[np.asarray(level) == l]
+        out.append((int(m.sum()) // max(1, len(m)), int(m.max()) if len(m) else 0))
+    return out
+
+
+def generate_columns(lengths, seed, xmode=1, n_fields=3, n_test=96, model_seed=MODEL_SEED):
+    """One-hot field data whose every field holds columns of exactly the given lengths.
+
+    Field f's m = len(lengths) ids are f m .. f m + m - 1 and its id c has lengths[(c + f) % m] rows
+    (the list rotated per field); which rows is a permutation per field (the order of the hashes
+    h_seed(8, f N + r)), so no field is a copy of another. x as generate() (xmode 0: every x is 1),
+    targets from generate()'s planted model over the ids. The test set draws each field's id
+    uniformly (h_seed(9, .)), except that its first row takes the id F m in the last field: an
+    attribute that no train row has. Return (train, test, nf_train, nf_test), the sets as
+    (row_ptr, feat, val, y)."""
+    lengths = [int(x) for x in lengths]
+    m, F, N = len(lengths), int(n_fields), int(sum(lengths))
+    D = F * m + 1
+    jd = np.arange(D, dtype=np.uint64)
+    b = (_u(model_seed, 3, jd) - 0.5) * bias_gain(F)
+    p0 = _u(model_seed, 5, 2 * jd) - 0.5
+    p1 = _u(model_seed, 5, 2 * jd + np.uint64(1)) - 0.5
+
+    def finish(fe, sd, n):
+        idx = np.arange(n * F, dtype=np.uint64)
+        if xmode:
+            val = (np.float32(0.5) + (h(sd, 2, idx) >> np.uint64(40)).astype(np.float32)
+                   * np.float32(2.0 ** -24)).astype(np.float32)
+        else:
+            val = np.ones(n * F, dtype=np.float32)
+        s = np.zeros(n)
+        s0, s1, q0, q1 = (np.zeros(n) for _ in range(4))
+        for f in range(F):
+            j = fe[:, f]
+            s = s + b[j]
+            s0, s1 = s0 + p0[j], s1 + p1[j]
+            q0, q1 = q0 + p0[j] * p0[j], q1 + p1[j] * p1[j]
+        t = 0.5 * (s0 * s0 - q0) + 0.5 * (s1 * s1 - q1)
+        noise = _u(sd, 4, np.arange(n, dtype=np.uint64)) - 0.5
+        y = np.clip(np.rint(((3.0 + s) + interaction_gain(F) * t) + 1.5 * noise), 1.0, 5.0).astype(np.float32)
+        return (np.arange(n + 1, dtype=np.uint64) * np.uint64(F), fe.reshape(-1).astype(np.uint32), val, y)
+
+    fe = np.empty((N, F), dtype=np.int64)
+    for f in range(F):
+        col = np.repeat(np.arange(m), [lengths[(c + f) % m] for c in range(m)])
+        perm = np.argsort(h(seed, 8, np.arange(N, dtype=np.uint64) + np.uint64(f * N)), kind="stable")
+        fe[perm, f] = f * m + col
+    te = np.empty((n_test, F), dtype=np.int64)
+    for f in range(F):
+        te[:, f] = f * m + (h(seed, 9, np.arange(n_test, dtype=np.uint64) * np.uint64(F) + np.uint64(f))
+                            % np.uint64(m)).astype(np.int64)
+    te[0, F - 1] = F * m
+    return finish(fe, seed, N), finish(te, seed + 1, n_test), F * m, F * m + 1
+
+
 ML_USERS, ML_ITEMS = 6040, 3952      # MovieLens-1M (SURVEY §8d, BASELINE configs[1])
 
 
