@@ -9,11 +9,12 @@
 //   * -out writes the clipped test predictions of the last iteration (the reference's VB
 //     predict() body is commented out and leaves the vector uninitialised, fm_learn_vb.h:321);
 //   * -method sgd/sgda/... are rejected with an error instead of running; -task c (binary
-//     classification, probit link) runs with -method mcmc | als and is refused for vb / vb_online
-//     other learners; -relation is not supported;
+//     classification, probit link) runs with -method mcmc | als and is refused for the other
+//     learners, vb and vb_online; -relation is not supported;
 //   * extra flags: -device (HIP ordinal), -vfile 0 (skip writing v_file.txt), -save_state /
-//     -resume (checkpoints), -parity_log (17-digit JSON lines per iteration), and the multi-GPU launch: -devices N | o0,o1,..., -shard
-//     rows|features, -transport rccl|host, -plan 1 (print the ranks' shard plan, no GPU);
+//     -resume (checkpoints), -parity_log (17-digit JSON lines per iteration), and the multi-GPU
+//     launch: -devices N | o0,o1,..., -shard rows|features, -transport rccl|host, -plan 1 (print
+//     the ranks' shard plan, no GPU);
 //   * -save_model FILE (every method: the parameters alone, after the last iteration) and the
 //     predict-only mode -load_model FILE -test T -out P [-out_var V] (no -train; no reference
 //     counterpart: the reference predicts only the test set attached while training); with
@@ -30,6 +31,13 @@
 // through a shared-memory page) or, with -transport host, an all-reduce through shared memory
 // (several ranks may then share one GPU, which RCCL refuses). Rank 0 prints the reference's
 // lines and writes its files; this process waits, and kills the other ranks when one fails.
+//
+// Training is one driver, run_train: it owns everything the four methods share (context, ranks,
+// v_file.txt, -rlog, -resume, the reference-format files, -parity_log, the iteration loop and its
+// timers, -save_state, -save_model, the -out gather) and asks the method's Learner (VbLearner,
+// OnlineLearner, McmcLearner for mcmc and als) only for what differs: the initial draws, its -rlog
+// columns, the library's iteration call and what the reference prints and logs of one iteration.
+// Every library handle and file is owned (Owned<T>), so a throw anywhere releases it.
 #include "../../include/vbfm.h"
 
 #include <cmath>
@@ -40,6 +48,8 @@
 #include <iomanip>
 #include <iostream>
 #include <map>
+#include <memory>
+#include <optional>
 #include <sstream>
 #include <string>
 #include <algorithm>
@@ -78,6 +88,17 @@
 #pragma weak vbfm_model_num_draws
 
 namespace {
+
+// owning handles of the library's objects and of C files: released on every path, a throw included
+struct Release {
+	void operator()(vbfm_ctx *p) const { vbfm_destroy(p); }
+	void operator()(vbfm_chain *p) const { vbfm_chain_destroy(p); }
+	void operator()(vbfm_model *p) const { vbfm_model_destroy(p); }
+	void operator()(vbfm_candidates *p) const { vbfm_candidates_destroy(p); }
+	void operator()(FILE *f) const { fclose(f); }
+};
+template <typename T>
+using Owned = std::unique_ptr<T, Release>;
 
 // CMDLine (src/util/cmdline.h:29-197): "-name value", "--name", lists split on ";,".
 class CmdLine {
@@ -141,22 +162,25 @@ public:
 // RLog (src/util/rlog.h:29-91): TSV of registered fields, one line per iteration
 class RLog {
 public:
-	explicit RLog(std::ostream *o) : out(o) {}
+	explicit RLog(const std::string &path) : out(path.c_str())
+	{
+		if (!out.is_open()) throw std::string("Unable to open file " + path);
+	}
 	void add(const std::string &f) { header.push_back(f); value[f] = NAN; }
 	void log(const std::string &f, double d) { value[f] = d; }
 	void init()
 	{
-		for (size_t i = 0; i < header.size(); i++) *out << header[i] << (i + 1 < header.size() ? "\t" : "\n");
-		out->flush();
+		for (size_t i = 0; i < header.size(); i++) out << header[i] << (i + 1 < header.size() ? "\t" : "\n");
+		out.flush();
 	}
 	void newline()
 	{
-		for (size_t i = 0; i < header.size(); i++) *out << value[header[i]] << (i + 1 < header.size() ? "\t" : "\n");
-		out->flush();
+		for (size_t i = 0; i < header.size(); i++) out << value[header[i]] << (i + 1 < header.size() ? "\t" : "\n");
+		out.flush();
 		for (auto &kv : value) kv.second = NAN;
 	}
 private:
-	std::ostream *out;
+	std::ofstream out;
 	std::vector<std::string> header;
 	std::map<std::string, double> value;
 };
@@ -170,15 +194,13 @@ private:
 // MCMC / ALS 72 nnz + 8 N + 16 D). Non-finite values are written as null.
 class ParityLog {
 public:
-	ParityLog(const std::string &path, bool lead)
+	struct KV { const char *key; double value; };
+	void open(const std::string &path, bool lead)
 	{
 		if (path.empty() || !lead) return;
-		f = fopen(path.c_str(), "w");
+		f.reset(fopen(path.c_str(), "w"));
 		if (!f) throw std::string("Unable to open file " + path);
 	}
-	~ParityLog() { if (f) fclose(f); }
-	ParityLog(const ParityLog &) = delete;
-	ParityLog &operator=(const ParityLog &) = delete;
 	bool on() const { return f != nullptr; }
 	void begin(const char *method, uint32_t it)
 	{
@@ -193,6 +215,10 @@ public:
 		else snprintf(b, sizeof(b), "null");
 		line += std::string(", \"") + key + "\": " + b;
 	}
+	void nums(std::initializer_list<KV> kv)   // a key beside its value, in the order written
+	{
+		for (const KV &p : kv) num(p.key, p.value);
+	}
 	// the factor sweep of one iteration: ms_v of rank 0, the whole job's nnz, rows and features
 	void sweep(double ms_v, int k, uint64_t nnz, uint32_t rows, uint32_t nf, int ranks, bool mcmc)
 	{
@@ -206,11 +232,11 @@ public:
 	void exchange(vbfm_ctx *ctx);
 	void end()
 	{
-		fprintf(f, "{%s}\n", line.c_str());
-		fflush(f);
+		fprintf(f.get(), "{%s}\n", line.c_str());
+		fflush(f.get());
 	}
 private:
-	FILE *f = nullptr;
+	Owned<FILE> f;
 	std::string line;
 };
 
@@ -230,10 +256,8 @@ void ParityLog::exchange(vbfm_ctx *ctx)
 {
 	vbfm_exchange_stats xs;
 	check(vbfm_exchange_info(ctx, &xs), ctx);
-	num("exchange_calls", (double)xs.n_calls);
-	num("exchange_bytes", (double)xs.bytes);
-	num("ms_exchange", xs.ms_estimated);
-	num("exchange_timed", xs.n_timed);
+	nums({{"exchange_calls", (double)xs.n_calls}, {"exchange_bytes", (double)xs.bytes}, {"ms_exchange", xs.ms_estimated},
+	      {"exchange_timed", (double)xs.n_timed}});
 }
 
 // -parity_log's first line: what setting the train set up cost (vbfm_setup_info): the load, the
@@ -245,15 +269,10 @@ static void plog_setup(ParityLog &plog, vbfm_ctx *ctx, const char *method)
 	check(vbfm_setup_info(ctx, &su), ctx);
 	plog.begin("setup", 0);
 	plog.str("learner", method);
-	plog.num("load_s", g_load_s);
-	plog.num("set_train_s", su.s_set_train);
-	plog.num("schedule_s", su.s_schedule);
-	plog.num("store_s", su.s_store);
-	plog.num("placement_s", su.s_placement);
-	plog.num("placement_bytes", (double)su.place_bytes);
-	plog.num("placement_candidates", su.place_candidates);
-	plog.num("placement_kept_0", su.place_kept[0]);
-	plog.num("placement_kept_1", su.place_kept[1]);
+	plog.nums({{"load_s", g_load_s}, {"set_train_s", su.s_set_train}, {"schedule_s", su.s_schedule},
+	           {"store_s", su.s_store}, {"placement_s", su.s_placement}, {"placement_bytes", (double)su.place_bytes},
+	           {"placement_candidates", (double)su.place_candidates}, {"placement_kept_0", (double)su.place_kept[0]},
+	           {"placement_kept_1", (double)su.place_kept[1]}});
 	plog.end();
 }
 
@@ -460,230 +479,83 @@ void gather_test(const Rank &rk, const Data &test, const std::vector<double> &lo
 
 }  // namespace
 
-// -method mcmc | als (libfm.cpp:131-135, 297-305, 367-411; fm_learn_mcmc_simultaneous.h:50-305)
-struct McmcRun {
-	bool sample;
+// ---- training ---------------------------------------------------------------------------
+// what a training run takes from the command line (every method; main fills it once)
+struct TrainOpts {
 	uint32_t seed;
 	double init_stdev;
 	uint32_t num_iter;
-	std::vector<double> reg;
 	const uint32_t *groups;
 	uint32_t G, D;
 	int k0, k1, k;
 	bool vfile;
 	std::string rlog_file, out_file, parity_file, save_file, resume_file, model_file;
-	int32_t task;   // VBFM_TASK_*
+	uint32_t num_batch;                // vb_online: -batch
+	bool sample;                       // mcmc (true) or als
+	std::vector<double> reg;           // mcmc / als: -regular
+	int32_t task;                      // VBFM_TASK_* (c: mcmc / als only, main refuses the others)
 	uint32_t chain_burn, chain_thin;   // -chain B,T (chain_thin = 0: no chain, -save_model writes the last draw)
 };
 
-static void run_mcmc(const McmcRun &r, Data &train, Data &test, const Rank &rk)
+// one rank's run as the driver (run_train) and the method's Learner share it
+struct Train {
+	const TrainOpts &r;
+	const Rank &rk;
+	const Data &train;
+	vbfm_ctx *ctx;
+	bool resume;   // -resume: the state comes from its file (no v_file.txt, nothing truncated)
+	bool cls;      // -task c
+	std::vector<std::string> group_cols;
+	ParityLog plog;
+	// a reference-format file of this -dim: "<what>_<k0><k1><k><tail>"
+	std::string file(const char *what, const char *tail) const
+	{
+		return std::string(what) + "_" + std::to_string(r.k0) + std::to_string(r.k1) + std::to_string(r.k) + tail;
+	}
+	void append(const std::string &name, double v) const   // rank 0 adds a line
+	{
+		if (!rk.lead()) return;
+		std::ofstream f(name.c_str(), std::ios_base::app);
+		f << v << "\n";
+	}
+};
+
+// the -rlog columns of the attribute groups' hyper-parameters (fm_learn_mcmc.h:1137-1149), in the order
+// they are registered and logged: per group wmu, wlambda, then vmu, vlambda of every factor
+static std::vector<std::string> group_columns(uint32_t G, int k)
 {
-	vbfm_ctx *ctx = nullptr;
-	vbfm_chain *chain = nullptr;
-	try {
-		const bool cls = r.task == VBFM_TASK_CLASSIFICATION;
-		if (cls && !vbfm_mcmc_class_info) throw std::string("this build has no -task c");
-		vbfm_config cfg{r.k0, r.k1, r.k, r.D, r.G, r.groups, train.h.min_target, train.h.max_target, rk.device, r.task};
-		check(vbfm_create(&ctx, &cfg), nullptr);
-		join(ctx, rk);
-		{
-			const Slice tr = rk.slice(train.h), te = rk.slice(test.h);
-			check(vbfm_set_train(ctx, &tr.csc), ctx);
-			check(vbfm_set_test(ctx, &te.csc), ctx);
+	std::vector<std::string> out;
+	for (uint32_t g = 0; g < G; g++) {
+		const std::string gs = std::to_string(g);
+		out.push_back("wmu[" + gs + "]");
+		out.push_back("wlambda[" + gs + "]");
+		for (int f = 0; f < k; f++) {
+			out.push_back("vmu[" + gs + "," + std::to_string(f) + "]");
+			out.push_back("vlambda[" + gs + "," + std::to_string(f) + "]");
 		}
-		// -task c -method mcmc on several ranks: the latent targets cannot follow the reference's
-		// stream (a rank's position in it would depend on the other ranks' rejections), so the run
-		// takes the device generator for every per-attribute and per-row draw
-		const int32_t rng = cls && r.sample && rk.multi() ? VBFM_RNG_DEVICE : VBFM_RNG_REFERENCE;
-		if (rng == VBFM_RNG_DEVICE && rk.lead())
-			std::cout << "-task c -method mcmc on " << rk.nranks << " ranks: draws from the device generator" << std::endl;
-		vbfm_mcmc_config mc{r.sample, r.sample, rng, r.seed, r.init_stdev,
-		                    r.reg.empty() ? nullptr : r.reg.data(), (int32_t)r.reg.size()};
-		check(vbfm_mcmc_init(ctx, &mc), ctx);
-		const size_t kd = (size_t)r.k * r.D, gk = (size_t)r.G * r.k;
-		std::vector<double> w(r.D), v(kd), wmu(r.G), wl(r.G), vmu(gk), vl(gk);
-		vbfm_mcmc_params p{w.data(), v.data(), wmu.data(), wl.data(), vmu.data(), vl.data(), 0, 0, 0};
-		const bool resume = !r.resume_file.empty();
-		if (r.vfile && rk.lead() && !resume) {   // fm_model.h:98: the initial factors (DMatrix::save, matrix.h:129-152)
-			check(vbfm_mcmc_get_params(ctx, &p), ctx);
-			std::ofstream vf("v_file.txt");
-			for (int f = 0; f < r.k; f++) {
-				for (uint32_t j = 0; j < r.D; j++) vf << (j ? "\t" : "") << v[(size_t)f * r.D + j];
-				vf << std::endl;
-			}
-		}
-		std::ofstream *rlog_out = nullptr;
-		RLog *rlog = nullptr;
-		if (!r.rlog_file.empty() && rk.lead()) {   // fm_learn::init + fm_learn_mcmc::init fields (:1118-1149)
-			rlog_out = new std::ofstream(r.rlog_file.c_str());
-			if (!rlog_out->is_open()) throw std::string("Unable to open file " + r.rlog_file);
-			std::cout << "logging to " << r.rlog_file << std::endl;
-			rlog = new RLog(rlog_out);
-			if (cls) {   // fm_learn.h:85-86, fm_learn_mcmc.h:1129-1135
-				for (const char *f : {"accuracy", "time_pred", "time_learn", "time_learn2", "time_learn4", "alpha",
-				                      "acc_mcmc_this", "acc_mcmc_all", "acc_mcmc_all_but5", "ll_mcmc_this", "ll_mcmc_all",
-				                      "ll_mcmc_all_but5"})
-					rlog->add(f);
-			} else {
-				for (const char *f : {"rmse", "mae", "time_pred", "time_learn", "time_learn2", "time_learn4", "alpha",
-				                      "rmse_mcmc_this", "rmse_mcmc_all", "rmse_mcmc_all_but5"})
-					rlog->add(f);
-			}
-			for (uint32_t g = 0; g < r.G; g++) {
-				std::ostringstream ss;
-				ss << "wmu[" << g << "]"; rlog->add(ss.str()); ss.str("");
-				ss << "wlambda[" << g << "]"; rlog->add(ss.str()); ss.str("");
-				for (int f = 0; f < r.k; f++) {
-					ss << "vmu[" << g << "," << f << "]"; rlog->add(ss.str()); ss.str("");
-					ss << "vlambda[" << g << "," << f << "]"; rlog->add(ss.str()); ss.str("");
-				}
-			}
-			rlog->init();
-		}
-		std::cout << "in mcmc learn" << std::endl << "preprocess complete" << std::endl;
-		// -resume: the chain's state from the file instead of the initial caches (the initial
-		// draws above are replaced by the file's parameters and RNG position)
-		uint32_t it0 = 0;
-		if (resume) {
-			check(vbfm_load_state(ctx, rk.rank_file(r.resume_file).c_str(), &it0), ctx);
-			std::cout << "resuming from " << r.resume_file << " after " << it0 << " iterations" << std::endl;
-		} else {
-			check(vbfm_mcmc_init_caches(ctx), ctx);
-		}
-		std::ostringstream tag;
-		tag << r.k0 << r.k1 << r.k;
-		const std::string f_rmse = "test_rmse_" + tag.str() + "_mcmc";
-		if (rk.lead() && !resume) { std::ofstream a(f_rmse.c_str()); }   // truncate (:52-62); a resumed run appends
-		ParityLog plog(r.parity_file, rk.lead());
-		plog_setup(plog, ctx, r.sample ? "mcmc" : "als");
-		if (r.chain_thin) {   // -chain: the kept draws stay on the device; every rank collects, rank 0 writes
-			if (!have_chain()) throw std::string("this build has no scorer");
-			const uint32_t kept = chain_kept(r.num_iter, r.chain_burn, r.chain_thin);
-			check(vbfm_chain_create(&chain, ctx, kept), ctx);
-			if (rk.lead())
-				std::cout << "-chain " << r.chain_burn << "," << r.chain_thin << ": keeping " << kept << " of " << r.num_iter
-				          << " draws" << std::endl;
-		}
-		for (uint32_t it = it0; it < it0 + r.num_iter; it++) {
-			const double t_user = usertime();
-			const clock_t t_clock = clock();
-			const double t_wall = (double)time(NULL);
-			vbfm_mcmc_stats st;
-			check(vbfm_mcmc_iterate(ctx, &st), ctx);
-			vbfm_mcmc_class_stats cs;
-			memset(&cs, 0, sizeof(cs));
-			if (cls) check(vbfm_mcmc_class_info(ctx, &cs), ctx);
-			// :104-127
-			const struct { const char *name; uint32_t nan, inf; } rep[] = {
-				{"alpha", st.nan_alpha, st.inf_alpha}, {"w0", st.nan_w0, st.inf_w0}, {"w", st.nan_w, st.inf_w},
-				{"v", st.nan_v, st.inf_v}, {"w_mu", st.nan_w_mu, st.inf_w_mu},
-				{"w_lambda", st.nan_w_lambda, st.inf_w_lambda}, {"v_mu", st.nan_v_mu, st.inf_v_mu},
-				{"v_lambda", st.nan_v_lambda, st.inf_v_lambda}};
-			for (const auto &q : rep)
-				if (q.nan > 0 || q.inf > 0)
-					std::cout << "#nans in " << q.name << ":\t" << q.nan << "\t#inf_in_" << q.name << ":\t" << q.inf
-					          << std::endl;
-			if (rlog) {
-				check(vbfm_mcmc_get_params(ctx, &p), ctx);
-				rlog->log("alpha", st.alpha);
-				for (uint32_t g = 0; g < r.G; g++) {
-					std::ostringstream ss;
-					ss << "wmu[" << g << "]"; rlog->log(ss.str(), wmu[g]); ss.str("");
-					ss << "wlambda[" << g << "]"; rlog->log(ss.str(), wl[g]); ss.str("");
-					for (int f = 0; f < r.k; f++) {
-						ss << "vmu[" << g << "," << f << "]"; rlog->log(ss.str(), vmu[(size_t)g * r.k + f]); ss.str("");
-						ss << "vlambda[" << g << "," << f << "]"; rlog->log(ss.str(), vl[(size_t)g * r.k + f]); ss.str("");
-					}
-				}
-				rlog->log("time_learn", usertime() - t_user);
-				rlog->log("time_learn2", (double)(clock() - t_clock) / CLOCKS_PER_SEC);
-				rlog->log("time_learn4", (double)time(NULL) - t_wall);
-				if (cls) {   // :280-286; the three columns the reference leaves uninitialised are written as
-					// 0, ll_mcmc_all (uninitialised there too) as the computed value
-					rlog->log("accuracy", cs.acc_all);
-					rlog->log("acc_mcmc_this", cs.acc_this);
-					rlog->log("acc_mcmc_all", cs.acc_all);
-					rlog->log("acc_mcmc_all_but5", 0.0);
-					rlog->log("ll_mcmc_this", cs.ll_this);
-					rlog->log("ll_mcmc_all", cs.ll_all);
-					rlog->log("ll_mcmc_all_but5", 0.0);
-				} else {
-					rlog->log("rmse", st.rmse_all);
-					rlog->log("mae", st.mae_all);
-					rlog->log("rmse_mcmc_this", st.rmse_this);
-					rlog->log("rmse_mcmc_all", st.rmse_all);
-				}
-				rlog->newline();
-			}
-			if (cls) {   // :275 without its MAP@5 field (that reads a fixed side file)
-				std::cout << "#Iter=" << std::setw(3) << it << "\tTrain=" << cs.acc_train << "\tTest=" << cs.acc_all << std::endl;
-				if (cs.nonfinite_rows || cs.capped_rows)
-					std::cout << "#non-finite train predictions:\t" << cs.nonfinite_rows << "\t#draws at the attempt cap:\t"
-					          << cs.capped_rows << std::endl;
-			} else {
-				std::cout << "#Iter=" << std::setw(3) << it << "\tTrain=" << st.train_rmse << "\tTest=" << st.rmse_all
-				          << std::endl;
-			}
-			if (plog.on()) {
-				plog.begin(r.sample ? "mcmc" : "als", it);
-				const double vals[] = {st.train_rmse, st.rmse_all, st.mae_all, st.rmse_this, st.mae_this, st.alpha, st.w0,
-				                       st.ms_hyper, st.ms_w, st.ms_v, st.ms_predict, st.ms_total};
-				const char *keys[] = {"train", "test_rmse", "test_mae", "test_rmse_this", "test_mae_this", "alpha", "w0",
-				                      "ms_hyper", "ms_w", "ms_v", "ms_predict", "ms_total"};
-				for (size_t i = 0; i < sizeof(vals) / sizeof(vals[0]); i++) plog.num(keys[i], vals[i]);
-				plog.num("levels", st.num_levels);
-				plog.num("rng_skipped", st.rng_skipped);
-				if (cls) {
-					const double cv[] = {cs.acc_train, cs.acc_this, cs.acc_all, cs.ll_this, cs.ll_all,
-					                     (double)cs.n_train_correct, (double)cs.n_test_correct_this,
-					                     (double)cs.n_test_correct_all, (double)cs.nonfinite_rows, (double)cs.capped_rows};
-					const char *ck[] = {"acc_train", "acc_this", "acc_all", "ll_this", "ll_all", "n_train_correct",
-					                    "n_test_correct_this", "n_test_correct_all", "nonfinite_rows", "capped_rows"};
-					for (size_t i = 0; i < sizeof(cv) / sizeof(cv[0]); i++) plog.num(ck[i], cv[i]);
-				}
-				plog.sweep(st.ms_v, r.k, train.h.nnz, train.h.num_rows, train.h.num_feature, rk.nranks, true);
-				plog.exchange(ctx);
-				plog.end();
-			}
-			if (rk.lead()) {
-				std::ofstream fr(f_rmse.c_str(), std::ios_base::app);
-				fr << (cls ? cs.acc_all : st.rmse_all) << "\n";
-			}
-			if (chain && it >= r.chain_burn && (it - r.chain_burn) % r.chain_thin == 0 && vbfm_chain_add(chain, ctx) != 0)
-				throw std::string(vbfm_chain_last_error(chain));
-		}
-		if (!r.save_file.empty())
-			check(vbfm_save_state(ctx, rk.rank_file(r.save_file).c_str(), it0 + r.num_iter), ctx);
-		if (chain) {
-			if (vbfm_chain_save(chain, r.model_file.c_str(), it0 + r.num_iter) != 0) throw std::string(vbfm_chain_last_error(chain));
-			vbfm_chain_destroy(chain);
-			chain = nullptr;
-		} else {
-			save_model(ctx, r.model_file, it0 + r.num_iter);
-		}
-		std::cout << "after learn" << std::endl;   // libfm.cpp:507; no Final line for mcmc (:509)
-		if (!r.out_file.empty()) {                 // libfm.cpp:514-519
-			uint32_t lo, hi;
-			rk.range(test.h.num_rows, &lo, &hi);
-			std::vector<double> pred(hi - lo), all;
-			check(vbfm_mcmc_get_test_pred(ctx, (int32_t)(it0 + r.num_iter), pred.data()), ctx);
-			gather_test(rk, test, pred, &all);
-			if (rk.lead()) {
-				std::ofstream o(r.out_file.c_str());
-				for (double x : all) o << x << std::endl;
-			}
-		}
-		delete rlog;
-		delete rlog_out;
-		vbfm_destroy(ctx);
-	} catch (...) {
-		if (chain) vbfm_chain_destroy(chain);
-		if (ctx) vbfm_destroy(ctx);
-		throw;
+	}
+	return out;
+}
+
+// the initial draws of vb / vb_online: the reference's stream restated on the host (small models) or
+// generated on the device; VBFM_INIT=host|replay overrides
+static bool replay_init(const TrainOpts &r)
+{
+	const char *env = getenv("VBFM_INIT");
+	return env ? std::string(env) == "replay" : (size_t)r.k * r.D + r.D >= 2000000;
+}
+
+// fm_model.h:98: the initial factors (DMatrix::save, matrix.h:129-152)
+static void write_vfile(const std::vector<double> &fm_v, int k, uint32_t D)
+{
+	std::ofstream vf("v_file.txt");
+	for (int f = 0; f < k; f++) {
+		for (uint32_t j = 0; j < D; j++) vf << (j ? "\t" : "") << fm_v[(size_t)f * D + j];
+		vf << std::endl;
 	}
 }
 
-// the reference's NaN reports (fm_learn_vb_simultaneous.h:89-118 and
+// the reference's NaN reports of vb and vb_online (fm_learn_vb_simultaneous.h:89-118 and
 // fm_learn_vb_online_simultaneous.h:159-188; labels as printed there)
 static void nan_reports(uint32_t nan_alpha, uint32_t inf_alpha, uint32_t nan_mu_w, uint32_t inf_mu_w,
                         uint32_t nan_sigma_w, uint32_t nan_mu_v, uint32_t inf_mu_v, uint32_t nan_sigma_v)
@@ -698,303 +570,382 @@ static void nan_reports(uint32_t nan_alpha, uint32_t inf_alpha, uint32_t nan_mu_
 	if (nan_sigma_v > 0) std::cout << "#nans in alpha:\t" << nan_sigma_v << "\t#inf_in_alpha:\t" << 0 << std::endl;
 }
 
-static void write_vfile(const std::vector<double> &fm_v, int k, uint32_t D)
-{
-	// fm_model.h:98 (DMatrix::save, matrix.h:129-152)
-	std::ofstream vf("v_file.txt");
-	for (int f = 0; f < k; f++) {
-		for (uint32_t j = 0; j < D; j++) vf << (j ? "\t" : "") << fm_v[(size_t)f * D + j];
-		vf << std::endl;
+// What a method adds to run_train's skeleton. The driver calls, in this order: init, [-rlog: columns],
+// banner, init_caches (unless -resume), truncated, begin, per iteration step / log (-rlog only) /
+// report, then save_model and test_pred (-out).
+struct Learner {
+	Train &t;
+	const char *name;            // -parity_log's "method"
+	bool resume_first = false;   // -resume is read before -rlog opens (the "resuming from" line comes first)
+	bool after_learn = true;     // prints "after learn" (libfm.cpp:507)
+	bool final_line = true;      // prints the Final line: evaluate() is NaN (libfm.cpp:509-511)
+	Learner(Train &t_, const char *name_) : t(t_), name(name_) {}
+	virtual ~Learner() {}
+	// the initial draws; fm_v, where it has k*D elements, receives fm.v for v_file.txt
+	virtual void init(std::vector<double> &fm_v) = 0;
+	virtual std::vector<const char *> columns() const   // fm_learn::init + the learner's init fields
+	{
+		return {"rmse", "mae", "time_pred", "time_learn", "time_learn2", "time_learn4", "alpha", "rmse_mcmc_this",
+		        "rmse_mcmc_all"};
 	}
-}
-
-// -method vb_online (libfm.cpp:159-171, 312-320, 494-503; fm_learn_vb_online_simultaneous.h:20-290)
-struct OnlineRun {
-	uint32_t seed;
-	double init_stdev;
-	uint32_t num_iter, num_batch;
-	const uint32_t *groups;
-	uint32_t G, D;
-	int k0, k1, k;
-	bool vfile;
-	std::string rlog_file, out_file, parity_file, save_file, resume_file, model_file;
+	virtual void banner() const {}
+	virtual void init_caches() {}
+	virtual std::vector<std::string> truncated() const = 0;   // the files a run that does not resume starts empty
+	virtual void begin() {}
+	virtual void step(uint32_t it) = 0;    // one iteration of the library and what the reference prints of it
+	virtual void log(RLog &rlog) = 0;      // its -rlog columns (the driver adds the timers)
+	virtual void report(uint32_t it) = 0;  // the "#Iter=" line, the test_rmse file, -parity_log
+	virtual void save_model(uint32_t iter) { ::save_model(t.ctx, t.r.model_file, iter); }
+	virtual void test_pred(uint32_t, double *pred) { check(vbfm_get_test_pred(t.ctx, pred), t.ctx); }
 };
-
-static void run_online(const OnlineRun &r, Data &train, Data &test, const Rank &rk)
-{
-	if (rk.multi()) throw std::string("-method vb_online runs on one GPU (-devices 1)");
-	vbfm_ctx *ctx = nullptr;
-	try {
-		vbfm_config cfg{r.k0, r.k1, r.k, r.D, r.G, r.groups, train.h.min_target, train.h.max_target, rk.device, 0};
-		check(vbfm_create(&ctx, &cfg), nullptr);
-		const vbfm_csc tr = train.csc(), te = test.csc();
-		check(vbfm_set_train(ctx, &tr), ctx);
-		check(vbfm_set_test(ctx, &te), ctx);
-		const size_t kd = (size_t)r.k * r.D;
-		std::vector<double> fm_v(r.vfile ? kd : 0);
-		const char *init_env = getenv("VBFM_INIT");
-		const bool replay = init_env ? std::string(init_env) == "replay" : kd + r.D >= 2000000;
-		vbfm_online_config oc{r.num_batch, r.seed, r.init_stdev,
-		                      replay ? VBFM_ONLINE_INIT_REPLAY : VBFM_ONLINE_INIT_HOST, r.vfile ? fm_v.data() : nullptr};
-		check(vbfm_online_init(ctx, &oc), ctx);
-		const bool resume = !r.resume_file.empty();
-		if (r.vfile && !resume) write_vfile(fm_v, r.k, r.D);
-		// -resume: the learner's state (parameters, natural parameters, step sizes, the rand()
-		// stream and the last permutation) from the file instead of the initial draws
-		uint32_t it0 = 0;
-		if (resume) {
-			check(vbfm_load_state(ctx, r.resume_file.c_str(), &it0), ctx);
-			std::cout << "resuming from " << r.resume_file << " after " << it0 << " iterations" << std::endl;
-		}
-		std::ofstream *rlog_out = nullptr;
-		RLog *rlog = nullptr;
-		if (!r.rlog_file.empty()) {   // fm_learn::init + fm_learn_vb_online::init fields (:761-783)
-			rlog_out = new std::ofstream(r.rlog_file.c_str());
-			if (!rlog_out->is_open()) throw std::string("Unable to open file " + r.rlog_file);
-			std::cout << "logging to " << r.rlog_file << std::endl;
-			rlog = new RLog(rlog_out);
-			for (const char *f : {"rmse", "mae", "time_pred", "time_learn", "time_learn2", "time_learn4", "alpha",
-			                      "rmse_mcmc_this", "rmse_mcmc_all"})
-				rlog->add(f);
-			for (uint32_t g = 0; g < r.G; g++) {
-				std::ostringstream ss;
-				ss << "wmu[" << g << "]"; rlog->add(ss.str()); ss.str("");
-				ss << "wlambda[" << g << "]"; rlog->add(ss.str()); ss.str("");
-				for (int f = 0; f < r.k; f++) {
-					ss << "vmu[" << g << "," << f << "]"; rlog->add(ss.str()); ss.str("");
-					ss << "vlambda[" << g << "," << f << "]"; rlog->add(ss.str()); ss.str("");
-				}
-			}
-			rlog->init();
-		}
-		std::cout << "check in fm_learn_vb_online_simultaneous" << std::endl;
-		std::ostringstream tag;
-		tag << r.k0 << r.k1 << r.k;
-		// :37-52: the rmse file and an (always empty) free_energy_..._vb_online are truncated; the
-		// free energies are appended to free_energy_..._vb (fm_learn_vb_online.h:636-662)
-		const std::string f_rmse = "test_rmse_" + tag.str() + "_vb_online", f_fe = "free_energy_" + tag.str() + "_vb";
-		if (!resume) { std::ofstream a(f_rmse.c_str()); std::ofstream b(("free_energy_" + tag.str() + "_vb_online").c_str()); }
-		ParityLog plog(r.parity_file, true);
-		plog_setup(plog, ctx, "vb_online");
-		for (uint32_t it = it0; it < it0 + r.num_iter; it++) {
-			const double t_user = usertime();
-			const clock_t t_clock = clock();
-			const double t_wall = (double)time(NULL);
-			vbfm_online_stats st;
-			check(vbfm_online_epoch(ctx, &st), ctx);
-			{
-				std::ofstream fe(f_fe.c_str(), std::ios_base::app);
-				fe << -st.free_energy_first << "\n";
-				std::cout << "free energy " << st.free_energy_first << std::endl;
-				if (r.num_batch > 1) {
-					fe << -st.free_energy_last << "\n";
-					std::cout << "free energy " << st.free_energy_last << std::endl;
-				}
-			}
-			nan_reports(st.nan_alpha, st.inf_alpha, st.nan_mu_w, st.inf_mu_w, st.nan_sigma_w, st.nan_mu_v, st.inf_mu_v,
-			            st.nan_sigma_v);
-			if (rlog) {
-				rlog->log("time_learn", usertime() - t_user);
-				rlog->log("time_learn2", (double)(clock() - t_clock) / CLOCKS_PER_SEC);
-				rlog->log("time_learn4", (double)time(NULL) - t_wall);
-				rlog->log("rmse_mcmc_this", st.rmse);
-				rlog->newline();
-			}
-			std::ofstream fr(f_rmse.c_str(), std::ios_base::app);
-			fr << st.rmse << "\n";
-			std::cout << "#Iter=" << std::setw(3) << it << "\tTest=" << st.rmse << std::endl;
-			if (plog.on()) {
-				plog.begin("vb_online", it);
-				const double vals[] = {st.rmse, st.mae, st.free_energy_first, st.free_energy_last, st.alpha, st.sigma_0,
-				                       st.mu_0_dash, st.sigma_0_dash, st.ms_regroup, st.ms_predict, st.ms_w0, st.ms_w,
-				                       st.ms_v, st.ms_hyper, st.ms_test, st.ms_total};
-				const char *keys[] = {"test_rmse", "test_mae", "free_energy_first", "free_energy_last", "alpha", "sigma_0",
-				                      "mu_0_dash", "sigma_0_dash", "ms_regroup", "ms_predict", "ms_w0", "ms_w", "ms_v",
-				                      "ms_hyper", "ms_test", "ms_total"};
-				for (size_t i = 0; i < sizeof(vals) / sizeof(vals[0]); i++) plog.num(keys[i], vals[i]);
-				plog.num("levels", st.num_levels);
-				plog.num("level_launches", st.n_vlevel_launches);
-				plog.num("sweep_nnz_k_per_s", st.ms_v > 0 ? (double)train.h.nnz * r.k / (st.ms_v * 1e-3) : NAN);
-				plog.end();
-			}
-		}
-		if (!r.save_file.empty()) check(vbfm_save_state(ctx, r.save_file.c_str(), it0 + r.num_iter), ctx);
-		save_model(ctx, r.model_file, it0 + r.num_iter);
-		std::cout << "after learn" << std::endl;                              // libfm.cpp:507
-		std::cout << "Final\tTrain=" << NAN << "\tTest=" << NAN << std::endl;   // evaluate() is NaN (:17)
-		if (!r.out_file.empty()) {
-			std::vector<double> pred(test.h.num_rows);
-			check(vbfm_get_test_pred(ctx, pred.data()), ctx);
-			std::ofstream o(r.out_file.c_str());
-			for (double x : pred) o << x << std::endl;
-		}
-		delete rlog;
-		delete rlog_out;
-		vbfm_destroy(ctx);
-	} catch (...) {
-		if (ctx) vbfm_destroy(ctx);
-		throw;
-	}
-}
 
 // -method vb (libfm.cpp:306-311, 366, 496-519; fm_learn_vb_simultaneous.h:18-259)
-struct VbRun {
-	uint32_t seed;
-	double init_stdev;
-	uint32_t num_iter;
-	const uint32_t *groups;
-	uint32_t G, D;
-	int k0, k1, k;
-	bool vfile;
-	std::string rlog_file, out_file, save_file, resume_file, parity_file, model_file;
+struct VbLearner : Learner {
+	vbfm_iter_stats st{};
+	explicit VbLearner(Train &t_) : Learner(t_, "vb") { after_learn = false; }
+	// fm.init + fm.w.init_normal + fml->init draws (libfm.cpp:123-366); every rank draws the same values
+	void init(std::vector<double> &fm_v) override
+	{
+		if (t.resume) return;
+		const TrainOpts &r = t.r;
+		double *v = fm_v.empty() ? nullptr : fm_v.data();
+		if (replay_init(r)) {
+			check(vbfm_init_params_replay(t.ctx, r.seed, r.init_stdev, v, nullptr), t.ctx);
+			return;
+		}
+		const size_t kd = (size_t)r.k * r.D;
+		std::vector<double> mu_w(r.D), sig_w(r.D), mu_v(kd), sig_v(kd), hw(r.G), hv((size_t)r.G * r.k);
+		vbfm_params p{mu_w.data(), sig_w.data(), mu_v.data(), sig_v.data(), hw.data(), hv.data(), 0, 0, 0, 0};
+		check(vbfm_init_params_host(r.seed, r.init_stdev, r.k, r.D, r.G, &p, v, nullptr), nullptr);
+		check(vbfm_set_params(t.ctx, &p), t.ctx);
+	}
+	void init_caches() override { check(vbfm_init_caches(t.ctx), t.ctx); }
+	std::vector<std::string> truncated() const override   // :58-73
+	{
+		return {t.file("test_rmse", "_vb"), t.file("free_energy", "_vb")};
+	}
+	void step(uint32_t) override
+	{
+		time_t now = time(0);
+		std::cout << ctime(&now) << std::endl;
+		check(vbfm_iterate(t.ctx, &st), t.ctx);
+		if (st.free_energy_valid) {   // fm_learn_vb.h:678-680
+			t.append(t.file("free_energy", "_vb"), -st.free_energy);
+			std::cout << "free energy " << st.free_energy << std::endl;
+		}
+		nan_reports(st.nan_alpha, st.inf_alpha, st.nan_mu_w, st.inf_mu_w, st.nan_sigma_w, st.nan_mu_v, st.inf_mu_v,
+		            st.nan_sigma_v);
+	}
+	void log(RLog &rlog) override { rlog.log("rmse_mcmc_this", st.rmse); }
+	void report(uint32_t it) override
+	{
+		t.append(t.file("test_rmse", "_vb"), st.rmse);
+		std::cout << "#Iter=" << std::setw(3) << it << "\tTrain=" << st.train_quirk << "\tTest=" << st.rmse << std::endl;
+		ParityLog &plog = t.plog;
+		if (!plog.on()) return;
+		plog.begin(name, it);
+		plog.nums({{"train", st.train_quirk}, {"test_rmse", st.rmse}, {"test_mae", st.mae},
+		           {"free_energy", st.free_energy_valid ? st.free_energy : NAN}, {"alpha", st.alpha},
+		           {"sigma_0", st.sigma_0}, {"mu_0_dash", st.mu_0_dash}, {"sigma_0_dash", st.sigma_0_dash},
+		           {"ms_w0", st.ms_w0}, {"ms_w", st.ms_w}, {"ms_qcache", st.ms_qcache}, {"ms_v", st.ms_v},
+		           {"ms_hyper", st.ms_hyper}, {"ms_test", st.ms_test}, {"ms_total", st.ms_total},
+		           {"nan_mu_w", (double)st.nan_mu_w}, {"nan_sigma_w", (double)st.nan_sigma_w},
+		           {"inf_mu_w", (double)st.inf_mu_w}, {"nan_mu_v", (double)st.nan_mu_v},
+		           {"nan_sigma_v", (double)st.nan_sigma_v}, {"inf_mu_v", (double)st.inf_mu_v},
+		           {"nan_alpha", (double)st.nan_alpha}, {"inf_alpha", (double)st.inf_alpha},
+		           {"levels", (double)st.num_levels}});
+		plog.sweep(st.ms_v, t.r.k, t.train.h.nnz, t.train.h.num_rows, t.train.h.num_feature, t.rk.nranks, false);
+		plog.exchange(t.ctx);
+		plog.end();
+	}
 };
 
-static void run_vb(const VbRun &r, Data &train, Data &test, const Rank &rk)
-{
-	vbfm_ctx *ctx = nullptr;
-	try {
-		vbfm_config cfg{r.k0, r.k1, r.k, r.D, r.G, r.groups, train.h.min_target, train.h.max_target, rk.device, 0};
-		check(vbfm_create(&ctx, &cfg), nullptr);
-		join(ctx, rk);
-		{
-			const Slice tr = rk.slice(train.h), te = rk.slice(test.h);
-			check(vbfm_set_train(ctx, &tr.csc), ctx);
-			check(vbfm_set_test(ctx, &te.csc), ctx);
+// -method vb_online (libfm.cpp:159-171, 312-320, 494-503; fm_learn_vb_online_simultaneous.h:20-290)
+struct OnlineLearner : Learner {
+	vbfm_online_stats st{};
+	// -resume: the learner's state (parameters, natural parameters, step sizes, the rand() stream and
+	// the last permutation) from the file instead of the initial draws
+	explicit OnlineLearner(Train &t_) : Learner(t_, "vb_online") { resume_first = true; }
+	void init(std::vector<double> &fm_v) override
+	{
+		const TrainOpts &r = t.r;
+		if (r.vfile) fm_v.resize((size_t)r.k * r.D);
+		vbfm_online_config oc{r.num_batch, r.seed, r.init_stdev,
+		                      replay_init(r) ? VBFM_ONLINE_INIT_REPLAY : VBFM_ONLINE_INIT_HOST,
+		                      r.vfile ? fm_v.data() : nullptr};
+		check(vbfm_online_init(t.ctx, &oc), t.ctx);
+	}
+	void banner() const override { std::cout << "check in fm_learn_vb_online_simultaneous" << std::endl; }
+	// :37-52: the rmse file and an (always empty) free_energy_..._vb_online are truncated; the free
+	// energies are appended to free_energy_..._vb (fm_learn_vb_online.h:636-662)
+	std::vector<std::string> truncated() const override
+	{
+		return {t.file("test_rmse", "_vb_online"), t.file("free_energy", "_vb_online")};
+	}
+	void step(uint32_t) override
+	{
+		check(vbfm_online_epoch(t.ctx, &st), t.ctx);
+		t.append(t.file("free_energy", "_vb"), -st.free_energy_first);
+		std::cout << "free energy " << st.free_energy_first << std::endl;
+		if (t.r.num_batch > 1) {
+			t.append(t.file("free_energy", "_vb"), -st.free_energy_last);
+			std::cout << "free energy " << st.free_energy_last << std::endl;
 		}
-		const int k = r.k;
-		const uint32_t D = r.D, G = r.G;
+		nan_reports(st.nan_alpha, st.inf_alpha, st.nan_mu_w, st.inf_mu_w, st.nan_sigma_w, st.nan_mu_v, st.inf_mu_v,
+		            st.nan_sigma_v);
+	}
+	void log(RLog &rlog) override { rlog.log("rmse_mcmc_this", st.rmse); }
+	void report(uint32_t it) override
+	{
+		t.append(t.file("test_rmse", "_vb_online"), st.rmse);
+		std::cout << "#Iter=" << std::setw(3) << it << "\tTest=" << st.rmse << std::endl;
+		ParityLog &plog = t.plog;
+		if (!plog.on()) return;
+		plog.begin(name, it);
+		plog.nums({{"test_rmse", st.rmse}, {"test_mae", st.mae}, {"free_energy_first", st.free_energy_first},
+		           {"free_energy_last", st.free_energy_last}, {"alpha", st.alpha}, {"sigma_0", st.sigma_0},
+		           {"mu_0_dash", st.mu_0_dash}, {"sigma_0_dash", st.sigma_0_dash}, {"ms_regroup", st.ms_regroup},
+		           {"ms_predict", st.ms_predict}, {"ms_w0", st.ms_w0}, {"ms_w", st.ms_w}, {"ms_v", st.ms_v},
+		           {"ms_hyper", st.ms_hyper}, {"ms_test", st.ms_test}, {"ms_total", st.ms_total},
+		           {"levels", (double)st.num_levels}, {"level_launches", (double)st.n_vlevel_launches},
+		           {"sweep_nnz_k_per_s", st.ms_v > 0 ? (double)t.train.h.nnz * t.r.k / (st.ms_v * 1e-3) : NAN}});
+		plog.end();
+	}
+};
 
-		// fm.init + fm.w.init_normal + fml->init draws (libfm.cpp:123-366): the same stream on
-		// the host (small models) or generated on the device (VBFM_INIT=host|replay overrides);
-		// every rank draws the same values. -resume takes the state from its file instead (no
-		// draws, no v_file.txt)
-		const bool resume = !r.resume_file.empty();
-		const size_t kd = (size_t)k * D;
-		const bool vfile = r.vfile && !resume && rk.lead();
-		const char *init_env = getenv("VBFM_INIT");
-		const bool replay = init_env ? std::string(init_env) == "replay" : kd + D >= 2000000;
-		std::vector<double> fm_v(vfile || (!replay && !resume) ? kd : 0);
-		if (replay && !resume) {
-			check(vbfm_init_params_replay(ctx, r.seed, r.init_stdev, vfile ? fm_v.data() : nullptr, nullptr), ctx);
-		} else if (!resume) {
-			std::vector<double> mu_w(D), sig_w(D), mu_v(kd), sig_v(kd), hw(G), hv((size_t)G * k);
-			vbfm_params p{mu_w.data(), sig_w.data(), mu_v.data(), sig_v.data(), hw.data(), hv.data(), 0, 0, 0, 0};
-			check(vbfm_init_params_host(r.seed, r.init_stdev, k, D, G, &p, fm_v.data(), nullptr), nullptr);
-			check(vbfm_set_params(ctx, &p), ctx);
-		}
-		if (vfile) write_vfile(fm_v, k, D);
-		fm_v.clear();
-		fm_v.shrink_to_fit();
-
-		// -rlog (libfm.cpp:353-363; fields of fm_learn::init and fm_learn_vb::init)
-		std::ofstream *rlog_out = nullptr;
-		RLog *rlog = nullptr;
-		if (!r.rlog_file.empty() && rk.lead()) {
-			rlog_out = new std::ofstream(r.rlog_file.c_str());
-			if (!rlog_out->is_open()) throw std::string("Unable to open file " + r.rlog_file);
-			std::cout << "logging to " << r.rlog_file << std::endl;
-			rlog = new RLog(rlog_out);
-			for (const char *f : {"rmse", "mae", "time_pred", "time_learn", "time_learn2", "time_learn4", "alpha",
-			                      "rmse_mcmc_this", "rmse_mcmc_all"})
-				rlog->add(f);
-			for (uint32_t g = 0; g < G; g++) {
-				std::ostringstream ss;
-				ss << "wmu[" << g << "]"; rlog->add(ss.str()); ss.str("");
-				ss << "wlambda[" << g << "]"; rlog->add(ss.str()); ss.str("");
-				for (int f = 0; f < k; f++) {
-					ss << "vmu[" << g << "," << f << "]"; rlog->add(ss.str()); ss.str("");
-					ss << "vlambda[" << g << "," << f << "]"; rlog->add(ss.str()); ss.str("");
-				}
+// -method mcmc | als (libfm.cpp:131-135, 297-305, 367-411; fm_learn_mcmc_simultaneous.h:50-305)
+struct McmcLearner : Learner {
+	vbfm_mcmc_stats st{};
+	vbfm_mcmc_class_stats cs{};   // stays 0 without -task c
+	std::vector<double> w, v, wmu, wl, vmu, vl;
+	vbfm_mcmc_params p;
+	Owned<vbfm_chain> chain;      // -chain: the kept draws stay on the device; every rank collects, rank 0 writes
+	explicit McmcLearner(Train &t_)
+		: Learner(t_, t_.r.sample ? "mcmc" : "als"), w(t_.r.D), v((size_t)t_.r.k * t_.r.D), wmu(t_.r.G), wl(t_.r.G),
+		  vmu((size_t)t_.r.G * t_.r.k), vl((size_t)t_.r.G * t_.r.k),
+		  p{w.data(), v.data(), wmu.data(), wl.data(), vmu.data(), vl.data(), 0, 0, 0}
+	{
+		final_line = false;   // no Final line for mcmc (libfm.cpp:509)
+	}
+	void init(std::vector<double> &fm_v) override
+	{
+		const TrainOpts &r = t.r;
+		// -task c -method mcmc on several ranks: the latent targets cannot follow the reference's
+		// stream (a rank's position in it would depend on the other ranks' rejections), so the run
+		// takes the device generator for every per-attribute and per-row draw
+		const int32_t rng = t.cls && r.sample && t.rk.multi() ? VBFM_RNG_DEVICE : VBFM_RNG_REFERENCE;
+		if (rng == VBFM_RNG_DEVICE && t.rk.lead())
+			std::cout << "-task c -method mcmc on " << t.rk.nranks << " ranks: draws from the device generator" << std::endl;
+		vbfm_mcmc_config mc{r.sample, r.sample, rng, r.seed, r.init_stdev, r.reg.empty() ? nullptr : r.reg.data(),
+		                    (int32_t)r.reg.size()};
+		check(vbfm_mcmc_init(t.ctx, &mc), t.ctx);
+		if (fm_v.empty()) return;
+		check(vbfm_mcmc_get_params(t.ctx, &p), t.ctx);
+		fm_v = v;
+	}
+	std::vector<const char *> columns() const override   // fm_learn.h:85-86, fm_learn_mcmc.h:1118-1135
+	{
+		if (t.cls)
+			return {"accuracy", "time_pred", "time_learn", "time_learn2", "time_learn4", "alpha", "acc_mcmc_this",
+			        "acc_mcmc_all", "acc_mcmc_all_but5", "ll_mcmc_this", "ll_mcmc_all", "ll_mcmc_all_but5"};
+		std::vector<const char *> c = Learner::columns();
+		c.push_back("rmse_mcmc_all_but5");
+		return c;
+	}
+	void banner() const override { std::cout << "in mcmc learn" << std::endl << "preprocess complete" << std::endl; }
+	void init_caches() override { check(vbfm_mcmc_init_caches(t.ctx), t.ctx); }
+	std::vector<std::string> truncated() const override { return {t.file("test_rmse", "_mcmc")}; }   // :52-62
+	void begin() override
+	{
+		const TrainOpts &r = t.r;
+		if (!r.chain_thin) return;
+		if (!have_chain()) throw std::string("this build has no scorer");
+		const uint32_t kept = chain_kept(r.num_iter, r.chain_burn, r.chain_thin);
+		vbfm_chain *c = nullptr;
+		check(vbfm_chain_create(&c, t.ctx, kept), t.ctx);
+		chain.reset(c);
+		if (t.rk.lead())
+			std::cout << "-chain " << r.chain_burn << "," << r.chain_thin << ": keeping " << kept << " of " << r.num_iter
+			          << " draws" << std::endl;
+	}
+	void step(uint32_t) override
+	{
+		check(vbfm_mcmc_iterate(t.ctx, &st), t.ctx);
+		if (t.cls) check(vbfm_mcmc_class_info(t.ctx, &cs), t.ctx);
+		// :104-127
+		const struct { const char *name; uint32_t nan, inf; } rep[] = {
+			{"alpha", st.nan_alpha, st.inf_alpha}, {"w0", st.nan_w0, st.inf_w0}, {"w", st.nan_w, st.inf_w},
+			{"v", st.nan_v, st.inf_v}, {"w_mu", st.nan_w_mu, st.inf_w_mu},
+			{"w_lambda", st.nan_w_lambda, st.inf_w_lambda}, {"v_mu", st.nan_v_mu, st.inf_v_mu},
+			{"v_lambda", st.nan_v_lambda, st.inf_v_lambda}};
+		for (const auto &q : rep)
+			if (q.nan > 0 || q.inf > 0)
+				std::cout << "#nans in " << q.name << ":\t" << q.nan << "\t#inf_in_" << q.name << ":\t" << q.inf
+				          << std::endl;
+	}
+	void log(RLog &rlog) override
+	{
+		check(vbfm_mcmc_get_params(t.ctx, &p), t.ctx);
+		rlog.log("alpha", st.alpha);
+		size_t c = 0;
+		for (uint32_t g = 0; g < t.r.G; g++) {
+			rlog.log(t.group_cols[c++], wmu[g]);
+			rlog.log(t.group_cols[c++], wl[g]);
+			for (int f = 0; f < t.r.k; f++) {
+				rlog.log(t.group_cols[c++], vmu[(size_t)g * t.r.k + f]);
+				rlog.log(t.group_cols[c++], vl[(size_t)g * t.r.k + f]);
 			}
-			rlog->init();
 		}
-
-		// fm_learn_vb_simultaneous::_learn
-		uint32_t it0 = 0;
-		if (resume) {
-			check(vbfm_load_state(ctx, rk.rank_file(r.resume_file).c_str(), &it0), ctx);
-			std::cout << "resuming from " << r.resume_file << " after " << it0 << " iterations" << std::endl;
+		if (t.cls) {   // :280-286; the three columns the reference leaves uninitialised are written as
+			// 0, ll_mcmc_all (uninitialised there too) as the computed value
+			rlog.log("accuracy", cs.acc_all);
+			rlog.log("acc_mcmc_this", cs.acc_this);
+			rlog.log("acc_mcmc_all", cs.acc_all);
+			rlog.log("acc_mcmc_all_but5", 0.0);
+			rlog.log("ll_mcmc_this", cs.ll_this);
+			rlog.log("ll_mcmc_all", cs.ll_all);
+			rlog.log("ll_mcmc_all_but5", 0.0);
 		} else {
-			check(vbfm_init_caches(ctx), ctx);
+			rlog.log("rmse", st.rmse_all);
+			rlog.log("mae", st.mae_all);
+			rlog.log("rmse_mcmc_this", st.rmse_this);
+			rlog.log("rmse_mcmc_all", st.rmse_all);
 		}
-		std::ostringstream tag;
-		tag << r.k0 << r.k1 << k;
-		const std::string f_rmse = "test_rmse_" + tag.str() + "_vb", f_fe = "free_energy_" + tag.str() + "_vb";
-		if (!resume && rk.lead()) { std::ofstream a(f_rmse.c_str()); std::ofstream b(f_fe.c_str()); }   // truncate (:58-73); a resumed run appends
-		ParityLog plog(r.parity_file, rk.lead());
-		plog_setup(plog, ctx, "vb");
-		for (uint32_t it = it0; it < it0 + r.num_iter; it++) {
-			time_t now = time(0);
-			std::cout << ctime(&now) << std::endl;
-			const double t_user = usertime();
-			const clock_t t_clock = clock();
-			const double t_wall = (double)time(NULL);
-			vbfm_iter_stats st;
-			check(vbfm_iterate(ctx, &st), ctx);
-			if (st.free_energy_valid) {   // fm_learn_vb.h:678-680
-				if (rk.lead()) {
-					std::ofstream fe(f_fe.c_str(), std::ios_base::app);
-					fe << -st.free_energy << "\n";
-				}
-				std::cout << "free energy " << st.free_energy << std::endl;
-			}
-			nan_reports(st.nan_alpha, st.inf_alpha, st.nan_mu_w, st.inf_mu_w, st.nan_sigma_w, st.nan_mu_v, st.inf_mu_v,
-			            st.nan_sigma_v);
-			if (rlog) {
-				rlog->log("time_learn", usertime() - t_user);
-				rlog->log("time_learn2", (double)(clock() - t_clock) / CLOCKS_PER_SEC);
-				rlog->log("time_learn4", (double)time(NULL) - t_wall);
-				rlog->log("rmse_mcmc_this", st.rmse);
-				rlog->newline();
-			}
-			if (rk.lead()) {
-				std::ofstream fr(f_rmse.c_str(), std::ios_base::app);
-				fr << st.rmse << "\n";
-			}
-			std::cout << "#Iter=" << std::setw(3) << it << "\tTrain=" << st.train_quirk << "\tTest=" << st.rmse << std::endl;
-			if (plog.on()) {
-				plog.begin("vb", it);
-				const double vals[] = {st.train_quirk, st.rmse, st.mae, st.free_energy_valid ? st.free_energy : NAN, st.alpha,
-				                       st.sigma_0, st.mu_0_dash, st.sigma_0_dash, st.ms_w0, st.ms_w, st.ms_qcache, st.ms_v,
-				                       st.ms_hyper, st.ms_test, st.ms_total};
-				const char *keys[] = {"train", "test_rmse", "test_mae", "free_energy", "alpha", "sigma_0", "mu_0_dash",
-				                      "sigma_0_dash", "ms_w0", "ms_w", "ms_qcache", "ms_v", "ms_hyper", "ms_test", "ms_total"};
-				for (size_t i = 0; i < sizeof(vals) / sizeof(vals[0]); i++) plog.num(keys[i], vals[i]);
-				const uint32_t nans[] = {st.nan_mu_w, st.nan_sigma_w, st.inf_mu_w, st.nan_mu_v, st.nan_sigma_v, st.inf_mu_v,
-				                         st.nan_alpha, st.inf_alpha};
-				const char *nkeys[] = {"nan_mu_w", "nan_sigma_w", "inf_mu_w", "nan_mu_v", "nan_sigma_v", "inf_mu_v",
-				                       "nan_alpha", "inf_alpha"};
-				for (size_t i = 0; i < sizeof(nans) / sizeof(nans[0]); i++) plog.num(nkeys[i], nans[i]);
-				plog.num("levels", st.num_levels);
-				plog.sweep(st.ms_v, k, train.h.nnz, train.h.num_rows, train.h.num_feature, rk.nranks, false);
-				plog.exchange(ctx);
-				plog.end();
-			}
+	}
+	void report(uint32_t it) override
+	{
+		const TrainOpts &r = t.r;
+		if (t.cls) {   // :275 without its MAP@5 field (that reads a fixed side file)
+			std::cout << "#Iter=" << std::setw(3) << it << "\tTrain=" << cs.acc_train << "\tTest=" << cs.acc_all << std::endl;
+			if (cs.nonfinite_rows || cs.capped_rows)
+				std::cout << "#non-finite train predictions:\t" << cs.nonfinite_rows << "\t#draws at the attempt cap:\t"
+				          << cs.capped_rows << std::endl;
+		} else {
+			std::cout << "#Iter=" << std::setw(3) << it << "\tTrain=" << st.train_rmse << "\tTest=" << st.rmse_all
+			          << std::endl;
 		}
-		if (!r.save_file.empty())
-			check(vbfm_save_state(ctx, rk.rank_file(r.save_file).c_str(), it0 + r.num_iter), ctx);
-		save_model(ctx, r.model_file, it0 + r.num_iter);
-		// libfm.cpp:509-511: fm_learn_vb::evaluate returns NaN
-		std::cout << "Final\tTrain=" << NAN << "\tTest=" << NAN << std::endl;
-		if (!r.out_file.empty()) {   // libfm.cpp:514-519, DVector::save (matrix.h:284-295)
-			uint32_t lo, hi;
-			rk.range(test.h.num_rows, &lo, &hi);
-			std::vector<double> pred(hi - lo), all;
-			check(vbfm_get_test_pred(ctx, pred.data()), ctx);
-			gather_test(rk, test, pred, &all);
-			if (rk.lead()) {
-				std::ofstream o(r.out_file.c_str());
-				for (double v : all) o << v << std::endl;
-			}
+		ParityLog &plog = t.plog;
+		if (plog.on()) {
+			plog.begin(name, it);
+			plog.nums({{"train", st.train_rmse}, {"test_rmse", st.rmse_all}, {"test_mae", st.mae_all},
+			           {"test_rmse_this", st.rmse_this}, {"test_mae_this", st.mae_this}, {"alpha", st.alpha}, {"w0", st.w0},
+			           {"ms_hyper", st.ms_hyper}, {"ms_w", st.ms_w}, {"ms_v", st.ms_v}, {"ms_predict", st.ms_predict},
+			           {"ms_total", st.ms_total}, {"levels", (double)st.num_levels},
+			           {"rng_skipped", (double)st.rng_skipped}});
+			if (t.cls)
+				plog.nums({{"acc_train", cs.acc_train}, {"acc_this", cs.acc_this}, {"acc_all", cs.acc_all},
+				           {"ll_this", cs.ll_this}, {"ll_all", cs.ll_all}, {"n_train_correct", (double)cs.n_train_correct},
+				           {"n_test_correct_this", (double)cs.n_test_correct_this},
+				           {"n_test_correct_all", (double)cs.n_test_correct_all},
+				           {"nonfinite_rows", (double)cs.nonfinite_rows}, {"capped_rows", (double)cs.capped_rows}});
+			plog.sweep(st.ms_v, r.k, t.train.h.nnz, t.train.h.num_rows, t.train.h.num_feature, t.rk.nranks, true);
+			plog.exchange(t.ctx);
+			plog.end();
 		}
-		delete rlog;
-		delete rlog_out;
-		vbfm_destroy(ctx);
-	} catch (...) {
-		if (ctx) vbfm_destroy(ctx);
-		throw;
+		t.append(t.file("test_rmse", "_mcmc"), t.cls ? cs.acc_all : st.rmse_all);
+		if (chain && it >= r.chain_burn && (it - r.chain_burn) % r.chain_thin == 0 && vbfm_chain_add(chain.get(), t.ctx) != 0)
+			throw std::string(vbfm_chain_last_error(chain.get()));
+	}
+	void save_model(uint32_t iter) override
+	{
+		if (!chain) return Learner::save_model(iter);
+		if (vbfm_chain_save(chain.get(), t.r.model_file.c_str(), iter) != 0) throw std::string(vbfm_chain_last_error(chain.get()));
+		chain.reset();
+	}
+	// the chain average (sampling) or the last iteration's predictions, libfm.cpp:514-519
+	void test_pred(uint32_t iter, double *pred) override { check(vbfm_mcmc_get_test_pred(t.ctx, (int32_t)iter, pred), t.ctx); }
+};
+
+// The one training driver: the skeleton every method shares -- the context, the communicator, the
+// rank's slices, the initial draws and v_file.txt, -rlog, -resume or the initial caches, the
+// reference-format files, -parity_log, the iteration loop with the reference's three timers, then
+// -save_state, -save_model and the -out gather -- with the method's Learner filling in the rest.
+static void run_train(const std::string &method, const TrainOpts &r, Data &train, Data &test, const Rank &rk)
+{
+	if (method == "vb_online" && rk.multi()) throw std::string("-method vb_online runs on one GPU (-devices 1)");
+	const bool cls = r.task == VBFM_TASK_CLASSIFICATION;
+	if (cls && !vbfm_mcmc_class_info) throw std::string("this build has no -task c");
+	vbfm_config cfg{r.k0, r.k1, r.k, r.D, r.G, r.groups, train.h.min_target, train.h.max_target, rk.device, r.task};
+	vbfm_ctx *raw = nullptr;
+	check(vbfm_create(&raw, &cfg), nullptr);
+	const Owned<vbfm_ctx> ctx(raw);
+	join(raw, rk);
+	{
+		const Slice tr = rk.slice(train.h), te = rk.slice(test.h);
+		check(vbfm_set_train(raw, &tr.csc), raw);
+		check(vbfm_set_test(raw, &te.csc), raw);
+	}
+	Train t{r, rk, train, raw, !r.resume_file.empty(), cls, group_columns(r.G, r.k), ParityLog()};
+	// declared after the context: a learner's chain is destroyed before the context it was made from
+	std::unique_ptr<Learner> learner;
+	if (method == "vb") learner = std::make_unique<VbLearner>(t);
+	else if (method == "vb_online") learner = std::make_unique<OnlineLearner>(t);
+	else learner = std::make_unique<McmcLearner>(t);
+	Learner &L = *learner;
+
+	// v_file.txt: rank 0, never on -resume, never with -vfile 0
+	const bool write_v = r.vfile && rk.lead() && !t.resume;
+	{
+		std::vector<double> fm_v(write_v ? (size_t)r.k * r.D : 0);
+		L.init(fm_v);
+		if (write_v) write_vfile(fm_v, r.k, r.D);
+	}
+	// -resume: the state from the rank's file instead of the initial caches (a resumed run appends to
+	// the reference-format files)
+	uint32_t it0 = 0;
+	auto resume_or_caches = [&] {
+		if (!t.resume) return L.init_caches();
+		check(vbfm_load_state(raw, rk.rank_file(r.resume_file).c_str(), &it0), raw);
+		std::cout << "resuming from " << r.resume_file << " after " << it0 << " iterations" << std::endl;
+	};
+	if (L.resume_first) resume_or_caches();
+	std::optional<RLog> rlog;   // -rlog (libfm.cpp:353-363)
+	if (!r.rlog_file.empty() && rk.lead()) {
+		rlog.emplace(r.rlog_file);
+		std::cout << "logging to " << r.rlog_file << std::endl;
+		for (const char *c : L.columns()) rlog->add(c);
+		for (const std::string &c : t.group_cols) rlog->add(c);
+		rlog->init();
+	}
+	L.banner();
+	if (!L.resume_first) resume_or_caches();
+	if (rk.lead() && !t.resume)
+		for (const std::string &f : L.truncated()) std::ofstream a(f.c_str());
+	t.plog.open(r.parity_file, rk.lead());
+	plog_setup(t.plog, raw, L.name);
+	L.begin();
+	for (uint32_t it = it0; it < it0 + r.num_iter; it++) {
+		const double t_user = usertime();
+		const clock_t t_clock = clock();
+		const double t_wall = (double)time(NULL);
+		L.step(it);
+		if (rlog) {
+			L.log(*rlog);
+			rlog->log("time_learn", usertime() - t_user);
+			rlog->log("time_learn2", (double)(clock() - t_clock) / CLOCKS_PER_SEC);
+			rlog->log("time_learn4", (double)time(NULL) - t_wall);
+			rlog->newline();
+		}
+		L.report(it);
+	}
+	const uint32_t iter = it0 + r.num_iter;
+	if (!r.save_file.empty()) check(vbfm_save_state(raw, rk.rank_file(r.save_file).c_str(), iter), raw);
+	L.save_model(iter);
+	if (L.after_learn) std::cout << "after learn" << std::endl;
+	if (L.final_line) std::cout << "Final\tTrain=" << NAN << "\tTest=" << NAN << std::endl;
+	if (!r.out_file.empty()) {   // libfm.cpp:514-519, DVector::save (matrix.h:284-295)
+		uint32_t lo, hi;
+		rk.range(test.h.num_rows, &lo, &hi);
+		std::vector<double> pred(hi - lo), all;
+		L.test_pred(iter, pred.data());
+		gather_test(rk, test, pred, &all);
+		if (rk.lead()) {
+			std::ofstream o(r.out_file.c_str());
+			for (double x : all) o << x << std::endl;
+		}
 	}
 }
+
 
 // -load_model FILE -test T -out P [-out_var V]: score T's rows with a saved model, no training. P
 // has the format and clipping of a training run's -out, V one T_n per line at 17 digits (VB kinds; a
@@ -1006,64 +957,70 @@ struct ScoreRun {
 	int32_t task;   // the file's
 };
 
+static Owned<vbfm_model> load_model(const std::string &file, int32_t device)
+{
+	vbfm_model *m = nullptr;
+	if (vbfm_model_load(&m, file.c_str(), device) != 0) throw std::string(vbfm_last_error(nullptr));
+	return Owned<vbfm_model>(m);
+}
+
+static Owned<FILE> open_for_writing(const std::string &file)
+{
+	Owned<FILE> f(fopen(file.c_str(), "w"));
+	if (!f) throw std::string("Unable to open file " + file);
+	return f;
+}
+
 static void run_score(const ScoreRun &r)
 {
 	if (!have_scorer()) throw std::string("this build has no scorer");
 	Data test;
 	load(r.test_file, test, "test");
-	vbfm_model *m = nullptr;
-	if (vbfm_model_load(&m, r.model_file.c_str(), r.device) != 0) throw std::string(vbfm_last_error(nullptr));
-	try {
-		vbfm_model_info info;
-		if (vbfm_model_info_get(m, &info) != 0) throw std::string(vbfm_last_error(nullptr));
-		const bool cls = r.task == VBFM_TASK_CLASSIFICATION;
-		if (cls) map_class_targets(test.h);   // as training maps them, so a 0 label is the negative class
-		static const char *const kinds[5] = {"vb", "vb_online", "als", "mcmc (last draw)", "mcmc (chain average)"};
-		uint32_t draws = 1;
-		if (info.kind == VBFM_MODEL_MCMC_CHAIN) {
-			if (!vbfm_model_num_draws) throw std::string("this build has no scorer");
-			if (vbfm_model_num_draws(m, &draws) != 0) throw std::string(vbfm_last_error(nullptr));
-		}
-		std::cout << "model " << r.model_file << ": " << kinds[info.kind] << ", dim " << info.k0 << "," << info.k1 << ","
-		          << info.num_factor << ", num_attribute=" << info.num_attribute << ", after " << info.iter
-		          << " iterations" << (cls ? ", task c" : "");
-		if (info.kind == VBFM_MODEL_MCMC_CHAIN) std::cout << ", " << draws << " draws";
-		std::cout << std::endl;
-		const uint32_t n = test.h.num_rows;
-		std::vector<double> mean(n), var(r.var_file.empty() ? 0 : n);
-		const vbfm_csr rows{n, test.h.nnz, test.h.row_ptr, test.h.row_ent};
-		const vbfm_score_opts o{VBFM_ORDER_AUTO, 1, r.skip_unknown ? 1 : 0, 0};
-		vbfm_score_stats st;
-		if (vbfm_score(m, &rows, &o, mean.data(), r.var_file.empty() ? nullptr : var.data(), &st) != 0)
-			throw std::string(vbfm_model_last_error(m));
-		if (st.skipped_entries) std::cout << "skipped " << st.skipped_entries << " entries with ids the model does not have" << std::endl;
-		double s2 = 0.0, s1 = 0.0;   // the mean is clipped to the model's target range already
-		for (uint32_t i = 0; i < n; i++) {
-			const double err = mean[i] - test.h.target[i];
-			s2 += err * err;
-			s1 += std::fabs(err);
-		}
-		if (n && cls) {   // the mean is the probability Phi(yhat): accuracy as _evaluate_class counts it
-			uint32_t ok = 0;
-			for (uint32_t i = 0; i < n; i++)
-				ok += (mean[i] >= 0.5 && test.h.target[i] > 0.0f) || (mean[i] < 0.5 && test.h.target[i] < 0.0f);
-			std::cout << "Test accuracy=" << (double)ok / n << std::endl;
-		} else if (n) std::cout << "Test RMSE=" << std::sqrt(s2 / n) << "\tMAE=" << s1 / n << std::endl;
-		{
-			std::ofstream out(r.out_file.c_str());
-			if (!out.is_open()) throw std::string("Unable to open file " + r.out_file);
-			for (double x : mean) out << x << std::endl;
-		}
-		if (!r.var_file.empty()) {
-			FILE *f = fopen(r.var_file.c_str(), "w");
-			if (!f) throw std::string("Unable to open file " + r.var_file);
-			for (double x : var) fprintf(f, "%.17g\n", x);
-			fclose(f);
-		}
-		vbfm_model_destroy(m);
-	} catch (...) {
-		vbfm_model_destroy(m);
-		throw;
+	const Owned<vbfm_model> model = load_model(r.model_file, r.device);
+	vbfm_model *m = model.get();
+	vbfm_model_info info;
+	if (vbfm_model_info_get(m, &info) != 0) throw std::string(vbfm_last_error(nullptr));
+	const bool cls = r.task == VBFM_TASK_CLASSIFICATION;
+	if (cls) map_class_targets(test.h);   // as training maps them, so a 0 label is the negative class
+	static const char *const kinds[5] = {"vb", "vb_online", "als", "mcmc (last draw)", "mcmc (chain average)"};
+	uint32_t draws = 1;
+	if (info.kind == VBFM_MODEL_MCMC_CHAIN) {
+		if (!vbfm_model_num_draws) throw std::string("this build has no scorer");
+		if (vbfm_model_num_draws(m, &draws) != 0) throw std::string(vbfm_last_error(nullptr));
+	}
+	std::cout << "model " << r.model_file << ": " << kinds[info.kind] << ", dim " << info.k0 << "," << info.k1 << ","
+	          << info.num_factor << ", num_attribute=" << info.num_attribute << ", after " << info.iter
+	          << " iterations" << (cls ? ", task c" : "");
+	if (info.kind == VBFM_MODEL_MCMC_CHAIN) std::cout << ", " << draws << " draws";
+	std::cout << std::endl;
+	const uint32_t n = test.h.num_rows;
+	std::vector<double> mean(n), var(r.var_file.empty() ? 0 : n);
+	const vbfm_csr rows{n, test.h.nnz, test.h.row_ptr, test.h.row_ent};
+	const vbfm_score_opts o{VBFM_ORDER_AUTO, 1, r.skip_unknown ? 1 : 0, 0};
+	vbfm_score_stats st;
+	if (vbfm_score(m, &rows, &o, mean.data(), r.var_file.empty() ? nullptr : var.data(), &st) != 0)
+		throw std::string(vbfm_model_last_error(m));
+	if (st.skipped_entries) std::cout << "skipped " << st.skipped_entries << " entries with ids the model does not have" << std::endl;
+	double s2 = 0.0, s1 = 0.0;   // the mean is clipped to the model's target range already
+	for (uint32_t i = 0; i < n; i++) {
+		const double err = mean[i] - test.h.target[i];
+		s2 += err * err;
+		s1 += std::fabs(err);
+	}
+	if (n && cls) {   // the mean is the probability Phi(yhat): accuracy as _evaluate_class counts it
+		uint32_t ok = 0;
+		for (uint32_t i = 0; i < n; i++)
+			ok += (mean[i] >= 0.5 && test.h.target[i] > 0.0f) || (mean[i] < 0.5 && test.h.target[i] < 0.0f);
+		std::cout << "Test accuracy=" << (double)ok / n << std::endl;
+	} else if (n) std::cout << "Test RMSE=" << std::sqrt(s2 / n) << "\tMAE=" << s1 / n << std::endl;
+	{
+		std::ofstream out(r.out_file.c_str());
+		if (!out.is_open()) throw std::string("Unable to open file " + r.out_file);
+		for (double x : mean) out << x << std::endl;
+	}
+	if (!r.var_file.empty()) {
+		const Owned<FILE> f = open_for_writing(r.var_file);
+		for (double x : var) fprintf(f.get(), "%.17g\n", x);
 	}
 }
 
@@ -1114,50 +1071,39 @@ static void run_recommend(const RecommendRun &r)
 		}
 		if (xidx.empty()) xidx.push_back(0);
 	}
-	vbfm_model *m = nullptr;
-	if (vbfm_model_load(&m, r.model_file.c_str(), r.device) != 0) throw std::string(vbfm_last_error(nullptr));
+	const Owned<vbfm_model> model = load_model(r.model_file, r.device);
+	vbfm_model *m = model.get();
+	const vbfm_csr item_rows{items.h.num_rows, items.h.nnz, items.h.row_ptr, items.h.row_ent};
 	vbfm_candidates *cs = nullptr;
-	try {
-		const vbfm_csr item_rows{items.h.num_rows, items.h.nnz, items.h.row_ptr, items.h.row_ent};
-		if (vbfm_candidates_create(&cs, m, &item_rows, r.skip_unknown ? 1 : 0) != 0) throw std::string(vbfm_model_last_error(m));
-		const vbfm_csr rows{B, ctx.h.nnz, ctx.h.row_ptr, ctx.h.row_ent};
-		const vbfm_recommend_opts o{r.topn, 1, r.skip_unknown ? 1 : 0, 0};
-		const size_t n = (size_t)B * (size_t)std::max(r.topn, 0);
-		std::vector<int32_t> idx(n);
-		std::vector<double> score(n);
-		std::vector<uint32_t> count(B);
-		vbfm_recommend_stats st;
-		if (vbfm_recommend(m, cs, &rows, xptr.empty() ? nullptr : xptr.data(), xptr.empty() ? nullptr : xidx.data(), &o,
-		                   idx.data(), score.data(), count.data(), &st) != 0)
-			throw std::string(vbfm_model_last_error(m));
-		std::cout << "ranked " << st.pairs << " pairs (" << B << " contexts x " << vbfm_candidates_count(cs) << " candidates) in "
-		          << st.ms_total << " ms: prepare " << st.ms_prepare << ", pairs " << st.ms_pairs << ", merge " << st.ms_merge
-		          << " ms on the device";
-		if (st.nonfinite_pairs) std::cout << "; " << st.nonfinite_pairs << " pairs were not finite";
-		std::cout << std::endl;
-		FILE *f = fopen(r.out_file.c_str(), "w");
-		if (!f) throw std::string("Unable to open file " + r.out_file);
-		for (uint32_t c = 0; c < B; c++) {
-			for (uint32_t e = 0; e < count[c]; e++)
-				fprintf(f, "%s%d:%.17g", e ? " " : "", idx[(size_t)c * r.topn + e], score[(size_t)c * r.topn + e]);
-			fputc('\n', f);
-		}
-		fclose(f);
-		vbfm_candidates_destroy(cs);
-		vbfm_model_destroy(m);
-	} catch (...) {
-		if (cs) vbfm_candidates_destroy(cs);
-		vbfm_model_destroy(m);
-		throw;
+	if (vbfm_candidates_create(&cs, m, &item_rows, r.skip_unknown ? 1 : 0) != 0) throw std::string(vbfm_model_last_error(m));
+	const Owned<vbfm_candidates> candidates(cs);   // declared after the model: destroyed before it
+	const vbfm_csr rows{B, ctx.h.nnz, ctx.h.row_ptr, ctx.h.row_ent};
+	const vbfm_recommend_opts o{r.topn, 1, r.skip_unknown ? 1 : 0, 0};
+	const size_t n = (size_t)B * (size_t)std::max(r.topn, 0);
+	std::vector<int32_t> idx(n);
+	std::vector<double> score(n);
+	std::vector<uint32_t> count(B);
+	vbfm_recommend_stats st;
+	if (vbfm_recommend(m, cs, &rows, xptr.empty() ? nullptr : xptr.data(), xptr.empty() ? nullptr : xidx.data(), &o,
+	                   idx.data(), score.data(), count.data(), &st) != 0)
+		throw std::string(vbfm_model_last_error(m));
+	std::cout << "ranked " << st.pairs << " pairs (" << B << " contexts x " << vbfm_candidates_count(cs) << " candidates) in "
+	          << st.ms_total << " ms: prepare " << st.ms_prepare << ", pairs " << st.ms_pairs << ", merge " << st.ms_merge
+	          << " ms on the device";
+	if (st.nonfinite_pairs) std::cout << "; " << st.nonfinite_pairs << " pairs were not finite";
+	std::cout << std::endl;
+	const Owned<FILE> f = open_for_writing(r.out_file);
+	for (uint32_t c = 0; c < B; c++) {
+		for (uint32_t e = 0; e < count[c]; e++)
+			fprintf(f.get(), "%s%d:%.17g", e ? " " : "", idx[(size_t)c * r.topn + e], score[(size_t)c * r.topn + e]);
+		fputc('\n', f.get());
 	}
 }
 
 // everything one rank runs, given the parsed command line
 struct Job {
 	std::string method;
-	VbRun vb;
-	McmcRun mc;
-	OnlineRun online;
+	TrainOpts opts;
 	bool plan = false;
 };
 
@@ -1191,6 +1137,13 @@ static void print_plan(const Job &job, const Data &train, const Data &test, cons
 	fflush(stdout);
 }
 
+// the ERROR: line (libfm.cpp:521-525), naming the rank when there are several
+static void print_error(const std::string &e, const Rank *rk = nullptr)
+{
+	std::cerr << std::endl << "ERROR: " << (rk && rk->multi() ? "rank " + std::to_string(rk->rank) + ": " : "") << e
+	          << std::endl;
+}
+
 // one rank of the run. Returns the process exit status of a rank (0 ok).
 static int run_rank(const Job &job, Data &train, Data &test, Rank &rk)
 {
@@ -1202,16 +1155,12 @@ static int run_rank(const Job &job, Data &train, Data &test, Rank &rk)
 			if (n <= 0) throw std::string("no HIP device available");
 			rk.device = rk.rank % n;
 		}
-		if (job.method == "vb_online") run_online(job.online, train, test, rk);
-		else if (job.method == "vb") run_vb(job.vb, train, test, rk);
-		else run_mcmc(job.mc, train, test, rk);
+		run_train(job.method, job.opts, train, test, rk);
 		return 0;
 	} catch (std::string &e) {
-		std::cerr << std::endl << "ERROR: " << (rk.multi() ? "rank " + std::to_string(rk.rank) + ": " : "") << e
-		          << std::endl;
+		print_error(e, &rk);
 	} catch (char const *e) {
-		std::cerr << std::endl << "ERROR: " << (rk.multi() ? "rank " + std::to_string(rk.rank) + ": " : "") << e
-		          << std::endl;
+		print_error(e, &rk);
 	}
 	return 1;
 }
@@ -1292,6 +1241,92 @@ static int launch(const Job &job, Data &train, Data &test, Rank proto, const std
 	return 0;
 }
 
+// -load_model: predict only; the model decides method and dimensions
+static void run_load_model(const CmdLine &cmd)
+{
+	for (const std::string p : {"method", "dim", "iter", "chain"})
+		if (cmd.has(p)) throw std::string("-load_model scores with a trained model: -" + p + " does not apply");
+	if (!cmd.has("test") || !cmd.has("out")) throw std::string("-load_model needs -test and -out");
+	if (cmd.has("topn") && !cmd.has("candidates")) throw std::string("-topn needs -candidates");
+	if (cmd.has("exclude") && !cmd.has("candidates")) throw std::string("-exclude needs -candidates");
+	if (cmd.has("candidates") && !cmd.has("topn")) throw std::string("-candidates needs -topn");
+	if (cmd.has("candidates") && cmd.has("out_var")) throw std::string("-out_var does not apply to -candidates (variances are not ranked)");
+	// the task is the file's; a -task that contradicts it is refused
+	int32_t ftask = VBFM_TASK_REGRESSION;
+	if (!have_scorer()) throw std::string("this build has no scorer");
+	if (vbfm_model_file_task) {
+		if (vbfm_model_file_task(cmd.get("load_model").c_str(), &ftask) != 0) throw std::string(vbfm_last_error(nullptr));
+	}
+	if (cmd.has("task")) {
+		const std::string t = cmd.get("task");
+		if (t != "r" && t != "c") throw std::string("unknown task");
+		if ((t == "c") != (ftask == VBFM_TASK_CLASSIFICATION))
+			throw std::string("-task " + t + " contradicts the model file, which is of task " +
+			                  (ftask == VBFM_TASK_CLASSIFICATION ? "c" : "r"));
+	}
+	const std::string unk = cmd.get("unknown_ids", "refuse");
+	if (unk != "refuse" && unk != "skip") throw std::string("-unknown_ids: refuse or skip");
+	if (cmd.has("candidates")) {
+		run_recommend(RecommendRun{cmd.get("load_model"), cmd.get("test"), cmd.get("candidates"), cmd.get("out"), cmd.get("exclude"),
+		                           (int32_t)cmd.geti("device", 0), (int32_t)cmd.geti("topn", 0), unk == "skip"});
+		return;
+	}
+	run_score(ScoreRun{cmd.get("load_model"), cmd.get("test"), cmd.get("out"), cmd.get("out_var"),
+	                   (int32_t)cmd.geti("device", 0), unk == "skip", ftask});
+}
+
+// -chain B,T (checked before the data load): the draws to keep follow from -iter
+static void parse_chain(const CmdLine &cmd, const std::string &method, uint32_t *chain_burn, uint32_t *chain_thin)
+{
+	if (!cmd.has("chain")) return;
+	const std::vector<std::string> bt = cmd.list("chain");
+	if (bt.size() != 2 || atol(bt[0].c_str()) < 0 || atol(bt[1].c_str()) < 1)
+		throw std::string("-chain needs B,T: a burn-in B >= 0 and a thinning interval T >= 1");
+	if (!cmd.has("save_model")) throw std::string("-chain keeps draws for -save_model: give the model file");
+	if (method != "mcmc")
+		throw std::string("-chain keeps the draws of -method mcmc (" + method + " has no chain of draws: -save_model alone writes its model)");
+	if (cmd.has("resume"))
+		throw std::string("-chain does not combine with -resume (the collected draws are not part of a checkpoint)");
+	*chain_burn = (uint32_t)atol(bt[0].c_str());
+	*chain_thin = (uint32_t)atol(bt[1].c_str());
+	const uint32_t iters = (uint32_t)cmd.geti("iter", 100);
+	if (chain_kept(iters, *chain_burn, *chain_thin) == 0)
+		throw std::string("-chain " + bt[0] + "," + bt[1] + " keeps no draw of -iter " + std::to_string(iters));
+	if (!have_chain()) throw std::string("this build has no scorer");
+}
+
+// the ranks: -devices N | o0,o1,..., -shard, -transport (checked before the data load)
+static Rank parse_ranks(const CmdLine &cmd, const std::string &method, std::vector<int32_t> &ordinals)
+{
+	Rank proto;
+	const std::vector<std::string> devs = cmd.list("devices");
+	if (devs.size() > 1) {
+		for (const std::string &d : devs) ordinals.push_back((int32_t)atoi(d.c_str()));
+		proto.nranks = (int32_t)ordinals.size();
+	} else if (devs.size() == 1) {
+		proto.nranks = (int32_t)atoi(devs[0].c_str());
+	}
+	if (proto.nranks < 1 || proto.nranks > 256) throw std::string("-devices: expected a rank count 1..256 or a list of ordinals");
+	for (int32_t o : ordinals)
+		if (o < 0) throw std::string("-devices: negative ordinal");
+	const std::string tr = cmd.get("transport", "rccl"), sh = cmd.get("shard", "rows");
+	if (tr != "rccl" && tr != "host") throw std::string("-transport: rccl or host");
+	if (sh != "rows" && sh != "features") throw std::string("-shard: rows or features");
+	proto.host = tr == "host";
+	proto.shard = sh == "rows" ? VBFM_SHARD_ROWS : VBFM_SHARD_FEATURES;
+	if (proto.shard == VBFM_SHARD_FEATURES && method != "vb")
+		throw std::string("-shard features is a -method vb mode");
+	if (proto.nranks > 1 && method == "vb_online") throw std::string("-method vb_online runs on one GPU (-devices 1)");
+	if (!proto.host && !ordinals.empty()) {
+		std::vector<int32_t> o = ordinals;
+		std::sort(o.begin(), o.end());
+		if (std::adjacent_find(o.begin(), o.end()) != o.end())
+			throw std::string("-devices: RCCL needs one GPU per rank (-transport host lets ranks share one)");
+	}
+	proto.device = proto.nranks == 1 ? (ordinals.empty() ? (int32_t)cmd.geti("device", 0) : ordinals[0]) : 0;
+	return proto;
+}
+
 int main(int argc, char **argv)
 {
 	try {
@@ -1323,10 +1358,10 @@ int main(int argc, char **argv)
 		const std::string p_rel = cmd.reg("relation", "BS: filenames for the relations, default=''");
 		cmd.reg("cache_size", "cache size for data storage (only applicable if data is in binary format), default=infty");
 		const std::string p_batch = cmd.reg("batch", "How many batches for online algorithm");
-		const std::string p_dev = cmd.reg("device", "HIP device ordinal of a one-GPU run; default=0");
-		const std::string p_devs = cmd.reg("devices", "GPUs: a count N (ranks on ordinals 0..N-1) or a list 'o0,o1,...' of ordinals, one rank each; default=1");
-		const std::string p_shard = cmd.reg("shard", "partition over the ranks: rows (exact, default) or features (the columns of every level; Jacobi across ranks, vb only)");
-		const std::string p_trans = cmd.reg("transport", "rank exchange: rccl (one GPU per rank, default) or host (shared memory; ranks may share a GPU)");
+		cmd.reg("device", "HIP device ordinal of a one-GPU run; default=0");
+		cmd.reg("devices", "GPUs: a count N (ranks on ordinals 0..N-1) or a list 'o0,o1,...' of ordinals, one rank each; default=1");
+		cmd.reg("shard", "partition over the ranks: rows (exact, default) or features (the columns of every level; Jacobi across ranks, vb only)");
+		cmd.reg("transport", "rank exchange: rccl (one GPU per rank, default) or host (shared memory; ranks may share a GPU)");
 		const std::string p_plan = cmd.reg("plan", "1: every rank prints its launch and shard plan as JSON and exits (no GPU)");
 		const std::string p_vfile = cmd.reg("vfile", "write v_file.txt like the reference (1) or not (0); default=1");
 		const std::string p_save = cmd.reg("save_state", "vb, vb_online, mcmc, als: write the learner's state to this file after the last iteration (.<rank> per rank with -devices)");
@@ -1335,7 +1370,7 @@ int main(int argc, char **argv)
 		const std::string p_savem = cmd.reg("save_model", "every method: write the model's parameters to this file after the last iteration (rank 0 with -devices); -load_model scores with it");
 		const std::string p_loadm = cmd.reg("load_model", "predict only: score -test with this -save_model file and write -out (no -train; not with -method, -dim, -iter)");
 		const std::string p_outvar = cmd.reg("out_var", "with -load_model: one variance term T_n per line at 17 digits (vb and vb_online models; var(y) = T_n + 1/alpha; a -chain model: the spread across its draws)");
-		const std::string p_chain = cmd.reg("chain", "with -method mcmc -save_model: B,T keeps the draw of iteration i (0-based) iff i >= B and (i - B) % T == 0 and writes them as one model that scores the chain average (0,1: every draw); not with -resume");
+		cmd.reg("chain", "with -method mcmc -save_model: B,T keeps the draw of iteration i (0-based) iff i >= B and (i - B) % T == 0 and writes them as one model that scores the chain average (0,1: every draw); not with -resume");
 		const std::string p_unknown = cmd.reg("unknown_ids", "with -load_model: refuse (default) or skip entries whose feature id the model does not have");
 		const std::string p_cand = cmd.reg("candidates", "with -load_model: rank the rows of this file for every row of -test and write the best -topn per row to -out as index:score pairs (targets are ignored)");
 		const std::string p_topn = cmd.reg("topn", "with -candidates: entries to return per row of -test (1..128)");
@@ -1343,36 +1378,8 @@ int main(int argc, char **argv)
 		if (cmd.has(p_help) || argc == 1) { cmd.print_help(); return 0; }
 		cmd.check();
 
-		if (cmd.has(p_loadm)) {   // predict only: the model decides method and dimensions
-			for (const std::string &p : {p_method, p_dim, p_iter, p_chain})
-				if (cmd.has(p)) throw std::string("-load_model scores with a trained model: -" + p + " does not apply");
-			if (!cmd.has(p_test) || !cmd.has(p_out)) throw std::string("-load_model needs -test and -out");
-			if (cmd.has(p_topn) && !cmd.has(p_cand)) throw std::string("-topn needs -candidates");
-			if (cmd.has(p_excl) && !cmd.has(p_cand)) throw std::string("-exclude needs -candidates");
-			if (cmd.has(p_cand) && !cmd.has(p_topn)) throw std::string("-candidates needs -topn");
-			if (cmd.has(p_cand) && cmd.has(p_outvar)) throw std::string("-out_var does not apply to -candidates (variances are not ranked)");
-			// the task is the file's; a -task that contradicts it is refused
-			int32_t ftask = VBFM_TASK_REGRESSION;
-			if (!have_scorer()) throw std::string("this build has no scorer");
-			if (vbfm_model_file_task) {
-				if (vbfm_model_file_task(cmd.get(p_loadm).c_str(), &ftask) != 0) throw std::string(vbfm_last_error(nullptr));
-			}
-			if (cmd.has(p_task)) {
-				const std::string t = cmd.get(p_task);
-				if (t != "r" && t != "c") throw std::string("unknown task");
-				if ((t == "c") != (ftask == VBFM_TASK_CLASSIFICATION))
-					throw std::string("-task " + t + " contradicts the model file, which is of task " +
-					                  (ftask == VBFM_TASK_CLASSIFICATION ? "c" : "r"));
-			}
-			const std::string unk = cmd.get(p_unknown, "refuse");
-			if (unk != "refuse" && unk != "skip") throw std::string("-unknown_ids: refuse or skip");
-			if (cmd.has(p_cand)) {
-				run_recommend(RecommendRun{cmd.get(p_loadm), cmd.get(p_test), cmd.get(p_cand), cmd.get(p_out), cmd.get(p_excl),
-				                           (int32_t)cmd.geti(p_dev, 0), (int32_t)cmd.geti(p_topn, 0), unk == "skip"});
-				return 0;
-			}
-			run_score(ScoreRun{cmd.get(p_loadm), cmd.get(p_test), cmd.get(p_out), cmd.get(p_outvar),
-			                   (int32_t)cmd.geti(p_dev, 0), unk == "skip", ftask});
+		if (cmd.has(p_loadm)) {
+			run_load_model(cmd);
 			return 0;
 		}
 		if (cmd.has(p_outvar) || cmd.has(p_unknown)) throw std::string("-out_var and -unknown_ids belong to -load_model");
@@ -1389,55 +1396,10 @@ int main(int argc, char **argv)
 		if (task == VBFM_TASK_CLASSIFICATION && (method == "vb" || method == "vb_online"))   // the library's message
 			throw std::string("task c (binary classification) is provided by the mcmc and als learners, not by vb / vb_online");
 		if (!cmd.list(p_rel).empty()) throw std::string("-relation is not supported by this build");
-		// -chain B,T (checked before the data load): the draws to keep follow from -iter
 		uint32_t chain_burn = 0, chain_thin = 0;
-		if (cmd.has(p_chain)) {
-			const std::vector<std::string> bt = cmd.list(p_chain);
-			if (bt.size() != 2 || atol(bt[0].c_str()) < 0 || atol(bt[1].c_str()) < 1)
-				throw std::string("-chain needs B,T: a burn-in B >= 0 and a thinning interval T >= 1");
-			if (!cmd.has(p_savem)) throw std::string("-chain keeps draws for -save_model: give the model file");
-			if (method != "mcmc")
-				throw std::string("-chain keeps the draws of -method mcmc (" + method + " has no chain of draws: -save_model alone writes its model)");
-			if (cmd.has(p_resume))
-				throw std::string("-chain does not combine with -resume (the collected draws are not part of a checkpoint)");
-			chain_burn = (uint32_t)atol(bt[0].c_str());
-			chain_thin = (uint32_t)atol(bt[1].c_str());
-			const uint32_t iters = (uint32_t)cmd.geti(p_iter, 100);
-			if (chain_kept(iters, chain_burn, chain_thin) == 0)
-				throw std::string("-chain " + bt[0] + "," + bt[1] + " keeps no draw of -iter " + std::to_string(iters));
-			if (!have_chain()) throw std::string("this build has no scorer");
-		}
-
-		// the ranks: -devices N | o0,o1,..., -shard, -transport (checked before the data load)
-		Rank proto;
+		parse_chain(cmd, method, &chain_burn, &chain_thin);
 		std::vector<int32_t> ordinals;
-		{
-			const std::vector<std::string> devs = cmd.list(p_devs);
-			if (devs.size() > 1) {
-				for (const std::string &d : devs) ordinals.push_back((int32_t)atoi(d.c_str()));
-				proto.nranks = (int32_t)ordinals.size();
-			} else if (devs.size() == 1) {
-				proto.nranks = (int32_t)atoi(devs[0].c_str());
-			}
-			if (proto.nranks < 1 || proto.nranks > 256) throw std::string("-devices: expected a rank count 1..256 or a list of ordinals");
-			for (int32_t o : ordinals)
-				if (o < 0) throw std::string("-devices: negative ordinal");
-			const std::string tr = cmd.get(p_trans, "rccl"), sh = cmd.get(p_shard, "rows");
-			if (tr != "rccl" && tr != "host") throw std::string("-transport: rccl or host");
-			if (sh != "rows" && sh != "features") throw std::string("-shard: rows or features");
-			proto.host = tr == "host";
-			proto.shard = sh == "rows" ? VBFM_SHARD_ROWS : VBFM_SHARD_FEATURES;
-			if (proto.shard == VBFM_SHARD_FEATURES && method != "vb")
-				throw std::string("-shard features is a -method vb mode");
-			if (proto.nranks > 1 && method == "vb_online") throw std::string("-method vb_online runs on one GPU (-devices 1)");
-			if (!proto.host && !ordinals.empty()) {
-				std::vector<int32_t> o = ordinals;
-				std::sort(o.begin(), o.end());
-				if (std::adjacent_find(o.begin(), o.end()) != o.end())
-					throw std::string("-devices: RCCL needs one GPU per rank (-transport host lets ranks share one)");
-			}
-			proto.device = proto.nranks == 1 ? (ordinals.empty() ? (int32_t)cmd.geti(p_dev, 0) : ordinals[0]) : 0;
-		}
+		Rank proto = parse_ranks(cmd, method, ordinals);
 
 		Data train, test;
 		const double t_load = wall_now();
@@ -1478,24 +1440,15 @@ int main(int argc, char **argv)
 		const uint32_t num_iter = (uint32_t)cmd.geti(p_iter, 100);
 		const uint32_t *gp = cmd.has(p_meta) ? groups.data() : nullptr;
 		const bool vfile = cmd.geti(p_vfile, 1) != 0;
-		const std::string rlog = cmd.has(p_rlog) ? cmd.get(p_rlog) : std::string();
-		const std::string out = cmd.has(p_out) ? cmd.get(p_out) : std::string();
-		const std::string plog = cmd.has(p_plog) ? cmd.get(p_plog) : std::string();
 
 		Job job;
 		job.method = method;
 		job.plan = cmd.geti(p_plan, 0) != 0;
-		job.online = OnlineRun{seed, init_stdev, num_iter, (uint32_t)cmd.geti(p_batch, 50), gp, G, D, k0, k1, k, vfile,
-		                       rlog, out, plog, cmd.has(p_save) ? cmd.get(p_save) : std::string(),
-		                       cmd.has(p_resume) ? cmd.get(p_resume) : std::string(), cmd.get(p_savem)};
 		std::vector<double> reg;
 		for (const std::string &r : cmd.list(p_reg)) reg.push_back(atof(r.c_str()));
-		job.mc = McmcRun{method == "mcmc", seed, init_stdev, num_iter, reg, gp, G, D, k0, k1, k, vfile, rlog, out, plog,
-		                 cmd.has(p_save) ? cmd.get(p_save) : std::string(), cmd.has(p_resume) ? cmd.get(p_resume) : std::string(),
-		                 cmd.get(p_savem), task, chain_burn, chain_thin};
-		job.vb = VbRun{seed, init_stdev, num_iter, gp, G, D, k0, k1, k, vfile, rlog, out,
-		               cmd.has(p_save) ? cmd.get(p_save) : std::string(), cmd.has(p_resume) ? cmd.get(p_resume) : std::string(),
-		               plog, cmd.get(p_savem)};
+		job.opts = TrainOpts{seed, init_stdev, num_iter, gp, G, D, k0, k1, k, vfile, cmd.get(p_rlog), cmd.get(p_out),
+		                     cmd.get(p_plog), cmd.get(p_save), cmd.get(p_resume), cmd.get(p_savem),
+		                     (uint32_t)cmd.geti(p_batch, 50), method == "mcmc", reg, task, chain_burn, chain_thin};
 
 		if (proto.nranks == 1) {   // one GPU, this process
 			run_rank(job, train, test, proto);
@@ -1503,9 +1456,9 @@ int main(int argc, char **argv)
 		}
 		launch(job, train, test, proto, ordinals);
 	} catch (std::string &e) {
-		std::cerr << std::endl << "ERROR: " << e << std::endl;   // libfm.cpp:521-525 (exit code 0 there too)
+		print_error(e);   // exit code 0, as libfm.cpp:521-525
 	} catch (char const *e) {
-		std::cerr << std::endl << "ERROR: " << e << std::endl;
+		print_error(e);
 	}
 	return 0;
 }
