@@ -262,6 +262,51 @@ SHAPE_COLUMNS = {
 SEG_MIN = 1024       # build_long_segs (csrc/vbfm_store.hip): a column is cut into segments beyond
 SEG_MEANS = 4        # max(SEG_MIN, SEG_MEANS x the level's mean column length)
 
+# The online learner's lanes per column, restated from csrc/vbfm_online.hip: a level whose
+# floor(mean column length) / num_batch is at most `upto` serves a column with G lanes; the last row
+# takes the rest. OV_G_TABLE is ov_level (the column kernels k_ov_{w,v}_level; 256 = one column per
+# workgroup), OV_LORD_G_TABLE is ov_lord_g (k_ov_lord on the per-batch level-ordered store).
+OV_G_TABLE = ((6, 4), (12, 8), (24, 16), (48, 32), (160, 64), (None, 256))
+OV_LORD_G_TABLE = ((6, 4), (12, 8), (24, 16), (48, 32), (None, 64))
+OV_CAP = 512         # records of a workgroup run that k_ov_lord stages; the padded layout's slot
+
+# One column-length list per lane-group width G (tests/online_cases.py): 1, G - 1, G, G + 1, 2 G,
+# 2 G + 1 and 3 G + 1 -- the two register slots full, one short and one over, and the loop arm.
+# floor(sum / 7) lies in G's band of both tables. The G = 64 list is ordered so that every window
+# of four consecutive columns (a k_ov_lord workgroup run, cyclic: the fields rotate the list) holds
+# at most 451 records; ascending, 65 + 128 + 129 + 193 = 515 would overflow OV_CAP.
+ONLINE_COLUMNS = {
+    4: (1, 3, 4, 5, 8, 9, 13),
+    8: (1, 7, 8, 9, 16, 17, 25),
+    16: (1, 15, 16, 17, 32, 33, 49),
+    32: (1, 31, 32, 33, 64, 65, 97),
+    64: (193, 1, 128, 63, 129, 64, 65),
+}
+# repeats of the list: more than 256 / G columns in a level and no multiple of it (a full workgroup
+# and a partial last one, whose dead lane groups take the first column's bounds)
+ONLINE_REPEATS = {4: 10, 8: 5, 16: 3, 32: 2, 64: 2}
+# floor(mean) = 300: the 256-lane column kernel on columns of 1, 255, 256, 257, 513 and beyond;
+# k_ov_lord<64> with runs -- and two single columns -- longer than OV_CAP, so packed, never padded
+ONLINE_WIDE = (520, 257, 256, 255, 1, 513, 300)
+
+
+def ov_g_of(avg_len, table):
+    """G of a level whose batch share of the mean column length is `avg_len` (OV_G_TABLE or
+    OV_LORD_G_TABLE)."""
+    for upto, g in table:
+        if upto is None or int(avg_len) <= upto:
+            return g
+
+
+def ov_band(g, table):
+    """(lowest, highest or None) avg_len that `table` gives G lanes."""
+    lo = 0
+    for upto, gg in table:
+        if gg == g:
+            return lo, upto
+        lo = upto + 1
+    raise KeyError(g)
+
 
 def shape_of_mean(mean):
     """(BLOCK, R) of a level whose mean column length is `mean` (SHAPE_TABLE)."""
