@@ -745,6 +745,51 @@ int vbfm_recommend(vbfm_model *m, const vbfm_candidates *c, const vbfm_csr *cont
                    const uint32_t *excl_idx, const vbfm_recommend_opts *o, int32_t *idx, double *score,
                    uint32_t *count, vbfm_recommend_stats *st);
 
+/* ---- ranking by mean + beta * sd (additive to ABI 4: new functions and structs only) ---------------
+ * The same ranking on an upper (beta > 0) or lower (beta < 0) confidence bound of the pair's row, for
+ * the kinds with has_variance (VBFM_MODEL_VB, VBFM_MODEL_VB_ONLINE); ALS, MCMC_DRAW and MCMC_CHAIN models
+ * are refused with a message that names the kind. The reference's T_n (predict_t_and_write_to_qterms,
+ * fm_learn_vb.h:207-312) is, per factor, built from Z[f] = sum sigma_v x^2 and P[f] = sum mu_v^2 x^2 over
+ * the row's entries as 1/2 Z^2 + Z P; every other term is a sum over entries. So for one row holding c's
+ * and j's entries
+ *     T(c u j) = T_c + T_j - [k0] sigma_0_dash + sum_f ( Z_c[f] (Z_j[f] + P_j[f]) + P_c[f] Z_j[f] )
+ * for any entries, repeated and shared ids included. Rows are prepared by the lane-group scorer:
+ * base_r, Q_r[f] and raw(c, j) are exactly those of vbfm_recommend above; tb_r is the T_n vbfm_score
+ * returns for row r alone (group order); Z_r[f], P_r[f] the scorer's per-factor sums of row r (entries in
+ * ascending id); U_j[f] = Z_j[f] + P_j[f], rounded once when the candidate set is prepared. Then
+ *     t = 0;  for f = 0 .. k - 1:  t = fma(Z_c[f], U_j[f], t);  t = fma(P_c[f], Z_j[f], t)
+ *     T(c, j)   = (tb_c + tb_j - (k0 ? sigma_0_dash : 0)) + t
+ *     sd(c, j)  = sqrt(max(T(c, j) + (noise ? 1 / alpha : 0), 0))
+ *     key(c, j) = fma(beta, sd(c, j), raw(c, j))
+ * Every pair's raw, T and key are formed by exactly these expressions, whatever tile, slice or chunk the
+ * pair falls in, and the ranking is the total order above applied to key (larger first, equal key by
+ * smaller candidate index), so all results are bit-identical whatever the chunk size and the launch
+ * geometry. A pair whose raw or T is not finite (or whose key overflows) is never returned and is counted
+ * in nonfinite_pairs. beta is any finite double (NaN and +-inf are refused); beta = 0 is vbfm_recommend's
+ * ranking. Returned for each survivor, best first: idx; key; score = raw, or with clip = 1 what
+ * vbfm_recommend returns for it; var = T(c, j) without the noise term -- as with vbfm_score, adding
+ * 1 / alpha is the caller's. T differs from vbfm_score's var of the merged row by the rounding of a
+ * reordered fp64 sum. Limits as vbfm_recommend.
+ *
+ * vbfm_candidates_create_var makes a candidate set that also holds Z, U and tb of its rows: three
+ * times the device memory of vbfm_candidates_create's (checked against the free memory before anything
+ * is allocated; the refusal names both figures). Such a set is also valid for vbfm_recommend, with the
+ * same bits; vbfm_recommend_ucb refuses a set made by vbfm_candidates_create. */
+int vbfm_candidates_create_var(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids);
+typedef struct {
+	int32_t topn;          /* the four fields of vbfm_recommend_opts */
+	int32_t clip;
+	int32_t unknown_ids;
+	uint64_t chunk_bytes;
+	double beta;           /* finite */
+	int32_t noise;         /* 1: sd is of y (T + 1 / alpha), 0: of the model's mean (T) */
+} vbfm_recommend_ucb_opts;
+/* contexts, exclusions, idx and count as vbfm_recommend; key, score, var [B * topn] (NaN beyond count),
+ * each may be NULL. st: nonfinite_pairs has the meaning above. */
+int vbfm_recommend_ucb(vbfm_model *m, const vbfm_candidates *c, const vbfm_csr *contexts, const uint64_t *excl_ptr,
+                       const uint32_t *excl_idx, const vbfm_recommend_ucb_opts *o, int32_t *idx, double *key,
+                       double *score, double *var, uint32_t *count, vbfm_recommend_stats *st);
+
 #ifdef __cplusplus
 }
 #endif

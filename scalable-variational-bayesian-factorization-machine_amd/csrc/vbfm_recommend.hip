@@ -11,6 +11,8 @@
 //
 // Kernels: k_score<.., QOUT> (vbfm_score.h: the lane-group scorer, which here also stores every
 // row's per-factor sums), k_rec_pairs (the hot path) and k_rec_merge (the slices' lists into one).
+// Ranking by mean + beta * sd (vbfm_recommend_ucb) adds the variance term of the merged
+// row by the same algebra: k_score<.., VAR, QOUT>, k_ucb_pairs, the same merge, k_ucb_finish.
 #include "vbfm_score.h"
 #include "vbfm_class_math.h"
 
@@ -336,14 +338,229 @@ hipError_t launch_pairs(const double *qc, const double *qt, const double *base_c
 	return hipGetLastError();
 }
 
+// ---- ranking by an upper confidence bound (include/vbfm.h "ranking by mean + beta * sd")
+// The pair kernel's sibling: a wave owns UCB_CTX contexts (half of REC_CTX: a pair keeps two
+// accumulators, dot and t, so the register block of UCB_CTX x REC_CJ pairs is the size of
+// k_rec_pairs'), a workgroup is UCB_WAVES waves whatever the list capacity (the lists of half as
+// many contexts fit), so its context tile is UCB_TILE_B rows. The 16-context form (k_rec_pairs'
+// workgroups, twice the register block) is compiled too and taken where it measured faster (ucb_ctx
+// below; VBFM_UCB_CTX forces either: probes and the geometry test). The result does not depend on it.
+#define UCB_CTX 8
+#define UCB_WAVES 4
+#define UCB_TILE_B (UCB_CTX * UCB_WAVES)
+
+struct UcbArgs {
+	double s0;      // k0 ? sigma_0_dash : 0
+	double na;      // noise ? 1 / alpha : 0
+	double beta;
+};
+
+struct UcbVal {
+	double raw, T, key;
+	bool ok;        // raw, T and key are finite
+};
+
+// THE expressions of a pair (include/vbfm.h): dot as rec_raw's, t is fma(Z_c[f], U_j[f], t) then
+// fma(P_c[f], Z_j[f], t) over f ascending. The pair kernel ranks on it and k_ucb_finish forms the
+// survivors' returned values with it.
+DEVI UcbVal ucb_pair(double base_c, double base_j, double w0, double dot, double tb_c, double tb_j, double t, const UcbArgs &u)
+{
+	UcbVal v;
+	v.raw = rec_raw(base_c, base_j, w0, dot);
+	v.T = ((tb_c + tb_j) - u.s0) + t;
+	const double sd = __builtin_sqrt(__builtin_fmax(v.T + u.na, 0.0));
+	v.key = __builtin_fma(u.beta, sd, v.raw);
+	v.ok = __builtin_isfinite(v.raw) && __builtin_isfinite(v.T) && __builtin_isfinite(v.key);
+	return v;
+}
+
+// k_rec_pairs with two accumulators per pair. Grid (context tiles of CTX * WAVES, candidate slices);
+// a wave's lists (ordered by key) are its own, no barrier, no atomics in the loops. The context side
+// is wave-uniform: ctx_all is the preparation's [tile of CTX][3][f][CTX] (Q, Z, P planes), read by
+// scalar loads through plain restrict parameters; a lane loads its REC_CJ candidates' Q, Z and U of
+// factor f (coalesced, [f][Mpad] each) and keeps 2 x REC_CJ x CTX accumulators across the f loop.
+template <int CAP, int WAVES, int CTX>
+__global__ __launch_bounds__(64 * WAVES) void k_ucb_pairs(const double *__restrict__ ctx_all, const double *__restrict__ qt,
+                                                          const double *__restrict__ zt, const double *__restrict__ ut,
+                                                          const double *__restrict__ base_c, const double *__restrict__ base_j,
+                                                          const double *__restrict__ tb_c, const double *__restrict__ tb_j,
+                                                          const PairArgs a, const UcbArgs u)
+{
+	__shared__ double s_key[WAVES][CTX][CAP];
+	__shared__ uint32_t s_idx[WAVES][CTX][CAP];
+	__shared__ uint32_t s_cnt[WAVES][CTX];
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+	const uint32_t tile = blockIdx.x * WAVES + wave;
+	const uint32_t c0 = tile * CTX;
+	if (c0 >= a.nB) return;
+	const int nctx = (int)min((uint32_t)CTX, a.nB - c0);
+	const int k = a.k, topn = a.topn;
+	const uint32_t slice = blockIdx.y;
+	const uint32_t jb = (uint32_t)min((uint64_t)a.M, (uint64_t)slice * a.slice_len);
+	const uint32_t je = (uint32_t)min((uint64_t)a.M, (uint64_t)jb + a.slice_len);
+	if (lane < CTX) {
+		s_cnt[wave][lane] = 0;
+		s_key[wave][lane][topn - 1] = -INFINITY;
+		s_idx[wave][lane][topn - 1] = 0xffffffffu;
+	}
+	wave_sync();
+	const double *__restrict__ qc = ctx_all + (size_t)tile * 3 * k * CTX;
+	const double *__restrict__ zc = qc + (size_t)k * CTX;
+	const double *__restrict__ pc = zc + (size_t)k * CTX;
+	const double w0 = a.w0;
+	uint32_t nonfinite = 0, exhits = 0;
+	for (uint32_t j0 = jb; j0 < je; j0 += REC_STEP) {   // at most slice_len / REC_STEP steps
+		double dot[REC_CJ][CTX], t[REC_CJ][CTX];
+#pragma unroll
+		for (int v = 0; v < REC_CJ; ++v)
+#pragma unroll
+			for (int i = 0; i < CTX; ++i) { dot[v][i] = 0.0; t[v][i] = 0.0; }
+		const size_t at = (size_t)j0 + lane;   // j0 + 127 < Mpad: Mpad % REC_STEP == 0
+#pragma unroll 1
+		for (int f = 0; f < k; ++f) {
+			const size_t o = (size_t)f * a.Mpad + at;
+			const double q0 = qt[o], q1 = qt[o + 64], z0 = zt[o], z1 = zt[o + 64], u0 = ut[o], u1 = ut[o + 64];
+			const double *__restrict__ cq = qc + (size_t)f * CTX;
+			const double *__restrict__ cz = zc + (size_t)f * CTX;
+			const double *__restrict__ cp = pc + (size_t)f * CTX;
+#pragma unroll
+			for (int i = 0; i < CTX; ++i) {
+				const double qi = cq[i], zi = cz[i], pi = cp[i];
+				dot[0][i] = __builtin_fma(qi, q0, dot[0][i]);
+				dot[1][i] = __builtin_fma(qi, q1, dot[1][i]);
+				t[0][i] = __builtin_fma(zi, u0, t[0][i]);
+				t[1][i] = __builtin_fma(zi, u1, t[1][i]);
+				t[0][i] = __builtin_fma(pi, z0, t[0][i]);
+				t[1][i] = __builtin_fma(pi, z1, t[1][i]);
+			}
+		}
+		const double bj0 = base_j[at], bj1 = base_j[at + 64], tj0 = tb_j[at], tj1 = tb_j[at + 64];
+		const bool in0 = j0 + lane < je, in1 = j0 + 64 + lane < je;
+#pragma unroll
+		for (int i = 0; i < CTX; ++i) {
+			if (i < nctx) {
+				const double bc = base_c[c0 + i], tc = tb_c[c0 + i];
+				const double tr = s_key[wave][i][topn - 1];
+				const uint32_t ti = s_idx[wave][i][topn - 1];
+				const UcbVal v0 = ucb_pair(bc, bj0, w0, dot[0][i], tc, tj0, t[0][i], u);
+				const UcbVal v1 = ucb_pair(bc, bj1, w0, dot[1][i], tc, tj1, t[1][i], u);
+				// a pair that is not ok carries a NaN key: rec_insert drops what is not finite
+				const double r[REC_CJ] = {v0.ok ? v0.key : __builtin_nan(""), v1.ok ? v1.key : __builtin_nan("")};
+				nonfinite += (uint32_t)__popcll(__ballot(in0 && !v0.ok)) + (uint32_t)__popcll(__ballot(in1 && !v1.ok));
+				const bool s0 = in0 && v0.ok && rec_better(r[0], j0 + lane, tr, ti);
+				const bool s1 = in1 && v1.ok && rec_better(r[1], j0 + 64 + lane, tr, ti);
+				if (__ballot(s0 || s1))
+					rec_insert<CAP>(a, s_key[wave][i], s_idx[wave][i], &s_cnt[wave][i], c0 + i, r, j0, je, lane, exhits);
+			}
+		}
+	}
+	wave_sync();
+	for (int i = 0; i < nctx; ++i) {
+		const uint32_t n = s_cnt[wave][i];
+		const size_t list = (size_t)(c0 + i) * a.slices + slice;
+		for (uint32_t e = lane; e < n; e += 64) {
+			a.part_raw[list * topn + e] = s_key[wave][i][e];
+			a.part_idx[list * topn + e] = s_idx[wave][i][e];
+		}
+		if (lane == 0) a.part_cnt[list] = n;
+	}
+	if (lane == 0) {
+		if (nonfinite) atomicAdd(&a.counters[0], (unsigned long long)nonfinite);
+		if (exhits) atomicAdd(&a.counters[1], (unsigned long long)exhits);
+	}
+}
+
+struct FinishArgs {
+	const double *ctx_all;        // [tile of ctx][3][f][ctx]
+	uint32_t ctx;
+	const double *qt, *zt, *ut, *base_c, *base_j, *tb_c, *tb_j;
+	uint32_t nB, Mpad;
+	int k, topn;
+	double w0;
+	UcbArgs u;
+	int clip;                     // the returned score clipped to [mn, mx] (a VB model is never of task c)
+	double mn, mx;
+	const int32_t *idx;           // [nB][topn] and [nB]: the merge's results
+	const uint32_t *count;
+	double *key, *score, *var;    // [nB][topn], NaN beyond count
+};
+
+// After the merge (which ordered the slices' lists by key): one thread per returned entry forms the
+// survivor's raw, T and key again -- the same sums in the same order through ucb_pair, so the bits
+// the pair kernel ranked on -- and the returned score from raw.
+__global__ __launch_bounds__(256) void k_ucb_finish(const FinishArgs a)
+{
+	const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (p >= (uint64_t)a.nB * a.topn) return;
+	const uint32_t c = (uint32_t)(p / a.topn), e = (uint32_t)(p % a.topn);
+	if (e >= a.count[c]) {
+		a.key[p] = a.score[p] = a.var[p] = __builtin_nan("");
+		return;
+	}
+	const uint32_t j = (uint32_t)a.idx[p];
+	const int k = a.k;
+	const double *qc = a.ctx_all + (size_t)(c / a.ctx) * 3 * k * a.ctx + c % a.ctx;
+	const double *zc = qc + (size_t)k * a.ctx, *pc = zc + (size_t)k * a.ctx;
+	double dot = 0.0, t = 0.0;
+	for (int f = 0; f < k; ++f) {
+		const size_t o = (size_t)f * a.Mpad + j;
+		dot = __builtin_fma(qc[(size_t)f * a.ctx], a.qt[o], dot);
+		t = __builtin_fma(zc[(size_t)f * a.ctx], a.ut[o], t);
+		t = __builtin_fma(pc[(size_t)f * a.ctx], a.zt[o], t);
+	}
+	const UcbVal v = ucb_pair(a.base_c[c], a.base_j[j], a.w0, dot, a.tb_c[c], a.tb_j[j], t, a.u);
+	a.key[p] = v.key;
+	a.score[p] = a.clip ? clip(v.raw, a.mn, a.mx) : v.raw;
+	a.var[p] = v.T;
+}
+
+// U = Z + P of a candidate set, in place over the P plane the preparation stored
+__global__ __launch_bounds__(256) void k_ucb_u(const double *__restrict__ z, double *__restrict__ pu, size_t n)
+{
+	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+	if (i < n) pu[i] = z[i] + pu[i];
+}
+
+// The context tile of a call whose largest chunk has nB rows. Measured: 8 contexts per
+// wave win wherever the lists matter (topn = 100: 1.5-1.8x) and at k <= 32; 16 win by 9 % at k = 100,
+// topn = 10 once their waves alone fill the chip. VBFM_UCB_CTX = 8 / 16 overrides (tests, probes).
+uint32_t ucb_ctx(size_t nB, int k, int topn)
+{
+	if (const char *env = getenv("VBFM_UCB_CTX")) return atoi(env) == 16 ? (uint32_t)REC_CTX : (uint32_t)UCB_CTX;
+	return topn <= 16 && k >= 64 && nB >= (size_t)REC_CTX * REC_TARGET_WAVES ? (uint32_t)REC_CTX : (uint32_t)UCB_CTX;
+}
+
+// capacities as launch_pairs; the 16-context form keeps k_rec_pairs' workgroups
+hipError_t launch_ucb_pairs(uint32_t ctx, const double *ctx_all, const double *qt, const double *zt, const double *ut,
+                            const double *base_c, const double *base_j, const double *tb_c, const double *tb_j,
+                            const PairArgs &a, const UcbArgs &u, hipStream_t s)
+{
+	if (a.nB == 0) return hipSuccess;
+	const uint32_t waves = (a.nB + ctx - 1) / ctx;
+	const dim3 grid((waves + 3) / 4, a.slices), grid2((waves + 1) / 2, a.slices);
+#define UCB_LAUNCH(CAP, WAVES, CTX, GRID) \
+	k_ucb_pairs<CAP, WAVES, CTX><<<GRID, 64 * WAVES, 0, s>>>(ctx_all, qt, zt, ut, base_c, base_j, tb_c, tb_j, a, u)
+	if (ctx == UCB_CTX) {
+		if (a.topn <= 16) UCB_LAUNCH(16, UCB_WAVES, UCB_CTX, grid);
+		else if (a.topn <= 64) UCB_LAUNCH(64, UCB_WAVES, UCB_CTX, grid);
+		else UCB_LAUNCH(VBFM_REC_MAX_TOPN, UCB_WAVES, UCB_CTX, grid);
+	} else {
+		if (a.topn <= 16) UCB_LAUNCH(16, REC_WAVES, REC_CTX, grid);
+		else if (a.topn <= 64) UCB_LAUNCH(64, REC_WAVES, REC_CTX, grid);
+		else UCB_LAUNCH(VBFM_REC_MAX_TOPN, 2, REC_CTX, grid2);
+	}
+#undef UCB_LAUNCH
+	return hipGetLastError();
+}
+
 uint32_t round_up(uint64_t v, uint32_t to) { return (uint32_t)((v + to - 1) / to * to); }
 
 // Candidate slices of a launch over nB contexts: enough waves to fill the chip when contexts are few
 // (one user against 1e6 items: REC_TARGET_WAVES slices of two steps), one slice when the context
 // waves alone do. VBFM_REC_SLICES overrides (tests, probes); the result does not depend on it.
-uint32_t pick_slices(uint32_t nB, uint32_t M)
+uint32_t pick_slices(uint32_t nB, uint32_t M, uint32_t ctx = REC_CTX)
 {
-	const uint32_t waves = (nB + REC_CTX - 1) / REC_CTX;
+	const uint32_t waves = (nB + ctx - 1) / ctx;
 	const uint32_t most = std::max<uint32_t>(1, std::min<uint32_t>(REC_MAX_SLICES, (M + REC_STEP - 1) / REC_STEP));
 	uint32_t want = waves ? (REC_TARGET_WAVES + waves - 1) / waves : 1;
 	if (const char *env = getenv("VBFM_REC_SLICES")) {
@@ -369,11 +586,69 @@ void launch_prepare(vbfm_model *m, const uint8_t *d_in, uint32_t nr, uint64_t e0
 	if (nr) HIPCHK((launch_group<false, true>(a, 0, m->s)));
 }
 
+// the same with the variance sums: q takes the three planes of a tile (ScoreArgs::q), tb the rows' T_n.
+// base and the Q plane are launch_prepare's bits: the VAR instantiations form the mean by the same
+// expressions from the same values.
+void launch_prepare_var(vbfm_model *m, const uint8_t *d_in, uint32_t nr, uint64_t e0, uint32_t r0, double *base, double *tb,
+                        double *q, uint32_t q_tile)
+{
+	ScoreArgs a = score_args(m, 0);
+	a.row_ptr = (const uint64_t *)d_in;
+	a.ent = (const uint2 *)(d_in + ((size_t)nr + 1) * 8);
+	a.ent_base = e0;
+	a.mean = base;
+	a.var = tb;
+	a.n = nr;
+	a.row0 = r0;
+	a.q = q;
+	a.q_tile = q_tile;
+	if (nr) HIPCHK((launch_group<true, true>(a, 0, m->s)));
+}
+
+const char *kind_name(int32_t kind)
+{
+	switch (kind) {
+	case VBFM_MODEL_VB: return "VBFM_MODEL_VB";
+	case VBFM_MODEL_VB_ONLINE: return "VBFM_MODEL_VB_ONLINE";
+	case VBFM_MODEL_ALS: return "VBFM_MODEL_ALS";
+	case VBFM_MODEL_MCMC_DRAW: return "VBFM_MODEL_MCMC_DRAW";
+	case VBFM_MODEL_MCMC_CHAIN: return "VBFM_MODEL_MCMC_CHAIN";
+	}
+	return "an unknown kind";
+}
+
+// ranking by a confidence bound needs the posterior variances
+void require_variance(const vbfm_model *m, const char *who)
+{
+	if (!m->info.has_variance || !m->ms_w || !m->ms_v)
+		throw std::string(who) + ": a model of kind " + kind_name(m->info.kind) +
+		    " holds no posterior variances; ranking by mean + beta * sd takes a VB model (VBFM_MODEL_VB, VBFM_MODEL_VB_ONLINE)";
+}
+
 void require_model(const vbfm_model *m, const char *who)
 {
 	if (m->info.num_factor > REC_MAX_K)
 		throw std::string(who) + ": num_factor = " + std::to_string(m->info.num_factor) + " is beyond the limit of " +
 		    std::to_string(REC_MAX_K);
+}
+
+// the exclusion lists of a call (`who` names it): positions from 0, monotone, every list ascending and
+// inside the candidate set
+void check_exclusions(const std::string &who, uint32_t B, uint32_t M, const uint64_t *excl_ptr, const uint32_t *excl_idx)
+{
+	if (!excl_ptr) return;
+	if (B && excl_ptr[0] != 0) throw who + ": excl_ptr does not start at 0";
+	for (uint32_t r = 0; r < B; r++) {
+		if (excl_ptr[r + 1] < excl_ptr[r]) throw who + ": excl_ptr is not monotone at context row " + std::to_string(r);
+		if (excl_ptr[r + 1] > excl_ptr[r] && !excl_idx) throw who + ": exclusions without excl_idx";
+		for (uint64_t p = excl_ptr[r]; p < excl_ptr[r + 1]; p++) {
+			if (excl_idx[p] >= M)
+				throw who + ": the exclusion list of context row " + std::to_string(r) + " holds candidate index " +
+				    std::to_string(excl_idx[p]) + ", but the candidate set has " + std::to_string(M) + " rows";
+			if (p > excl_ptr[r] && excl_idx[p] < excl_idx[p - 1])
+				throw who + ": the exclusion list of context row " + std::to_string(r) + " is not sorted";
+		}
+	}
 }
 
 // event pairs around the phases of the chunk in a slot
@@ -401,47 +676,58 @@ struct vbfm_candidates {
 	int k = 0;
 	double *qt = nullptr;         // [k][Mpad], zero beyond M
 	double *base = nullptr;       // [Mpad]
+	// vbfm_candidates_create_var only: Z and U = Z + P, the planes behind qt in its allocation
+	// ([3][k][Mpad]), and the rows' T_n
+	double *zt = nullptr, *ut = nullptr;
+	double *tb = nullptr;         // [Mpad]
 };
 
-extern "C" {
+namespace {
 
-uint32_t vbfm_candidates_count(const vbfm_candidates *c) { return c ? c->M : 0; }
-
-void vbfm_candidates_destroy(vbfm_candidates *c)
+// vbfm_candidates_create (var = false: what it always allocated and launched) and _create_var
+int candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids, bool var, const std::string &who)
 {
-	if (!c) return;
-	(void)hipSetDevice(c->dev);
-	dfree(c->qt);
-	dfree(c->base);
-	delete c;
-}
-
-int vbfm_candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids)
-{
-	if (!m) return mfail(nullptr, "vbfm_candidates_create: null model");
-	if (!out || !rows) return mfail(m, "vbfm_candidates_create: null argument");
+	if (!m) return mfail(nullptr, who + ": null model");
+	if (!out || !rows) return mfail(m, who + ": null argument");
 	*out = nullptr;
 	if (m->info.kind == VBFM_MODEL_MCMC_CHAIN)
-		return mfail(m, "vbfm_candidates_create: a chain of draws (VBFM_MODEL_MCMC_CHAIN) is scored, not ranked: "
+		return mfail(m, who + ": a chain of draws (VBFM_MODEL_MCMC_CHAIN) is scored, not ranked: "
 		                "recommendation takes a model of one set of parameters");
 	vbfm_candidates *c = nullptr;
 	const int rc = mguarded(m, [&] {
-		if (unknown_ids != 0 && unknown_ids != 1)
-			throw std::string("vbfm_candidates_create: unknown_ids is 0 (refuse) or 1 (skip)");
-		require_model(m, "vbfm_candidates_create");
-		if (rows->num_rows > 0x7fffff00u) throw std::string("vbfm_candidates_create: too many candidate rows");
+		if (var) require_variance(m, who.c_str());
+		if (unknown_ids != 0 && unknown_ids != 1) throw who + ": unknown_ids is 0 (refuse) or 1 (skip)";
+		require_model(m, who.c_str());
+		if (rows->num_rows > 0x7fffff00u) throw who + ": too many candidate rows";
 		size_t need_in = 0, need_rows = 0;
-		const std::vector<ChunkPlan> plan = plan_chunks(rows, VBFM_SCORE_CHUNK_DEFAULT, "vbfm_candidates_create", &need_in, &need_rows);
+		const std::vector<ChunkPlan> plan = plan_chunks(rows, VBFM_SCORE_CHUNK_DEFAULT, who, &need_in, &need_rows);
+		const uint32_t Mpad = round_up(rows->num_rows, REC_STEP);
+		const int k = m->info.num_factor;
+		const size_t planes = var ? 3 : 1, nq = planes * (size_t)k * Mpad;
+		if (var) {   // three times a plain set: its bytes against the free memory before anything is allocated
+			const uint64_t bytes = ((uint64_t)nq + 2 * (uint64_t)Mpad) * 8;
+			size_t free_b = 0, total_b = 0;
+			HIPCHK(hipMemGetInfo(&free_b, &total_b));
+			if (bytes > (uint64_t)free_b)
+				throw who + ": " + std::to_string(rows->num_rows) + " candidates of num_factor = " + std::to_string(k) + " need " +
+				    std::to_string(bytes) + " bytes of device memory, " + std::to_string((uint64_t)free_b) + " are free";
+		}
 		staging_reserve(m, need_in, 0);
 		c = new vbfm_candidates();
 		c->m = m;
 		c->dev = m->dev;
 		c->M = rows->num_rows;
-		c->Mpad = round_up(c->M, REC_STEP);
-		c->k = m->info.num_factor;
-		c->qt = dalloc<double>((size_t)c->k * c->Mpad);
+		c->Mpad = Mpad;
+		c->k = k;
+		c->qt = dalloc<double>(nq);
 		c->base = dalloc<double>(c->Mpad);
-		if ((size_t)c->k * c->Mpad) HIPCHK(hipMemsetAsync(c->qt, 0, (size_t)c->k * c->Mpad * 8, m->s));
+		if (var) {
+			c->zt = c->qt + (size_t)k * Mpad;
+			c->ut = c->zt + (size_t)k * Mpad;
+			c->tb = dalloc<double>(c->Mpad);
+			if (c->Mpad) HIPCHK(hipMemsetAsync(c->tb, 0, (size_t)c->Mpad * 8, m->s));
+		}
+		if (nq) HIPCHK(hipMemsetAsync(c->qt, 0, nq * 8, m->s));
 		if (c->Mpad) HIPCHK(hipMemsetAsync(c->base, 0, (size_t)c->Mpad * 8, m->s));
 		flags_reset(m);
 		// one chunk at a time through slot 0: a candidate set is prepared once
@@ -450,7 +736,14 @@ int vbfm_candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr 
 			const uint32_t nr = p.r1 - p.r0;
 			const size_t bytes = stage_rows(sl.h_in, rows, p.r0, nr);
 			HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, bytes, hipMemcpyHostToDevice, m->s));
-			launch_prepare(m, sl.d_in, nr, rows->row_ptr[p.r0], p.r0, c->base + p.r0, c->qt + p.r0, c->Mpad);
+			if (var) launch_prepare_var(m, sl.d_in, nr, rows->row_ptr[p.r0], p.r0, c->base + p.r0, c->tb + p.r0, c->qt + p.r0, c->Mpad);
+			else launch_prepare(m, sl.d_in, nr, rows->row_ptr[p.r0], p.r0, c->base + p.r0, c->qt + p.r0, c->Mpad);
+			HIPCHK(hipStreamSynchronize(m->s));
+		}
+		if (var && (size_t)k * Mpad) {   // the P plane becomes U = Z + P, rounded once
+			const size_t n = (size_t)k * Mpad;
+			k_ucb_u<<<(unsigned)((n + 255) / 256), 256, 0, m->s>>>(c->zt, c->ut, n);
+			HIPCHK(hipGetLastError());
 			HIPCHK(hipStreamSynchronize(m->s));
 		}
 		const ScoreFlags f = flags_read(m);
@@ -462,6 +755,32 @@ int vbfm_candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr 
 	}
 	*out = c;
 	return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t vbfm_candidates_count(const vbfm_candidates *c) { return c ? c->M : 0; }
+
+void vbfm_candidates_destroy(vbfm_candidates *c)
+{
+	if (!c) return;
+	(void)hipSetDevice(c->dev);
+	dfree(c->qt);
+	dfree(c->base);
+	dfree(c->tb);
+	delete c;
+}
+
+int vbfm_candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids)
+{
+	return candidates_create(out, m, rows, unknown_ids, false, "vbfm_candidates_create");
+}
+
+int vbfm_candidates_create_var(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids)
+{
+	return candidates_create(out, m, rows, unknown_ids, true, "vbfm_candidates_create_var");
 }
 
 int vbfm_recommend(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *contexts, const uint64_t *excl_ptr,
@@ -486,20 +805,7 @@ int vbfm_recommend(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *con
 		const size_t topn = (size_t)o.topn;
 		const int k = cs->k;
 		vbfm_recommend_stats out = {};
-		if (excl_ptr) {
-			if (B && excl_ptr[0] != 0) throw std::string("vbfm_recommend: excl_ptr does not start at 0");
-			for (uint32_t r = 0; r < B; r++) {
-				if (excl_ptr[r + 1] < excl_ptr[r]) throw std::string("vbfm_recommend: excl_ptr is not monotone at context row ") + std::to_string(r);
-				if (excl_ptr[r + 1] > excl_ptr[r] && !excl_idx) throw std::string("vbfm_recommend: exclusions without excl_idx");
-				for (uint64_t p = excl_ptr[r]; p < excl_ptr[r + 1]; p++) {
-					if (excl_idx[p] >= M)
-						throw "vbfm_recommend: the exclusion list of context row " + std::to_string(r) + " holds candidate index " +
-						    std::to_string(excl_idx[p]) + ", but the candidate set has " + std::to_string(M) + " rows";
-					if (p > excl_ptr[r] && excl_idx[p] < excl_idx[p - 1])
-						throw "vbfm_recommend: the exclusion list of context row " + std::to_string(r) + " is not sorted";
-				}
-			}
-		}
+		check_exclusions("vbfm_recommend", B, M, excl_ptr, excl_idx);
 		size_t need_in = 0, need_rows = 0;
 		const std::vector<ChunkPlan> plan = plan_chunks(contexts, o.chunk_bytes ? o.chunk_bytes : VBFM_SCORE_CHUNK_DEFAULT,
 		                                                "vbfm_recommend", &need_in, &need_rows);
@@ -583,6 +889,159 @@ int vbfm_recommend(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *con
 			g.idx = (int32_t *)(sl.d_out + (size_t)nr * topn);
 			g.count = (uint32_t *)(g.idx + (size_t)nr * topn);
 			HIPCHK(launch_merge(g, m->s));
+			HIPCHK(hipEventRecord(ev[3], m->s));
+			HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, out_doubles(nr) * 8, hipMemcpyDeviceToHost, m->s));
+			HIPCHK(hipEventRecord(sl.ev[SEV_DONE], m->s));
+			out.pairs += (uint64_t)nr * M;
+		}
+		for (size_t i = plan.size() >= 2 ? plan.size() - 2 : 0; i < plan.size(); i++) drain(i);
+		const ScoreFlags f = flags_read(m);
+		if (f.first != ~0ull && !o.unknown_ids) throw unknown_msg(m, f.first >> 32, (uint32_t)f.first);
+		unsigned long long cnt[2];
+		HIPCHK(hipMemcpyAsync(cnt, counters, 16, hipMemcpyDeviceToHost, m->s));
+		HIPCHK(hipStreamSynchronize(m->s));
+		out.n_chunks = (uint32_t)plan.size();
+		out.nonfinite_pairs = cnt[0];
+		out.excluded_hits = cnt[1];
+		out.ms_total = (wall_s() - t_begin) * 1e3;
+		if (st) *st = out;
+	});
+}
+
+// vbfm_recommend's staging and phases with the variance sums beside the means: the preparation's
+// VAR form, k_ucb_pairs, the merge on key and k_ucb_finish for the returned values
+int vbfm_recommend_ucb(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *contexts, const uint64_t *excl_ptr,
+                       const uint32_t *excl_idx, const vbfm_recommend_ucb_opts *opts, int32_t *idx, double *key,
+                       double *score, double *var, uint32_t *count, vbfm_recommend_stats *st)
+{
+	const std::string who = "vbfm_recommend_ucb";
+	if (!m) return mfail(nullptr, who + ": null model");
+	if (!cs || !contexts || !opts) return mfail(m, who + ": null argument");
+	if (m->info.kind == VBFM_MODEL_MCMC_CHAIN)
+		return mfail(m, who + ": a chain of draws (VBFM_MODEL_MCMC_CHAIN) is scored, not ranked: "
+		                "recommendation takes a model of one set of parameters");
+	return mguarded(m, [&] {
+		const double t_begin = wall_s();
+		const vbfm_recommend_ucb_opts o = *opts;
+		require_variance(m, who.c_str());
+		if (cs->m != m) throw who + ": the candidate set was made from another model";
+		if (!cs->tb) throw who + ": the candidate set holds no variance sums (it was made by vbfm_candidates_create; use vbfm_candidates_create_var)";
+		if (o.topn < 1 || o.topn > VBFM_REC_MAX_TOPN)
+			throw who + ": topn = " + std::to_string(o.topn) + " is outside 1 .. " + std::to_string(VBFM_REC_MAX_TOPN);
+		if (!std::isfinite(o.beta)) throw who + ": beta = " + std::to_string(o.beta) + " is not a finite number";
+		if (o.noise != 0 && o.noise != 1) throw who + ": noise is 0 or 1";
+		require_model(m, who.c_str());
+		if (o.unknown_ids != 0 && o.unknown_ids != 1) throw who + ": unknown_ids is 0 (refuse) or 1 (skip)";
+		const uint32_t B = contexts->num_rows, M = cs->M;
+		if (B && (!idx || !count)) throw who + ": null result array";
+		const size_t topn = (size_t)o.topn;
+		const int k = cs->k;
+		vbfm_recommend_stats out = {};
+		check_exclusions(who, B, M, excl_ptr, excl_idx);
+		size_t need_in = 0, need_rows = 0;
+		const std::vector<ChunkPlan> plan = plan_chunks(contexts, o.chunk_bytes ? o.chunk_bytes : VBFM_SCORE_CHUNK_DEFAULT, who,
+		                                                &need_in, &need_rows);
+		const uint32_t ctx = ucb_ctx(need_rows, k, o.topn);
+		// a chunk in a slot: [row_ptr slice | entries | excl_ptr slice | excl_idx slice]; its results
+		// [key | score | var | idx | count]
+		size_t need_part = 0;
+		for (const ChunkPlan &p : plan) {
+			const uint32_t nr = p.r1 - p.r0;
+			if (excl_ptr) {
+				const size_t rows_bytes = ((size_t)nr + 1) * 8 + (contexts->row_ptr[p.r1] - contexts->row_ptr[p.r0]) * 8;
+				need_in = std::max(need_in, rows_bytes + ((size_t)nr + 1) * 8 + (excl_ptr[p.r1] - excl_ptr[p.r0]) * 4);
+			}
+			need_part = std::max(need_part, (size_t)nr * pick_slices(nr, M, ctx));
+		}
+		const auto out_doubles = [&](size_t nr) { return 3 * nr * topn + (nr * topn * 4 + nr * 4 + 7) / 8; };
+		staging_reserve(m, need_in, out_doubles(need_rows));
+		const size_t rows_pad = round_up(need_rows, ctx);
+		DevScratch<double> base_c(rows_pad), tb_c(rows_pad), qc(3 * rows_pad * (size_t)k), part_key(need_part * topn);
+		DevScratch<uint32_t> part_idx(need_part * topn), part_cnt(need_part);
+		DevScratch<unsigned long long> counters(2);
+		HIPCHK(hipMemsetAsync(counters, 0, 16, m->s));
+		HIPCHK(hipMemsetAsync(base_c, 0, rows_pad * 8, m->s));
+		HIPCHK(hipMemsetAsync(tb_c, 0, rows_pad * 8, m->s));
+		flags_reset(m);
+		PhaseEvents pe;
+		UcbArgs u;
+		u.s0 = m->info.k0 ? m->info.sigma_0_dash : 0.0;
+		u.na = o.noise ? 1.0 / m->info.alpha : 0.0;
+		u.beta = o.beta;
+		auto drain = [&](size_t i) {
+			vbfm_model::Slot &sl = m->slot[i & 1];
+			HIPCHK(hipEventSynchronize(sl.ev[SEV_DONE]));
+			const size_t r0 = plan[i].r0, nr = plan[i].r1 - plan[i].r0, n = nr * topn;
+			if (key) memcpy(key + r0 * topn, sl.h_out, n * 8);
+			if (score) memcpy(score + r0 * topn, sl.h_out + n, n * 8);
+			if (var) memcpy(var + r0 * topn, sl.h_out + 2 * n, n * 8);
+			memcpy(idx + r0 * topn, sl.h_out + 3 * n, n * 4);
+			memcpy(count + r0, (const uint8_t *)(sl.h_out + 3 * n) + n * 4, nr * 4);
+			out.ms_prepare += elapsed(pe.ev[i & 1][0], pe.ev[i & 1][1]);
+			out.ms_pairs += elapsed(pe.ev[i & 1][1], pe.ev[i & 1][2]);
+			out.ms_merge += elapsed(pe.ev[i & 1][2], pe.ev[i & 1][3]);
+		};
+		for (size_t i = 0; i < plan.size(); i++) {
+			vbfm_model::Slot &sl = m->slot[i & 1];
+			if (i >= 2) drain(i - 2);   // the slot's previous chunk has left both of its buffers
+			const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
+			size_t bytes = stage_rows(sl.h_in, contexts, r0, nr);
+			const size_t excl_off = bytes;
+			uint64_t xe0 = 0, nx = 0;
+			if (excl_ptr) {
+				xe0 = excl_ptr[r0];
+				nx = excl_ptr[r0 + nr] - xe0;
+				memcpy(sl.h_in + bytes, excl_ptr + r0, ((size_t)nr + 1) * 8);
+				bytes += ((size_t)nr + 1) * 8;
+				if (nx) memcpy(sl.h_in + bytes, excl_idx + xe0, nx * 4);
+				bytes += nx * 4;
+			}
+			HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, bytes, hipMemcpyHostToDevice, m->s_copy));
+			HIPCHK(hipEventRecord(sl.ev[SEV_C1], m->s_copy));
+			HIPCHK(hipStreamWaitEvent(m->s, sl.ev[SEV_C1], 0));
+			hipEvent_t *ev = pe.ev[i & 1];
+			HIPCHK(hipEventRecord(ev[0], m->s));
+			launch_prepare_var(m, sl.d_in, nr, contexts->row_ptr[r0], r0, base_c, tb_c, qc, ctx);
+			HIPCHK(hipEventRecord(ev[1], m->s));
+			PairArgs a = {};
+			a.nB = nr; a.M = M; a.Mpad = cs->Mpad;
+			a.k = k;
+			a.w0 = m->info.k0 ? m->info.w0_or_mu0 : 0.0;
+			a.topn = o.topn;
+			a.slices = pick_slices(nr, M, ctx);
+			a.slice_len = std::max<uint32_t>(REC_STEP, round_up(((uint64_t)M + a.slices - 1) / a.slices, REC_STEP));
+			if (excl_ptr) {
+				a.excl_ptr = (const uint64_t *)(sl.d_in + excl_off);
+				a.excl_idx = (const uint32_t *)(sl.d_in + excl_off + ((size_t)nr + 1) * 8);
+				a.excl_base = xe0;
+			}
+			a.part_raw = part_key; a.part_idx = part_idx; a.part_cnt = part_cnt;
+			a.counters = counters;
+			HIPCHK(launch_ucb_pairs(ctx, qc, cs->qt, cs->zt, cs->ut, base_c, cs->base, tb_c, cs->tb, a, u, m->s));
+			HIPCHK(hipEventRecord(ev[2], m->s));
+			const size_t n = (size_t)nr * topn;
+			MergeArgs g = {};
+			g.part_raw = part_key; g.part_idx = part_idx; g.part_cnt = part_cnt;
+			g.nB = nr; g.slices = a.slices; g.topn = o.topn;
+			g.link = 0;                       // the lists' keys as they are; k_ucb_finish forms what is returned
+			g.score = sl.d_out;
+			g.idx = (int32_t *)(sl.d_out + 3 * n);
+			g.count = (uint32_t *)(g.idx + n);
+			HIPCHK(launch_merge(g, m->s));
+			FinishArgs fa = {};
+			fa.ctx_all = qc; fa.ctx = ctx;
+			fa.qt = cs->qt; fa.zt = cs->zt; fa.ut = cs->ut;
+			fa.base_c = base_c; fa.base_j = cs->base; fa.tb_c = tb_c; fa.tb_j = cs->tb;
+			fa.nB = nr; fa.Mpad = cs->Mpad; fa.k = k; fa.topn = o.topn;
+			fa.w0 = a.w0; fa.u = u;
+			fa.clip = o.clip != 0;
+			fa.mn = m->info.min_target; fa.mx = m->info.max_target;
+			fa.idx = g.idx; fa.count = g.count;
+			fa.key = sl.d_out; fa.score = sl.d_out + n; fa.var = sl.d_out + 2 * n;
+			if (n) {
+				k_ucb_finish<<<(unsigned)((n + 255) / 256), 256, 0, m->s>>>(fa);
+				HIPCHK(hipGetLastError());
+			}
 			HIPCHK(hipEventRecord(ev[3], m->s));
 			HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, out_doubles(nr) * 8, hipMemcpyDeviceToHost, m->s));
 			HIPCHK(hipEventRecord(sl.ev[SEV_DONE], m->s));

@@ -38,7 +38,9 @@ struct ScoreArgs {
 	uint32_t row0;                // the call's index of row 0 of this launch (ScoreFlags::first)
 	ScoreFlags *flags;
 	// QOUT only: the per-factor sums qe of row r go to q[(r / q_tile) * k * q_tile + f * q_tile +
-	// r % q_tile] -- factor-major inside tiles of q_tile rows (one tile of all rows: [f][q_tile])
+	// r % q_tile] -- factor-major inside tiles of q_tile rows (one tile of all rows: [f][q_tile]).
+	// VAR and QOUT: a tile is three such planes, [3][k][q_tile] -- qe, then z (sum sigma_v x^2), then
+	// q (sum mu_v^2 x^2) -- and the row's T_n goes to var
 	double *q;
 	uint32_t q_tile;
 };
@@ -116,7 +118,8 @@ template <int G> DEVI double group_sum(double v)
 // that is the wave kernels' result bit for bit, from 64 / G times as many rows per wave.
 // VAR = false reads the means ([j*k + f], 8 B per factor); VAR = true the {mu, sigma} pairs, once
 // for both outputs. QOUT also stores every per-factor sum qe (ScoreArgs::q): the row preparation of
-// vbfm_recommend.hip; the other instantiations are as they were.
+// vbfm_recommend.hip, with VAR the sums z and q beside it (vbfm_recommend_ucb); the other
+// instantiations are as they were.
 template <int G, int KP, bool VAR, bool QOUT = false>
 __global__ __launch_bounds__(256) void k_score(const ScoreArgs a)
 {
@@ -187,11 +190,23 @@ __global__ __launch_bounds__(256) void k_score(const ScoreArgs a)
 				}
 			}
 		}
-		if constexpr (QOUT) {
+		if constexpr (QOUT && !VAR) {
 			const size_t qbase = (size_t)(r / a.q_tile) * k * a.q_tile + r % a.q_tile;
 #pragma unroll
 			for (int c = 0; c < KP; ++c)
 				if ((int)gl + 64 * c < k) a.q[qbase + (size_t)((int)gl + 64 * c) * a.q_tile] = qe[c];
+		}
+		if constexpr (QOUT && VAR) {
+			const size_t plane = (size_t)k * a.q_tile;
+			const size_t qbase = (size_t)(r / a.q_tile) * 3 * plane + r % a.q_tile;
+#pragma unroll
+			for (int c = 0; c < KP; ++c)
+				if ((int)gl + 64 * c < k) {
+					const size_t at = qbase + (size_t)((int)gl + 64 * c) * a.q_tile;
+					a.q[at] = qe[c];
+					a.q[at + plane] = z[c];
+					a.q[at + 2 * plane] = q[c];
+				}
 		}
 		double e = 0.0, t = 0.0;
 #pragma unroll

@@ -18,7 +18,8 @@
 //   * -save_model FILE (every method: the parameters alone, after the last iteration) and the
 //     predict-only mode -load_model FILE -test T -out P [-out_var V] (no -train; no reference
 //     counterpart: the reference predicts only the test set attached while training); with
-//     -candidates ITEMS -topn N [-exclude X] that mode ranks the rows of ITEMS for every row of T;
+//     -candidates ITEMS -topn N [-exclude X] that mode ranks the rows of ITEMS for every row of T,
+//     with -ucb BETA [-ucb_noise 1] [-out_rank_var V] on mean + BETA * sd (a model with variances);
 //   * -method mcmc -save_model FILE -chain B,T keeps the draws of iterations B, B + T, ... and writes
 //     them as one model whose -load_model scores are the chain average (what -out reports), -out_var
 //     the spread across the draws.
@@ -40,6 +41,7 @@
 // Every library handle and file is owned (Owned<T>), so a throw anywhere releases it.
 #include "../../include/vbfm.h"
 
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -79,6 +81,8 @@
 #pragma weak vbfm_candidates_count
 #pragma weak vbfm_candidates_destroy
 #pragma weak vbfm_recommend
+#pragma weak vbfm_candidates_create_var
+#pragma weak vbfm_recommend_ucb
 #pragma weak vbfm_chain_create
 #pragma weak vbfm_chain_add
 #pragma weak vbfm_chain_count
@@ -121,8 +125,9 @@ public:
 	}
 	static bool parse_name(std::string &s)
 	{
+		if (s.size() > 1 && s[0] == '-' && (isdigit((unsigned char)s[1]) || s[1] == '.')) return false;   // a negative number is a value (-ucb -1.5)
 		if (s.size() > 0 && s[0] == '-') {
-			s = (s.size() > 1 && s[1] == '-') ? s.substr(2) : s.substr(1);
+			s =(s.size() > 1 && s[1] == '-') ? s.substr(2) : s.substr(1);
 			return true;
 		}
 		return false;
@@ -1029,10 +1034,16 @@ static void run_score(const ScoreRun &r)
 // Line r of P: the context's "index:score" pairs, best first, scores at 17 digits and as -out of a
 // scoring run would print them (clipped; task c: probabilities); an empty line when nothing is
 // returned. Line r of X: candidate indices (0-based rows of ITEMS) never to return, in any order.
+// With -ucb BETA [-ucb_noise 1] [-out_rank_var V] the ranking is on mean + BETA * sd
+// (vbfm_recommend_ucb; a model with variances); P is as before and V holds, in P's layout, the
+// survivors' variance terms T.
 struct RecommendRun {
 	std::string model_file, context_file, item_file, out_file, exclude_file;
 	int32_t device, topn;
 	bool skip_unknown;
+	bool ucb = false, ucb_noise = false;
+	double beta = 0.0;
+	std::string rank_var_file;
 };
 
 static bool have_recommender()
@@ -1042,7 +1053,8 @@ static bool have_recommender()
 
 static void run_recommend(const RecommendRun &r)
 {
-	if (!have_recommender()) throw std::string("this build has no scorer");
+	if (!have_recommender() || (r.ucb && !(vbfm_candidates_create_var && vbfm_recommend_ucb)))
+		throw std::string("this build has no scorer");
 	Data ctx, items;
 	load(r.context_file, ctx, "contexts");
 	load(r.item_file, items, "candidates");
@@ -1073,20 +1085,33 @@ static void run_recommend(const RecommendRun &r)
 	}
 	const Owned<vbfm_model> model = load_model(r.model_file, r.device);
 	vbfm_model *m = model.get();
+	if (r.ucb) {
+		vbfm_model_info info;
+		if (vbfm_model_info_get(m, &info) != 0) throw std::string(vbfm_model_last_error(m));
+		if (!info.has_variance)
+			throw std::string("-ucb needs a model with variances (-method vb or vb_online): " + r.model_file + " holds none");
+	}
 	const vbfm_csr item_rows{items.h.num_rows, items.h.nnz, items.h.row_ptr, items.h.row_ent};
 	vbfm_candidates *cs = nullptr;
-	if (vbfm_candidates_create(&cs, m, &item_rows, r.skip_unknown ? 1 : 0) != 0) throw std::string(vbfm_model_last_error(m));
+	if ((r.ucb ? vbfm_candidates_create_var : vbfm_candidates_create)(&cs, m, &item_rows, r.skip_unknown ? 1 : 0) != 0)
+		throw std::string(vbfm_model_last_error(m));
 	const Owned<vbfm_candidates> candidates(cs);   // declared after the model: destroyed before it
 	const vbfm_csr rows{B, ctx.h.nnz, ctx.h.row_ptr, ctx.h.row_ent};
 	const vbfm_recommend_opts o{r.topn, 1, r.skip_unknown ? 1 : 0, 0};
 	const size_t n = (size_t)B * (size_t)std::max(r.topn, 0);
 	std::vector<int32_t> idx(n);
-	std::vector<double> score(n);
+	std::vector<double> score(n), var(r.ucb ? n : 0);
 	std::vector<uint32_t> count(B);
 	vbfm_recommend_stats st;
-	if (vbfm_recommend(m, cs, &rows, xptr.empty() ? nullptr : xptr.data(), xptr.empty() ? nullptr : xidx.data(), &o,
-	                   idx.data(), score.data(), count.data(), &st) != 0)
+	const uint64_t *xp = xptr.empty() ? nullptr : xptr.data();
+	const uint32_t *xi = xptr.empty() ? nullptr : xidx.data();
+	if (r.ucb) {
+		const vbfm_recommend_ucb_opts uo{o.topn, o.clip, o.unknown_ids, o.chunk_bytes, r.beta, r.ucb_noise ? 1 : 0};
+		if (vbfm_recommend_ucb(m, cs, &rows, xp, xi, &uo, idx.data(), nullptr, score.data(), var.data(), count.data(), &st) != 0)
+			throw std::string(vbfm_model_last_error(m));
+	} else if (vbfm_recommend(m, cs, &rows, xp, xi, &o, idx.data(), score.data(), count.data(), &st) != 0) {
 		throw std::string(vbfm_model_last_error(m));
+	}
 	std::cout << "ranked " << st.pairs << " pairs (" << B << " contexts x " << vbfm_candidates_count(cs) << " candidates) in "
 	          << st.ms_total << " ms: prepare " << st.ms_prepare << ", pairs " << st.ms_pairs << ", merge " << st.ms_merge
 	          << " ms on the device";
@@ -1097,6 +1122,13 @@ static void run_recommend(const RecommendRun &r)
 		for (uint32_t e = 0; e < count[c]; e++)
 			fprintf(f.get(), "%s%d:%.17g", e ? " " : "", idx[(size_t)c * r.topn + e], score[(size_t)c * r.topn + e]);
 		fputc('\n', f.get());
+	}
+	if (r.rank_var_file.empty()) return;
+	const Owned<FILE> fv = open_for_writing(r.rank_var_file);
+	for (uint32_t c = 0; c < B; c++) {
+		for (uint32_t e = 0; e < count[c]; e++)
+			fprintf(fv.get(), "%s%d:%.17g", e ? " " : "", idx[(size_t)c * r.topn + e], var[(size_t)c * r.topn + e]);
+		fputc('\n', fv.get());
 	}
 }
 
@@ -1251,6 +1283,16 @@ static void run_load_model(const CmdLine &cmd)
 	if (cmd.has("exclude") && !cmd.has("candidates")) throw std::string("-exclude needs -candidates");
 	if (cmd.has("candidates") && !cmd.has("topn")) throw std::string("-candidates needs -topn");
 	if (cmd.has("candidates") && cmd.has("out_var")) throw std::string("-out_var does not apply to -candidates (variances are not ranked)");
+	if (cmd.has("ucb") && !cmd.has("candidates")) throw std::string("-ucb needs -candidates");
+	if (cmd.has("ucb_noise") && !cmd.has("ucb")) throw std::string("-ucb_noise needs -ucb");
+	if (cmd.has("out_rank_var") && !cmd.has("ucb")) throw std::string("-out_rank_var needs -ucb");
+	double beta = 0.0;
+	if (cmd.has("ucb")) {
+		const std::string b = cmd.get("ucb");
+		char *end = nullptr;
+		beta = strtod(b.c_str(), &end);
+		if (b.empty() || *end || !std::isfinite(beta)) throw std::string("-ucb needs a finite number, not '" + b + "'");
+	}
 	// the task is the file's; a -task that contradicts it is refused
 	int32_t ftask = VBFM_TASK_REGRESSION;
 	if (!have_scorer()) throw std::string("this build has no scorer");
@@ -1267,8 +1309,15 @@ static void run_load_model(const CmdLine &cmd)
 	const std::string unk = cmd.get("unknown_ids", "refuse");
 	if (unk != "refuse" && unk != "skip") throw std::string("-unknown_ids: refuse or skip");
 	if (cmd.has("candidates")) {
-		run_recommend(RecommendRun{cmd.get("load_model"), cmd.get("test"), cmd.get("candidates"), cmd.get("out"), cmd.get("exclude"),
-		                           (int32_t)cmd.geti("device", 0), (int32_t)cmd.geti("topn", 0), unk == "skip"});
+		RecommendRun run{cmd.get("load_model"), cmd.get("test"), cmd.get("candidates"), cmd.get("out"), cmd.get("exclude"),
+		                 (int32_t)cmd.geti("device", 0), (int32_t)cmd.geti("topn", 0), unk == "skip"};
+		if (cmd.has("ucb")) {
+			run.beta = beta;
+			run.ucb = true;
+			run.ucb_noise = cmd.geti("ucb_noise", 0) != 0;
+			run.rank_var_file = cmd.get("out_rank_var");
+		}
+		run_recommend(run);
 		return;
 	}
 	run_score(ScoreRun{cmd.get("load_model"), cmd.get("test"), cmd.get("out"), cmd.get("out_var"),
@@ -1375,6 +1424,9 @@ int main(int argc, char **argv)
 		const std::string p_cand = cmd.reg("candidates", "with -load_model: rank the rows of this file for every row of -test and write the best -topn per row to -out as index:score pairs (targets are ignored)");
 		const std::string p_topn = cmd.reg("topn", "with -candidates: entries to return per row of -test (1..128)");
 		const std::string p_excl = cmd.reg("exclude", "with -candidates: line r lists the candidate indices (0-based rows of -candidates) never to return for row r of -test");
+		const std::string p_ucb = cmd.reg("ucb", "with -candidates: rank on mean + BETA * sd of the pair's row (vb and vb_online models; a negative BETA ranks on a lower bound); -out still holds the scores");
+		const std::string p_ucbn = cmd.reg("ucb_noise", "with -ucb: 1 = sd is of y (T + 1/alpha), 0 (default) = of the model's mean (T)");
+		const std::string p_orv = cmd.reg("out_rank_var", "with -ucb: the returned entries' variance terms T as index:T pairs, in the layout of -out");
 		if (cmd.has(p_help) || argc == 1) { cmd.print_help(); return 0; }
 		cmd.check();
 
@@ -1385,6 +1437,8 @@ int main(int argc, char **argv)
 		if (cmd.has(p_outvar) || cmd.has(p_unknown)) throw std::string("-out_var and -unknown_ids belong to -load_model");
 		if (cmd.has(p_cand) || cmd.has(p_topn) || cmd.has(p_excl))
 			throw std::string("-candidates, -topn and -exclude belong to -load_model");
+		if (cmd.has(p_ucb) || cmd.has(p_ucbn) || cmd.has(p_orv))
+			throw std::string("-ucb, -ucb_noise and -out_rank_var belong to -load_model");
 
 		const uint32_t seed = cmd.has(p_seed) ? (uint32_t)cmd.geti(p_seed, 0) : (uint32_t)time(NULL);
 		const std::string method = cmd.get(p_method, "mcmc");

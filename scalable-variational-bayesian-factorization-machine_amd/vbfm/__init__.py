@@ -214,6 +214,11 @@ class RecommendOpts(C.Structure):
     _fields_ = [("topn", C.c_int32), ("clip", C.c_int32), ("unknown_ids", C.c_int32), ("chunk_bytes", C.c_uint64)]
 
 
+class RecommendUcbOpts(C.Structure):
+    """vbfm_recommend_ucb_opts: RecommendOpts, then beta and noise."""
+    _fields_ = RecommendOpts._fields_ + [("beta", C.c_double), ("noise", C.c_int32)]
+
+
 class RecommendStats(C.Structure):
     _fields_ = [("n_chunks", C.c_uint32), ("pairs", C.c_uint64), ("nonfinite_pairs", C.c_uint64),
                 ("excluded_hits", C.c_uint64), ("ms_prepare", C.c_double), ("ms_pairs", C.c_double),
@@ -240,7 +245,7 @@ EXPORTS = ["vbfm_abi_version", "vbfm_last_error", "vbfm_create", "vbfm_destroy",
            "vbfm_model_destroy", "vbfm_score", "vbfm_score_device",
            "vbfm_synth_binarize", "vbfm_mcmc_class_info", "vbfm_model_file_task", "vbfm_model_write_host_task",
            "vbfm_model_task", "vbfm_candidates_create", "vbfm_candidates_count", "vbfm_candidates_destroy",
-           "vbfm_recommend",
+           "vbfm_recommend", "vbfm_candidates_create_var", "vbfm_recommend_ucb",
            "vbfm_model_file_draws", "vbfm_model_write_host_chain", "vbfm_model_read_host_draw", "vbfm_model_num_draws",
            "vbfm_model_draw_scalars", "vbfm_chain_create", "vbfm_chain_add", "vbfm_chain_count", "vbfm_chain_save",
            "vbfm_model_from_chain", "vbfm_chain_destroy", "vbfm_chain_last_error"]
@@ -351,6 +356,9 @@ def lib():
         L.vbfm_candidates_destroy.restype = None
         L.vbfm_recommend.argtypes = [V, V, C.POINTER(Csr), P_u64, P_u32, C.POINTER(RecommendOpts),
                                      C.POINTER(C.c_int32), P_f64, P_u32, C.POINTER(RecommendStats)]
+        L.vbfm_candidates_create_var.argtypes = [C.POINTER(V), V, C.POINTER(Csr), C.c_int32]
+        L.vbfm_recommend_ucb.argtypes = [V, V, C.POINTER(Csr), P_u64, P_u32, C.POINTER(RecommendUcbOpts),
+                                         C.POINTER(C.c_int32), P_f64, P_f64, P_f64, P_u32, C.POINTER(RecommendStats)]
         L.vbfm_model_file_draws.argtypes = [C.c_char_p, P_u32]
         L.vbfm_model_write_host_chain.argtypes = [C.c_char_p, C.POINTER(ModelInfo), C.c_int32, C.c_uint32,
                                                   C.POINTER(McmcParams)]
@@ -1166,12 +1174,14 @@ class Model:
         self.last_stats = st.as_dict()
         return (mean, var) if variance else mean
 
-    def candidates(self, data, unknown_ids="refuse"):
+    def candidates(self, data, unknown_ids="refuse", variance=False):
         """The rows of `data` (as score takes them) prepared once on the device as a candidate set
-        for recommend. Close it before the model."""
+        for recommend; with variance=True (VB kinds) also the variance sums recommend_ucb needs,
+        at three times the device memory. Close it before the model."""
         rows, _keep = self._rows(data)
         h = C.c_void_p()
-        self._mcheck(lib().vbfm_candidates_create(C.byref(h), self._m, C.byref(rows), UNKNOWN_IDS[unknown_ids]))
+        create = lib().vbfm_candidates_create_var if variance else lib().vbfm_candidates_create
+        self._mcheck(create(C.byref(h), self._m, C.byref(rows), UNKNOWN_IDS[unknown_ids]))
         return Candidates(h, self)
 
     def recommend(self, contexts, candidates, topn, exclude=None, clip=True, unknown_ids="refuse", chunk_bytes=0):
@@ -1182,23 +1192,7 @@ class Model:
         candidate indices (ascending) per context, or a (ptr, idx) pair."""
         rows, _keep = self._rows(contexts)
         B, topn = rows.num_rows, int(topn)
-        xp = xi = None
-        if exclude is not None:
-            if isinstance(exclude, tuple) and len(exclude) == 2:
-                xp = np.ascontiguousarray(exclude[0], dtype=np.uint64)
-                xi = np.ascontiguousarray(exclude[1], dtype=np.uint32)
-            else:
-                if len(exclude) != B:
-                    raise VbfmError("exclude holds %d lists for %d contexts" % (len(exclude), B))
-                xp = np.zeros(B + 1, dtype=np.uint64)
-                np.cumsum([len(e) for e in exclude], out=xp[1:])
-                xi = (np.concatenate([np.asarray(e, dtype=np.uint32).ravel() for e in exclude])
-                      if B else np.zeros(0, dtype=np.uint32))
-                xi = np.ascontiguousarray(xi, dtype=np.uint32)
-            if len(xp) != B + 1 or int(xp[-1]) != len(xi):
-                raise VbfmError("exclude: ptr must hold B + 1 positions ending at len(idx)")
-            if len(xi) == 0:
-                xi = np.zeros(1, dtype=np.uint32)
+        xp, xi = self._exclusions(exclude, B)
         shape = max(topn, 0)
         idx = np.full((B, shape), -1, dtype=np.int32)
         score = np.full((B, shape), np.nan)
@@ -1210,6 +1204,50 @@ class Model:
                                           _ptr(count, P_u32), C.byref(st)))
         self.last_recommend_stats = st.as_dict()
         return idx, score, count
+
+    @staticmethod
+    def _exclusions(exclude, B):
+        """recommend's `exclude` as the (ptr, idx) arrays of the C call, or (None, None)."""
+        if exclude is None:
+            return None, None
+        if isinstance(exclude, tuple) and len(exclude) == 2:
+            xp = np.ascontiguousarray(exclude[0], dtype=np.uint64)
+            xi = np.ascontiguousarray(exclude[1], dtype=np.uint32)
+        else:
+            if len(exclude) != B:
+                raise VbfmError("exclude holds %d lists for %d contexts" % (len(exclude), B))
+            xp = np.zeros(B + 1, dtype=np.uint64)
+            np.cumsum([len(e) for e in exclude], out=xp[1:])
+            xi = (np.concatenate([np.asarray(e, dtype=np.uint32).ravel() for e in exclude])
+                  if B else np.zeros(0, dtype=np.uint32))
+            xi = np.ascontiguousarray(xi, dtype=np.uint32)
+        if len(xp) != B + 1 or int(xp[-1]) != len(xi):
+            raise VbfmError("exclude: ptr must hold B + 1 positions ending at len(idx)")
+        if len(xi) == 0:
+            xi = np.zeros(1, dtype=np.uint32)
+        return xp, xi
+
+    def recommend_ucb(self, contexts, candidates, topn, beta, noise=False, exclude=None, clip=True, unknown_ids="refuse",
+                      chunk_bytes=0):
+        """recommend ranked on mean + beta * sd of the pair's row (include/vbfm.h "ranking by mean +
+        beta * sd"; VB kinds, a candidate set made with variance=True): (idx, key, score, var, count),
+        key the value ranked on, score as recommend returns it, var the pair's T without the noise
+        term; sd is sqrt(T), with noise=True sqrt(T + 1 / alpha). A negative beta ranks on a lower
+        bound. exclude as recommend takes it."""
+        rows, _keep = self._rows(contexts)
+        B, topn = rows.num_rows, int(topn)
+        xp, xi = self._exclusions(exclude, B)
+        shape = max(topn, 0)
+        idx = np.full((B, shape), -1, dtype=np.int32)
+        key, score, var = (np.full((B, shape), np.nan) for _ in range(3))
+        count = np.zeros(B, dtype=np.uint32)
+        st = RecommendStats()
+        o = RecommendUcbOpts(topn, int(bool(clip)), UNKNOWN_IDS[unknown_ids], int(chunk_bytes), float(beta), int(bool(noise)))
+        self._mcheck(lib().vbfm_recommend_ucb(self._m, candidates._c, C.byref(rows), _ptr(xp, P_u64), _ptr(xi, P_u32),
+                                              C.byref(o), idx.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(key, P_f64),
+                                              _ptr(score, P_f64), _ptr(var, P_f64), _ptr(count, P_u32), C.byref(st)))
+        self.last_recommend_stats = st.as_dict()
+        return idx, key, score, var, count
 
     def close(self):
         if self._m:

@@ -1,0 +1,468 @@
+"""Top-N by a confidence bound (include/vbfm.h "ranking by mean + beta * sd"): Model.candidates(
+variance=True) / Model.recommend_ucb and bin/libFM -ucb against the EXISTING scorer -- every (context,
+candidate) pair expanded on the host into one row holding both sets of entries, scored with
+Model.score(variance=True, order="exact", clip=False), and key = mean + beta * sqrt(max(T + noise /
+alpha, 0)) formed and ranked in numpy.
+
+Tolerances, per context: tol_m = 1e-9 * max(1, max|mean|) and tol_T = 1e-9 * max(1, max|T|), the
+project's bound for a reordered fp64 sum (REL in tests/test_score_gpu.py), and, carried through the
+square root, tol_key = tol_m + |beta| * tol_T / (2 * sqrt(min(T + noise / alpha))). The models keep
+min(T + noise / alpha) at least 1e4 * tol_T (checked on the reference values), so the linearisation
+of the square root holds. Everything that compares the code with itself (beta = 0 against
+Model.recommend, chunk sizes, slice counts, the two tile shapes, a reused set, clip, duplicates) is bit
+for bit. Models are written with Model.write_params from numpy arrays; nothing is trained.
+
+Largest errors seen on an MI355X (the prints below; DESIGN.md §14 quotes them): 1.35e-13 in score,
+8.5e-14 in var, 1.35e-13 in key -- 1.5e-5, 1.7e-6 and 4.9e-6 of their bounds.
+"""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import synth
+import vbfm
+from conftest import GOLDEN, ROOT
+
+pytestmark = pytest.mark.gpu
+REL = 1e-9
+CLI = os.path.join(ROOT, "scalable-variational-bayesian-factorization-machine_amd", "bin", "libFM")
+F, S = 5, 50                      # contexts: synth.generate's 5 fields x 50 ids
+D_SYNTH = F * S + 1               # id 250 is in the model and in no context
+# the UCB pair kernel's geometry (csrc/vbfm_recommend.hip): a wave owns UCB_CTX contexts, a workgroup
+# UCB_TILE_B; a wave step takes REC_STEP candidates, slices are whole steps
+UCB_CTX, UCB_TILE_B, REC_STEP = 8, 32, 128
+VB, VB_ONLINE, ALS, MCMC_DRAW, MCMC_CHAIN = 0, 1, 2, 3, 4
+ALPHA = 1.5
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def same(a, b):
+    """(idx, key, score, var, count) bit for bit."""
+    return (np.array_equal(a[0], b[0]) and all(np.array_equal(bits(a[i]), bits(b[i])) for i in (1, 2, 3))
+            and np.array_equal(a[4], b[4]))
+
+
+def make_model(tmp_path, kind, k, k0, k1, D=D_SYNTH, seed=1, mn=-1.0, mx=1.5, edit=None, sig=0.05, name="m"):
+    """A model of random parameters; VB kinds: sigma_w, sigma_v in [0.01, 0.01 + sig), sigma_0_dash 0.02."""
+    rng = np.random.default_rng(1000 * seed + k)
+    vbk = kind in (VB, VB_ONLINE)
+    info = dict(kind=kind, k0=k0, k1=k1, num_factor=k, num_attribute=D, min_target=mn, max_target=mx, iter=1,
+                has_variance=int(vbk), w0_or_mu0=0.37, sigma_0_dash=0.02 if vbk else 0.0, alpha=ALPHA)
+    w, v = 0.3 * rng.standard_normal(D), 0.3 * rng.standard_normal(k * D)
+    if vbk:
+        p = {"mu_w": w, "sigma_w": 0.01 + sig * rng.random(D), "mu_v": v, "sigma_v": 0.01 + sig * rng.random(k * D)}
+    else:
+        p = {"w": w, "v": v}
+    if edit:
+        edit(p)
+    path = str(tmp_path / ("%s_%d_%d_%d%d.vbfm" % (name, kind, k, k0, k1)))
+    vbfm.Model.write_params(path, info, p)
+    return vbfm.Model.load(path)
+
+
+_CTX = {}
+
+
+def contexts(B, seed=3):
+    """synth.generate rows (non-unit x), every third value negated."""
+    if (B, seed) not in _CTX:
+        rp, f, v, _ = synth.generate(B, F, S, seed, 1)
+        v = v.copy()
+        v[::3] *= -1.0
+        _CTX[(B, seed)] = (rp, f, v)
+    return _CTX[(B, seed)]
+
+
+def candidates(M, seed=5, D=D_SYNTH):
+    """M rows of 1-3 entries over the contexts' id range (so candidates share ids with contexts),
+    non-unit and negative x, a repeated id now and then; row 1 (when there is one) is empty."""
+    rng = np.random.default_rng(seed)
+    n = rng.integers(1, 4, size=M)
+    if M > 1:
+        n[1] = 0
+    rp = np.zeros(M + 1, dtype=np.uint64)
+    np.cumsum(n, out=rp[1:])
+    f = rng.integers(0, D - 1, size=int(rp[-1])).astype(np.uint32)
+    v = (rng.standard_normal(int(rp[-1])) + 0.25).astype(np.float32)
+    return rp, f, v
+
+
+def expand(ctx, cand):
+    """The B * M rows (context entries, then candidate entries), context-major."""
+    crp, cf, cv = ctx
+    jrp, jf, jv = cand
+    B, M = len(crp) - 1, len(jrp) - 1
+    crp, jrp = crp.astype(np.int64), jrp.astype(np.int64)
+    fs, vs, lens = [], [], np.zeros(B * M, dtype=np.int64)
+    for c in range(B):
+        a_f, a_v = cf[crp[c]:crp[c + 1]], cv[crp[c]:crp[c + 1]]
+        for j in range(M):
+            fs += [a_f, jf[jrp[j]:jrp[j + 1]]]
+            vs += [a_v, jv[jrp[j]:jrp[j + 1]]]
+            lens[c * M + j] = len(a_f) + jrp[j + 1] - jrp[j]
+    rp = np.zeros(B * M + 1, dtype=np.uint64)
+    np.cumsum(lens, out=rp[1:])
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dtype=dt)
+    return rp, cat(fs, np.uint32), cat(vs, np.float32)
+
+
+def reference(m, ctx, cand):
+    """(mean, T) [B, M] of the merged rows by the existing scorer."""
+    B, M = len(ctx[0]) - 1, len(cand[0]) - 1
+    if B * M == 0:
+        return np.zeros((B, M)), np.zeros((B, M))
+    mean, T = m.score(expand(ctx, cand), variance=True, order="exact", clip=False)
+    return mean.reshape(B, M), T.reshape(B, M)
+
+
+def ref_key(mean, T, beta, noise):
+    with np.errstate(invalid="ignore"):
+        return mean + beta * np.sqrt(np.maximum(T + (1.0 / ALPHA if noise else 0.0), 0.0))
+
+
+WORST = {"score": 0.0, "var": 0.0, "key": 0.0}
+
+
+def check(res, ref, beta, noise, topn, excl=None, label=""):
+    """The issue's checks of one result against the reference (mean, T) [B, M]."""
+    idx, key, score, var, count = res
+    mean, T = ref
+    B, M = mean.shape
+    na = 1.0 / ALPHA if noise else 0.0
+    rk = ref_key(mean, T, beta, noise)
+    assert idx.shape == (B, topn) and count.shape == (B,)
+    assert key.shape == (B, topn) and score.shape == (B, topn) and var.shape == (B, topn)
+    for c in range(B):
+        allowed = np.isfinite(mean[c]) & np.isfinite(T[c])
+        if excl is not None:
+            allowed[np.asarray(excl[c], dtype=np.int64)] = False
+        n = int(count[c])
+        assert n == min(topn, int(allowed.sum())), (label, c, n, int(allowed.sum()))
+        got = idx[c, :n].astype(np.int64)
+        assert np.all(idx[c, n:] == -1), (label, c)
+        for a in (key, score, var):
+            assert np.all(np.isnan(a[c, n:])) and np.all(np.isfinite(a[c, :n])), (label, c)
+        assert len(set(got.tolist())) == n and np.all((got >= 0) & (got < M)) and np.all(allowed[got]), (label, c)
+        if n == 0:
+            continue
+        fin = np.isfinite(mean[c]) & np.isfinite(T[c])
+        tol_m = REL * max(1.0, float(np.max(np.abs(mean[c][fin]))))
+        tol_T = REL * max(1.0, float(np.max(np.abs(T[c][fin]))))
+        min_T = float(np.min(T[c][fin] + na))
+        assert min_T >= 1e4 * tol_T, (label, c, min_T)               # the precondition of tol_key
+        tol_key = tol_m + abs(beta) * tol_T / (2.0 * np.sqrt(min_T))
+        e_m = float(np.max(np.abs(score[c, :n] - mean[c, got])))
+        e_T = float(np.max(np.abs(var[c, :n] - T[c, got])))
+        e_k = float(np.max(np.abs(key[c, :n] - rk[c, got])))
+        kth = np.sort(rk[c, allowed])[::-1][n - 1]
+        for name, e, tol in (("score", e_m, tol_m), ("var", e_T, tol_T), ("key", e_k, tol_key)):
+            WORST[name] = max(WORST[name], e / tol)
+        print("%s ctx %d: |score - ref| %.3e (tol %.3e), |var - ref| %.3e (tol %.3e), |key - ref| %.3e (tol %.3e), "
+              "worst margin to the reference's cut %.3e" % (label, c, e_m, tol_m, e_T, tol_T, e_k, tol_key,
+                                                            float(np.min(rk[c, got] - kth))))
+        assert e_m <= tol_m and e_T <= tol_T and e_k <= tol_key, (label, c, e_m, tol_m, e_T, tol_T, e_k, tol_key)
+        assert np.all(rk[c, got] >= kth - 2 * tol_key), (label, c)
+        kc = key[c, :n]
+        assert np.all(kc[:-1] >= kc[1:]), (label, c)
+        ties = kc[:-1] == kc[1:]
+        assert np.all(got[:-1][ties] < got[1:][ties]), (label, c)
+    print("%s: worst error / tolerance so far: score %.3g, var %.3g, key %.3g" % (label, WORST["score"], WORST["var"], WORST["key"]))
+
+
+# ---- 1. every k, tile and slice edge against the scorer -------------------------------------------
+# k rotates through the G / KP boundaries of the preparation kernel and the k0 / k1 combinations; B
+# through the wave's and the workgroup's context tile +-1; M through the candidate step +-1, 2 steps + 1
+# and M < topn; topn through the three list capacities (16, 64, 128); beta and noise rotate
+SHAPES = [
+    # k, k0, k1, kind, B, M, topn, beta, noise
+    (0, 1, 1, VB, UCB_CTX + 1, REC_STEP + 1, 10, 2.0, 0),
+    (1, 0, 1, VB_ONLINE, 1, 1, 1, -1.0, 1),
+    (7, 1, 0, VB, UCB_CTX - 1, REC_STEP - 1, 10, 0.5, 0),
+    (8, 1, 1, VB_ONLINE, UCB_CTX, REC_STEP, 128, 2.0, 1),
+    (9, 0, 0, VB, UCB_CTX + 1, REC_STEP + 1, 1, -1.0, 0),
+    (33, 1, 1, VB, UCB_TILE_B - 1, 2 * REC_STEP + 1, 10, 0.5, 1),
+    (64, 1, 1, VB_ONLINE, UCB_TILE_B, 5, 10, 2.0, 0),           # M < topn: short lists, padding
+    (65, 0, 1, VB, UCB_TILE_B + 1, 2 * REC_STEP - 1, 128, -1.0, 1),
+    (100, 1, 1, VB, 3, 100, 128, 0.5, 0),                      # M < topn
+    (100, 1, 0, VB_ONLINE, 1, 3 * REC_STEP, 64, 2.0, 1),
+    (16, 0, 0, VB, UCB_TILE_B + 1, REC_STEP + 1, 100, -1.0, 1),
+]
+
+
+@pytest.mark.parametrize("k,k0,k1,kind,B,M,topn,beta,noise", SHAPES)
+def test_ranking_matches_the_scorer_of_the_merged_rows(tmp_path, k, k0, k1, kind, B, M, topn, beta, noise):
+    m = make_model(tmp_path, kind, k, k0, k1)
+    ctx, cand = contexts(B), candidates(M)
+    ref = reference(m, ctx, cand)
+    cs = m.candidates(cand, variance=True)
+    assert len(cs) == M
+    res = m.recommend_ucb(ctx, cs, topn, beta, noise=bool(noise), clip=False)
+    check(res, ref, beta, noise, topn, label="k=%d B=%d M=%d topn=%d beta=%g noise=%d" % (k, B, M, topn, beta, noise))
+    st = m.last_recommend_stats
+    assert st["pairs"] == B * M and st["nonfinite_pairs"] == 0 and st["n_chunks"] == 1
+    cs.close()
+    m.close()
+
+
+def test_a_negative_beta_changes_the_returned_set(tmp_path):
+    m = make_model(tmp_path, VB, 8, 1, 1, sig=0.6)              # wide posteriors: sd differs much between candidates
+    B, M, topn = 4, REC_STEP + 2, 10
+    ctx, cand = contexts(B), candidates(M)
+    ref = reference(m, ctx, cand)
+    top = lambda a: [set(np.argsort(-a[c], kind="stable")[:topn].tolist()) for c in range(B)]
+    by_mean, by_lcb = top(ref[0]), top(ref_key(ref[0], ref[1], -1.0, 0))
+    differ = [c for c in range(B) if by_mean[c] != by_lcb[c]]
+    assert differ, "the reference's sets do not differ: the case would show nothing"
+    cs = m.candidates(cand, variance=True)
+    r0 = m.recommend_ucb(ctx, cs, topn, 0.0, clip=False)
+    r1 = m.recommend_ucb(ctx, cs, topn, -1.0, clip=False)
+    check(r0, ref, 0.0, 0, topn, label="beta=0")
+    check(r1, ref, -1.0, 0, topn, label="beta=-1")
+    for c in differ:
+        assert set(r0[0][c].tolist()) != set(r1[0][c].tolist()), c
+    cs.close()
+    m.close()
+
+
+# ---- 2. beta = 0 is the mean ranking, bit for bit -------------------------------------------------
+@pytest.mark.parametrize("k,topn", [(9, 10), (65, 100)])
+def test_beta_zero_is_recommend_bit_for_bit(tmp_path, k, topn):
+    m = make_model(tmp_path, VB, k, 1, 1, mn=-0.25, mx=0.5)
+    B, M = UCB_TILE_B + 3, 2 * REC_STEP + 5
+    ctx, cand = contexts(B), candidates(M)
+    plain, withvar = m.candidates(cand), m.candidates(cand, variance=True)
+    for clip in (False, True):
+        want = m.recommend(ctx, plain, topn, clip=clip)
+        also = m.recommend(ctx, withvar, topn, clip=clip)       # a variance set serves recommend with the same bits
+        got = m.recommend_ucb(ctx, withvar, topn, 0.0, clip=clip)
+        for w in (want, also):
+            assert np.array_equal(w[0], got[0]) and np.array_equal(bits(w[1]), bits(got[2])) and np.array_equal(w[2], got[4])
+        if not clip:
+            assert np.array_equal(bits(got[1]), bits(got[2]))   # key == score
+    with pytest.raises(vbfm.VbfmError, match="holds no variance sums"):
+        m.recommend_ucb(ctx, plain, topn, 0.0)
+    for h in (plain, withvar, m):
+        h.close()
+
+
+# ---- 3. geometry independence -----------------------------------------------------------------
+def test_results_do_not_depend_on_chunks_slices_tile_or_reuse(tmp_path, monkeypatch):
+    m = make_model(tmp_path, VB, 33, 1, 1)
+    B, M, topn = 2 * UCB_TILE_B + 5, 3 * REC_STEP + 9, 10
+    ctx, cand = contexts(B), candidates(M)
+    excl = [np.arange(c % 4, M, 7, dtype=np.uint32) if c % 3 else np.zeros(0, dtype=np.uint32) for c in range(B)]
+    cs = m.candidates(cand, variance=True)
+    monkeypatch.delenv("VBFM_REC_SLICES", raising=False)
+    monkeypatch.delenv("VBFM_UCB_CTX", raising=False)
+    call = lambda **kw: m.recommend_ucb(ctx, cs, topn, 2.0, noise=True, exclude=excl, **kw)
+    base = call()
+    check(call(clip=False), reference(m, ctx, cand), 2.0, 1, topn, excl, "geometry base")
+    assert m.last_recommend_stats["n_chunks"] == 1
+    assert same(base, call())                                   # the candidate set reused
+    row_bytes = 8 + F * 8
+    for chunk_bytes, chunks in ((1, B), (8 + 3 * row_bytes, (B + 2) // 3), (8 + 64 * row_bytes, 2), (1 << 20, 1)):
+        got = call(chunk_bytes=chunk_bytes)
+        assert m.last_recommend_stats["n_chunks"] == chunks, (chunk_bytes, m.last_recommend_stats)
+        assert same(base, got), chunk_bytes
+    for slices in ("1", "2", "7", "100"):                       # read at every call; > 64: the wide merge kernel
+        monkeypatch.setenv("VBFM_REC_SLICES", slices)
+        assert same(base, call()), slices
+        assert same(base, call(chunk_bytes=8 + 3 * row_bytes)), slices
+    monkeypatch.delenv("VBFM_REC_SLICES")
+    monkeypatch.setenv("VBFM_UCB_CTX", "16")                    # the 16-context tile: the same pairs, the same bits
+    assert same(base, call())
+    for big in (64, 128):                                       # its other list capacities
+        monkeypatch.delenv("VBFM_UCB_CTX")
+        want = m.recommend_ucb(ctx, cs, big, -1.0, exclude=excl)
+        monkeypatch.setenv("VBFM_UCB_CTX", "16")
+        assert same(want, m.recommend_ucb(ctx, cs, big, -1.0, exclude=excl)), big
+    cs.close()
+    m.close()
+
+
+# ---- 4. the total order -----------------------------------------------------------------------
+def test_duplicate_candidates_tie_bit_for_bit_and_the_lower_index_wins(tmp_path):
+    m = make_model(tmp_path, VB, 9, 1, 1)
+    rp, f, v = candidates(40)
+    lo, hi = 7, 31                                              # row hi becomes a copy of row lo
+    rows = [(f[int(rp[j]):int(rp[j + 1])], v[int(rp[j]):int(rp[j + 1])]) for j in range(40)]
+    rows[hi] = rows[lo]
+    rp2 = np.zeros(41, dtype=np.uint64)
+    np.cumsum([len(r[0]) for r in rows], out=rp2[1:])
+    cand = (rp2, np.concatenate([r[0] for r in rows]), np.concatenate([r[1] for r in rows]))
+    cs = m.candidates(cand, variance=True)
+    ctx = contexts(3)
+    idx, key, score, var, count = m.recommend_ucb(ctx, cs, 40, 2.0, clip=False)
+    assert np.all(count == 40)
+    for c in range(3):
+        p = int(np.nonzero(idx[c] == lo)[0][0])
+        assert idx[c, p + 1] == hi
+        for a in (key, score, var):
+            assert bits(a[c, p]) == bits(a[c, p + 1])
+        # only one of the two fits at rank p + 1: the lower index is kept
+        one = (ctx[0][c:c + 2] - ctx[0][c], ctx[1][int(ctx[0][c]):int(ctx[0][c + 1])], ctx[2][int(ctx[0][c]):int(ctx[0][c + 1])])
+        r1 = m.recommend_ucb(one, cs, p + 1, 2.0, clip=False)
+        assert r1[4][0] == p + 1 and r1[0][0, p] == lo and hi not in r1[0][0].tolist()
+        assert np.array_equal(r1[0][0], idx[c, :p + 1]) and np.array_equal(bits(r1[1][0]), bits(key[c, :p + 1]))
+    # an excluded index is never returned
+    excl = [np.sort(idx[c, :5]).astype(np.uint32) for c in range(3)]
+    r2 = m.recommend_ucb(ctx, cs, 40, 2.0, exclude=excl, clip=False)
+    for c in range(3):
+        assert r2[4][c] == 35 and not set(excl[c].tolist()) & set(r2[0][c, :35].tolist())
+        assert np.array_equal(r2[0][c, :35], idx[c, 5:]) and np.array_equal(bits(r2[1][c, :35]), bits(key[c, 5:]))
+    assert m.last_recommend_stats["excluded_hits"] >= 15
+    cs.close()
+    m.close()
+
+
+# ---- 5. non-finite pairs ----------------------------------------------------------------------
+def edit_sigma_v(p):
+    p["sigma_v"][0 * D_SYNTH + D_SYNTH - 1] = np.inf           # v is [f][j]: factor 0 of id 250
+
+
+def edit_mu_w(p):
+    p["mu_w"][D_SYNTH - 1] = np.inf
+
+
+@pytest.mark.parametrize("edit,what", [(edit_sigma_v, "T"), (edit_mu_w, "raw")])
+def test_a_nonfinite_candidate_is_never_returned(tmp_path, edit, what):
+    B, M, topn, special = 5, REC_STEP + 3, 10, 77
+    ctx = contexts(B)
+    rp, f, v = candidates(M)
+    f = f.copy()
+    f[int(rp[special])] = D_SYNTH - 1                           # the only row that holds id 250; no context does
+    cand = (rp, f, v)
+    m_inf = make_model(tmp_path, VB, 7, 1, 1, edit=edit, name="inf")
+    m_fin = make_model(tmp_path, VB, 7, 1, 1, name="fin")
+    cs_inf, cs_fin = m_inf.candidates(cand, variance=True), m_fin.candidates(cand, variance=True)
+    ref = reference(m_inf, ctx, cand)
+    bad = ~(np.isfinite(ref[0]) & np.isfinite(ref[1]))
+    assert np.all(bad[:, special]) and bad.sum() == B          # the reference agrees: that column and nothing else
+    if what == "T":
+        assert np.all(np.isfinite(ref[0]))
+    res = m_inf.recommend_ucb(ctx, cs_inf, topn, 2.0, clip=False)
+    assert m_inf.last_recommend_stats["nonfinite_pairs"] == B
+    assert special not in res[0].ravel().tolist()
+    check(res, ref, 2.0, 0, topn, label="inf " + what)
+    # the other results: the finite model with that candidate excluded
+    want = m_fin.recommend_ucb(ctx, cs_fin, topn, 2.0, exclude=[np.array([special], dtype=np.uint32)] * B, clip=False)
+    assert m_fin.last_recommend_stats["nonfinite_pairs"] == 0
+    assert same(res, want)
+    for h in (cs_inf, cs_fin, m_inf, m_fin):
+        h.close()
+
+
+# ---- 6. clip -------------------------------------------------------------------------------
+def test_clip_changes_the_score_only(tmp_path):
+    B, M, topn = 9, REC_STEP + 7, 10
+    ctx, cand = contexts(B), candidates(M)
+    m = make_model(tmp_path, VB, 8, 1, 1, mn=-0.25, mx=0.5)     # a range the best pairs leave
+    cs = m.candidates(cand, variance=True)
+    raw = m.recommend_ucb(ctx, cs, topn, 0.5, clip=False)
+    clipped = m.recommend_ucb(ctx, cs, topn, 0.5, clip=True)
+    assert np.array_equal(raw[0], clipped[0]) and np.array_equal(raw[4], clipped[4])
+    assert np.array_equal(bits(raw[1]), bits(clipped[1])) and np.array_equal(bits(raw[3]), bits(clipped[3]))
+    assert np.any(raw[2] > 0.5)
+    assert np.array_equal(bits(clipped[2]), bits(np.clip(raw[2], np.float32(-0.25), np.float32(0.5))))
+    cs.close()
+    m.close()
+    # a VB model of task c does not exist (the model writer refuses it), so the VB kinds' returned
+    # score is always the clip to the target range
+    info = dict(kind=VB, k0=1, k1=1, num_factor=1, num_attribute=2, min_target=0.0, max_target=1.0, iter=1,
+                has_variance=1, w0_or_mu0=0.0, sigma_0_dash=0.02, alpha=ALPHA)
+    p = {n: np.ones(2) for n in ("mu_w", "sigma_w", "mu_v", "sigma_v")}
+    with pytest.raises(vbfm.VbfmError, match="task c is provided by the ALS / MCMC kinds only"):
+        vbfm.Model.write_params(str(tmp_path / "c.vbfm"), info, p, task="c")
+
+
+# ---- 7. refusals ----------------------------------------------------------------------------
+def test_refusals(tmp_path):
+    ctx, cand = contexts(4), candidates(20)
+    for kind, name in ((ALS, "VBFM_MODEL_ALS"), (MCMC_DRAW, "VBFM_MODEL_MCMC_DRAW")):
+        pm = make_model(tmp_path, kind, 8, 1, 1)
+        with pytest.raises(vbfm.VbfmError, match=r"vbfm_candidates_create_var: a model of kind %s holds no posterior variances" % name):
+            pm.candidates(cand, variance=True)
+        plain = pm.candidates(cand)
+        with pytest.raises(vbfm.VbfmError, match=r"vbfm_recommend_ucb: a model of kind %s holds no posterior variances" % name):
+            pm.recommend_ucb(ctx, plain, 5, 1.0)
+        plain.close()
+        pm.close()
+    rng = np.random.default_rng(4)
+    info = dict(kind=MCMC_CHAIN, k0=1, k1=1, num_factor=4, num_attribute=D_SYNTH, min_target=-1.0, max_target=1.5, iter=1,
+                has_variance=0, w0_or_mu0=0.0, sigma_0_dash=0.0, alpha=1.0)
+    draws = [dict(w=0.3 * rng.standard_normal(D_SYNTH), v=0.3 * rng.standard_normal(4 * D_SYNTH), w0=0.1 * s, alpha=1.0 + s)
+             for s in range(2)]
+    vbfm.Model.write_chain(str(tmp_path / "chain.vbfm"), info, draws)
+    chain = vbfm.Model.load(str(tmp_path / "chain.vbfm"))
+    m = make_model(tmp_path, VB, 8, 1, 1)
+    cs = m.candidates(cand, variance=True)
+    with pytest.raises(vbfm.VbfmError, match=r"vbfm_candidates_create_var: a chain of draws \(VBFM_MODEL_MCMC_CHAIN\)"):
+        chain.candidates(cand, variance=True)
+    with pytest.raises(vbfm.VbfmError, match=r"vbfm_recommend_ucb: a chain of draws \(VBFM_MODEL_MCMC_CHAIN\)"):
+        chain.recommend_ucb(ctx, cs, 5, 1.0)
+    chain.close()
+    plain = m.candidates(cand)
+    with pytest.raises(vbfm.VbfmError, match=r"holds no variance sums \(it was made by vbfm_candidates_create; use vbfm_candidates_create_var\)"):
+        m.recommend_ucb(ctx, plain, 5, 1.0)
+    for beta in (float("nan"), float("inf"), float("-inf")):
+        with pytest.raises(vbfm.VbfmError, match=r"beta = \S+ is not a finite number"):
+            m.recommend_ucb(ctx, cs, 5, beta)
+    for topn in (0, vbfm.REC_MAX_TOPN + 1):
+        with pytest.raises(vbfm.VbfmError, match=r"topn = %d is outside 1 \.\. 128" % topn):
+            m.recommend_ucb(ctx, cs, topn, 1.0)
+    other = make_model(tmp_path, VB, 8, 1, 1, name="other")
+    with pytest.raises(vbfm.VbfmError, match="made from another model"):
+        other.recommend_ucb(ctx, cs, 5, 1.0)
+    for h in (plain, cs, m, other):
+        h.close()
+
+
+# ---- 8. the CLI -------------------------------------------------------------------------------
+def test_cli_round_trip_and_flag_refusals(tmp_path):
+    d = os.path.join(GOLDEN, "tiny")
+    tr, te = os.path.join(d, "train.libfm"), os.path.join(d, "test.libfm")
+    items, users = vbfm.DataSubset.load(tr), vbfm.DataSubset.load(te)
+    D = vbfm.num_all_attribute(items, users)
+    m = make_model(tmp_path, VB, 3, 1, 1, D=D, mn=float(items.min_target), mx=float(items.max_target))
+    mfile = [str(p) for p in tmp_path.iterdir() if str(p).endswith(".vbfm")][0]
+    B, M, topn = users.num_cases, items.num_cases, 3
+    rng = np.random.default_rng(9)
+    excl = [rng.permutation(M)[:rng.integers(0, 4)] for _ in range(B)]
+    with open(tmp_path / "ex", "w") as fh:
+        for e in excl:
+            fh.write(" ".join(str(int(x)) for x in e) + "\n")
+    run = lambda args: subprocess.run([CLI] + args, cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
+    lines = lambda idx, val, count: [" ".join("%d:%.17g" % (idx[c, e], val[c, e]) for e in range(count[c])) for c in range(B)]
+    cs = m.candidates(items, variance=True)
+    for beta in ("1.5", "-1.5"):
+        r = run(["-load_model", mfile, "-test", te, "-candidates", tr, "-topn", str(topn), "-out", "rec", "-exclude", "ex",
+                 "-ucb", beta, "-ucb_noise", "1", "-out_rank_var", "rv"])
+        assert r.returncode == 0, r.stderr[-2000:]
+        idx, key, score, var, count = m.recommend_ucb(users, cs, topn, float(beta), noise=True,
+                                                      exclude=[np.unique(e).astype(np.uint32) for e in excl])
+        assert count.max() > 0
+        for name, val in (("rec", score), ("rv", var)):
+            got = open(tmp_path / name).read().split("\n")
+            assert got[-1] == "" and got[:-1] == lines(idx, val, count), (beta, name)
+    cs.close()
+    m.close()
+    base = ["-load_model", mfile, "-test", te, "-out", "o"]
+    for extra, msg in ((["-ucb", "1.5"], "-ucb needs -candidates"),
+                       (["-candidates", tr, "-topn", "3", "-ucb_noise", "1"], "-ucb_noise needs -ucb"),
+                       (["-candidates", tr, "-topn", "3", "-out_rank_var", "v"], "-out_rank_var needs -ucb"),
+                       (["-candidates", tr, "-topn", "3", "-ucb", "1.5", "-out_var", "v"], "-out_var does not apply to -candidates"),
+                       (["-candidates", tr, "-topn", "3", "-ucb", "inf"], "-ucb needs a finite number")):
+        r = run(base + extra)
+        assert msg in r.stderr, (extra, r.stderr[-500:])
+    als = make_model(tmp_path, ALS, 3, 1, 1, D=D, name="als")
+    als.close()
+    afile = [str(p) for p in tmp_path.iterdir() if os.path.basename(str(p)).startswith("als_")][0]
+    r = run(["-load_model", afile, "-test", te, "-candidates", tr, "-topn", "3", "-out", "o", "-ucb", "1.5"])
+    assert "-ucb needs a model with variances" in r.stderr, r.stderr[-500:]
+    r = run(["-task", "r", "-train", tr, "-test", te, "-ucb", "1.5"])
+    assert "-ucb, -ucb_noise and -out_rank_var belong to -load_model" in r.stderr
