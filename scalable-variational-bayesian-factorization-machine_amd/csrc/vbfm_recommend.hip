@@ -12,11 +12,13 @@
 // Kernels: k_score<.., QOUT> (vbfm_score.h: the lane-group scorer, which here also stores every
 // row's per-factor sums), k_rec_pairs (the hot path) and k_rec_merge (the slices' lists into one).
 // Ranking by mean + beta * sd (vbfm_recommend_ucb) adds the variance term of the merged
-// row by the same algebra: k_score<.., VAR, QOUT>, k_ucb_pairs, the same merge, k_ucb_finish.
+// row by the same algebra: k_score<.., VAR, QOUT>, k_ucb_pairs, the same merge, k_ucb_finish. Both
+// calls are one host pipeline (rank_call) under two descriptions (Ranking).
 #include "vbfm_score.h"
 #include "vbfm_class_math.h"
 
 #include <cmath>
+#include <functional>
 
 using namespace vbs;
 
@@ -324,17 +326,21 @@ hipError_t launch_merge(const MergeArgs &a, hipStream_t s)
 	return hipGetLastError();
 }
 
+// the pair kernels' pointer parameters on the host; zt, ut, tb_c and tb_j are k_ucb_pairs'
+struct PairPtrs {
+	const double *ctx_all, *qt, *zt, *ut, *base_c, *base_j, *tb_c, *tb_j;
+};
+
 // the list capacity is the smallest of {16, 64, VBFM_REC_MAX_TOPN} that holds topn: LDS per workgroup
 // (12.3, 48.3, 96.3 KiB) decides how many workgroups share a CU
-hipError_t launch_pairs(const double *qc, const double *qt, const double *base_c, const double *base_j, const PairArgs &a,
-                        hipStream_t s)
+hipError_t launch_pairs(const PairPtrs &p, const PairArgs &a, hipStream_t s)
 {
 	if (a.nB == 0) return hipSuccess;
 	const uint32_t waves = (a.nB + REC_CTX - 1) / REC_CTX;
 	const dim3 grid((waves + REC_WAVES - 1) / REC_WAVES, a.slices), grid2((waves + 1) / 2, a.slices);
-	if (a.topn <= 16) k_rec_pairs<16, REC_WAVES><<<grid, 64 * REC_WAVES, 0, s>>>(qc, qt, base_c, base_j, a);
-	else if (a.topn <= 64) k_rec_pairs<64, REC_WAVES><<<grid, 64 * REC_WAVES, 0, s>>>(qc, qt, base_c, base_j, a);
-	else k_rec_pairs<VBFM_REC_MAX_TOPN, 2><<<grid2, 128, 0, s>>>(qc, qt, base_c, base_j, a);
+	if (a.topn <= 16) k_rec_pairs<16, REC_WAVES><<<grid, 64 * REC_WAVES, 0, s>>>(p.ctx_all, p.qt, p.base_c, p.base_j, a);
+	else if (a.topn <= 64) k_rec_pairs<64, REC_WAVES><<<grid, 64 * REC_WAVES, 0, s>>>(p.ctx_all, p.qt, p.base_c, p.base_j, a);
+	else k_rec_pairs<VBFM_REC_MAX_TOPN, 2><<<grid2, 128, 0, s>>>(p.ctx_all, p.qt, p.base_c, p.base_j, a);
 	return hipGetLastError();
 }
 
@@ -531,15 +537,13 @@ uint32_t ucb_ctx(size_t nB, int k, int topn)
 }
 
 // capacities as launch_pairs; the 16-context form keeps k_rec_pairs' workgroups
-hipError_t launch_ucb_pairs(uint32_t ctx, const double *ctx_all, const double *qt, const double *zt, const double *ut,
-                            const double *base_c, const double *base_j, const double *tb_c, const double *tb_j,
-                            const PairArgs &a, const UcbArgs &u, hipStream_t s)
+hipError_t launch_ucb_pairs(uint32_t ctx, const PairPtrs &p, const PairArgs &a, const UcbArgs &u, hipStream_t s)
 {
 	if (a.nB == 0) return hipSuccess;
 	const uint32_t waves = (a.nB + ctx - 1) / ctx;
 	const dim3 grid((waves + 3) / 4, a.slices), grid2((waves + 1) / 2, a.slices);
 #define UCB_LAUNCH(CAP, WAVES, CTX, GRID) \
-	k_ucb_pairs<CAP, WAVES, CTX><<<GRID, 64 * WAVES, 0, s>>>(ctx_all, qt, zt, ut, base_c, base_j, tb_c, tb_j, a, u)
+	k_ucb_pairs<CAP, WAVES, CTX><<<GRID, 64 * WAVES, 0, s>>>(p.ctx_all, p.qt, p.zt, p.ut, p.base_c, p.base_j, p.tb_c, p.tb_j, a, u)
 	if (ctx == UCB_CTX) {
 		if (a.topn <= 16) UCB_LAUNCH(16, UCB_WAVES, UCB_CTX, grid);
 		else if (a.topn <= 64) UCB_LAUNCH(64, UCB_WAVES, UCB_CTX, grid);
@@ -570,29 +574,14 @@ uint32_t pick_slices(uint32_t nB, uint32_t M, uint32_t ctx = REC_CTX)
 	return std::max<uint32_t>(1, std::min(want, most));
 }
 
-// the sums and bases of rows [r0, r0 + nr) (already staged at d_in) by the lane-group scorer
-void launch_prepare(vbfm_model *m, const uint8_t *d_in, uint32_t nr, uint64_t e0, uint32_t r0, double *base, double *q,
-                    uint32_t q_tile)
+// The sums and bases of rows [r0, r0 + nr) (already staged at d_in) by the lane-group scorer. With tb
+// also the variance sums: q takes the three planes of a tile (ScoreArgs::q), tb the rows' T_n; base and
+// the Q plane are the same bits either way (the VAR instantiations form the mean by the same
+// expressions from the same values).
+void launch_prepare(vbfm_model *m, const uint8_t *d_in, uint32_t nr, uint64_t e0, uint32_t r0, double *base, double *tb,
+                    double *q, uint32_t q_tile)
 {
 	ScoreArgs a = score_args(m, 0);   // the unclipped mean
-	a.row_ptr = (const uint64_t *)d_in;
-	a.ent = (const uint2 *)(d_in + ((size_t)nr + 1) * 8);
-	a.ent_base = e0;
-	a.mean = base;
-	a.n = nr;
-	a.row0 = r0;
-	a.q = q;
-	a.q_tile = q_tile;
-	if (nr) HIPCHK((launch_group<false, true>(a, 0, m->s)));
-}
-
-// the same with the variance sums: q takes the three planes of a tile (ScoreArgs::q), tb the rows' T_n.
-// base and the Q plane are launch_prepare's bits: the VAR instantiations form the mean by the same
-// expressions from the same values.
-void launch_prepare_var(vbfm_model *m, const uint8_t *d_in, uint32_t nr, uint64_t e0, uint32_t r0, double *base, double *tb,
-                        double *q, uint32_t q_tile)
-{
-	ScoreArgs a = score_args(m, 0);
 	a.row_ptr = (const uint64_t *)d_in;
 	a.ent = (const uint2 *)(d_in + ((size_t)nr + 1) * 8);
 	a.ent_base = e0;
@@ -602,7 +591,8 @@ void launch_prepare_var(vbfm_model *m, const uint8_t *d_in, uint32_t nr, uint64_
 	a.row0 = r0;
 	a.q = q;
 	a.q_tile = q_tile;
-	if (nr) HIPCHK((launch_group<true, true>(a, 0, m->s)));
+	if (!nr) return;
+	HIPCHK(tb ? (launch_group<true, true>(a, 0, m->s)) : (launch_group<false, true>(a, 0, m->s)));
 }
 
 const char *kind_name(int32_t kind)
@@ -736,8 +726,8 @@ int candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows
 			const uint32_t nr = p.r1 - p.r0;
 			const size_t bytes = stage_rows(sl.h_in, rows, p.r0, nr);
 			HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, bytes, hipMemcpyHostToDevice, m->s));
-			if (var) launch_prepare_var(m, sl.d_in, nr, rows->row_ptr[p.r0], p.r0, c->base + p.r0, c->tb + p.r0, c->qt + p.r0, c->Mpad);
-			else launch_prepare(m, sl.d_in, nr, rows->row_ptr[p.r0], p.r0, c->base + p.r0, c->qt + p.r0, c->Mpad);
+			launch_prepare(m, sl.d_in, nr, rows->row_ptr[p.r0], p.r0, c->base + p.r0, var ? c->tb + p.r0 : nullptr, c->qt + p.r0,
+			               c->Mpad);
 			HIPCHK(hipStreamSynchronize(m->s));
 		}
 		if (var && (size_t)k * Mpad) {   // the P plane becomes U = Z + P, rounded once
@@ -755,6 +745,174 @@ int candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows
 	}
 	*out = c;
 	return 0;
+}
+
+// What a ranking adds to rank_call below (vbfm_recommend, vbfm_recommend_ucb).
+struct Ranking {
+	const char *who = "";         // the call, in messages
+	int planes = 1;               // prepared per context: 1 (Q) or 3 (Q, Z, P)
+	bool tb = false;              // the contexts' T_n beside their bases (and the candidate set's tb)
+	// the pair kernel's context tile for a call whose largest chunk has nB rows
+	std::function<uint32_t(size_t nB, int k, int topn)> tile;
+	std::function<hipError_t(uint32_t ctx, const PairPtrs &, const PairArgs &, hipStream_t)> pairs;
+	int link = 0;                 // MergeArgs::link: what the merge makes of a list's key
+	// A chunk's result block is [vals[0] | .. | vals[nvals - 1] | idx | count], vals [rows][topn]
+	// doubles each, the merge's values in block 0. vals: where each goes for the caller, or NULL.
+	int nvals = 1;
+	double *vals[3] = {};
+	// after the merge, to form the blocks from its idx and count (MergeArgs::score is the block's
+	// start), or empty
+	std::function<void(uint32_t ctx, const PairPtrs &, const PairArgs &, const MergeArgs &, hipStream_t)> finish;
+};
+
+// what both ranking calls refuse before anything else; then fn under the model's guard
+template <class F>
+int ranking_guarded(const std::string &who, vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *contexts, const void *opts, F &&fn)
+{
+	if (!m) return mfail(nullptr, who + ": null model");
+	if (!cs || !contexts || !opts) return mfail(m, who + ": null argument");
+	if (m->info.kind == VBFM_MODEL_MCMC_CHAIN)
+		return mfail(m, who + ": a chain of draws (VBFM_MODEL_MCMC_CHAIN) is scored, not ranked: "
+		                "recommendation takes a model of one set of parameters");
+	return mguarded(m, fn);
+}
+
+// The refusals both ranking calls share, each written once; an entry point makes them in the order it
+// always did, its own between them.
+void require_own_set(const std::string &who, const vbfm_model *m, const vbfm_candidates *cs)
+{
+	if (cs->m != m) throw who + ": the candidate set was made from another model";
+}
+
+void require_topn(const std::string &who, int32_t topn)
+{
+	if (topn < 1 || topn > VBFM_REC_MAX_TOPN)
+		throw who + ": topn = " + std::to_string(topn) + " is outside 1 .. " + std::to_string(VBFM_REC_MAX_TOPN);
+}
+
+// have_results: every result array the call requires is there
+void require_rest(const std::string &who, const vbfm_model *m, int32_t unknown_ids, const vbfm_csr *contexts, bool have_results)
+{
+	require_model(m, who.c_str());
+	if (unknown_ids != 0 && unknown_ids != 1) throw who + ": unknown_ids is 0 (refuse) or 1 (skip)";
+	if (contexts->num_rows && !have_results) throw who + ": null result array";
+}
+
+// A ranking call (validated by its entry point): the contexts in chunks of whole rows through the two slots (rotate_chunks), each
+// chunk [row_ptr slice | entries | excl_ptr slice | excl_idx slice] prepared, ranked against the whole
+// candidate set, merged and, where the ranking has one, finished before its result block comes back.
+void rank_call(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *contexts, const uint64_t *excl_ptr,
+               const uint32_t *excl_idx, const vbfm_recommend_opts &o, const Ranking &d, int32_t *idx, uint32_t *count,
+               vbfm_recommend_stats *st)
+{
+	const double t_begin = wall_s();
+	const std::string who = d.who;
+	const uint32_t B = contexts->num_rows, M = cs->M;
+	const size_t topn = (size_t)o.topn;
+	const int k = cs->k;
+	vbfm_recommend_stats out = {};
+	check_exclusions(who, B, M, excl_ptr, excl_idx);
+	size_t need_in = 0, need_rows = 0;
+	const std::vector<ChunkPlan> plan = plan_chunks(contexts, o.chunk_bytes ? o.chunk_bytes : VBFM_SCORE_CHUNK_DEFAULT, who,
+	                                                &need_in, &need_rows);
+	const uint32_t ctx = d.tile(need_rows, k, o.topn);
+	// a chunk's rows as stage_rows writes them; its exclusion lists follow
+	const auto rows_bytes = [&](uint32_t r0, uint32_t nr) {
+		return ((size_t)nr + 1) * 8 + (contexts->row_ptr[r0 + nr] - contexts->row_ptr[r0]) * 8;
+	};
+	size_t need_part = 0;
+	for (const ChunkPlan &p : plan) {
+		const uint32_t nr = p.r1 - p.r0;
+		if (excl_ptr)
+			need_in = std::max(need_in, rows_bytes(p.r0, nr) + ((size_t)nr + 1) * 8 + (excl_ptr[p.r1] - excl_ptr[p.r0]) * 4);
+		need_part = std::max(need_part, (size_t)nr * pick_slices(nr, M, ctx));
+	}
+	const auto out_doubles = [&](size_t nr) { return d.nvals * nr * topn + (nr * topn * 4 + nr * 4 + 7) / 8; };
+	staging_reserve(m, need_in, out_doubles(need_rows));
+	const size_t rows_pad = round_up(need_rows, ctx);
+	DevScratch<double> base_c(rows_pad), tb_c;
+	if (d.tb) tb_c.p = dalloc<double>(rows_pad);
+	DevScratch<double> qc(d.planes * rows_pad * (size_t)k), part_key(need_part * topn);
+	DevScratch<uint32_t> part_idx(need_part * topn), part_cnt(need_part);
+	DevScratch<unsigned long long> counters(2);
+	HIPCHK(hipMemsetAsync(counters, 0, 16, m->s));
+	HIPCHK(hipMemsetAsync(base_c, 0, rows_pad * 8, m->s));
+	if (d.tb) HIPCHK(hipMemsetAsync(tb_c, 0, rows_pad * 8, m->s));
+	flags_reset(m);
+	PhaseEvents pe;
+	const PairPtrs ptrs = {qc, cs->qt, cs->zt, cs->ut, base_c, cs->base, tb_c, cs->tb};
+	rotate_chunks(
+	    m, plan.size(),
+	    [&](size_t i, vbfm_model::Slot &sl) {
+		    const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
+		    size_t bytes = stage_rows(sl.h_in, contexts, r0, nr);
+		    if (excl_ptr) {
+			    const uint64_t xe0 = excl_ptr[r0], nx = excl_ptr[r0 + nr] - xe0;
+			    memcpy(sl.h_in + bytes, excl_ptr + r0, ((size_t)nr + 1) * 8);
+			    bytes += ((size_t)nr + 1) * 8;
+			    if (nx) memcpy(sl.h_in + bytes, excl_idx + xe0, nx * 4);
+			    bytes += nx * 4;
+		    }
+		    return bytes;
+	    },
+	    [&](size_t i, vbfm_model::Slot &sl) {
+		    const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
+		    const size_t n = (size_t)nr * topn;
+		    hipEvent_t *ev = pe.ev[i & 1];
+		    HIPCHK(hipEventRecord(ev[0], m->s));
+		    launch_prepare(m, sl.d_in, nr, contexts->row_ptr[r0], r0, base_c, tb_c, qc, ctx);
+		    HIPCHK(hipEventRecord(ev[1], m->s));
+		    PairArgs a = {};
+		    a.nB = nr; a.M = M; a.Mpad = cs->Mpad;
+		    a.k = k;
+		    a.w0 = m->info.k0 ? m->info.w0_or_mu0 : 0.0;
+		    a.topn = o.topn;
+		    a.slices = pick_slices(nr, M, ctx);
+		    a.slice_len = std::max<uint32_t>(REC_STEP, round_up(((uint64_t)M + a.slices - 1) / a.slices, REC_STEP));
+		    if (excl_ptr) {
+			    const size_t excl_off = rows_bytes(r0, nr);
+			    a.excl_ptr = (const uint64_t *)(sl.d_in + excl_off);
+			    a.excl_idx = (const uint32_t *)(sl.d_in + excl_off + ((size_t)nr + 1) * 8);
+			    a.excl_base = excl_ptr[r0];
+		    }
+		    a.part_raw = part_key; a.part_idx = part_idx; a.part_cnt = part_cnt;
+		    a.counters = counters;
+		    HIPCHK(d.pairs(ctx, ptrs, a, m->s));
+		    HIPCHK(hipEventRecord(ev[2], m->s));
+		    MergeArgs g = {};
+		    g.part_raw = part_key; g.part_idx = part_idx; g.part_cnt = part_cnt;
+		    g.nB = nr; g.slices = a.slices; g.topn = o.topn;
+		    g.link = d.link;
+		    g.mn = m->info.min_target; g.mx = m->info.max_target;
+		    g.score = sl.d_out;
+		    g.idx = (int32_t *)(sl.d_out + d.nvals * n);
+		    g.count = (uint32_t *)(g.idx + n);
+		    HIPCHK(launch_merge(g, m->s));
+		    if (d.finish) d.finish(ctx, ptrs, a, g, m->s);
+		    HIPCHK(hipEventRecord(ev[3], m->s));
+		    HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, out_doubles(nr) * 8, hipMemcpyDeviceToHost, m->s));
+		    out.pairs += (uint64_t)nr * M;
+	    },
+	    [&](size_t i, vbfm_model::Slot &sl) {
+		    const size_t r0 = plan[i].r0, nr = plan[i].r1 - plan[i].r0, n = nr * topn;
+		    for (int v = 0; v < d.nvals; v++)
+			    if (d.vals[v]) memcpy(d.vals[v] + r0 * topn, sl.h_out + v * n, n * 8);
+		    memcpy(idx + r0 * topn, sl.h_out + d.nvals * n, n * 4);
+		    memcpy(count + r0, (const uint8_t *)(sl.h_out + d.nvals * n) + n * 4, nr * 4);
+		    out.ms_prepare += elapsed(pe.ev[i & 1][0], pe.ev[i & 1][1]);
+		    out.ms_pairs += elapsed(pe.ev[i & 1][1], pe.ev[i & 1][2]);
+		    out.ms_merge += elapsed(pe.ev[i & 1][2], pe.ev[i & 1][3]);
+	    });
+	const ScoreFlags f = flags_read(m);
+	if (f.first != ~0ull && !o.unknown_ids) throw unknown_msg(m, f.first >> 32, (uint32_t)f.first);
+	unsigned long long cnt[2];
+	HIPCHK(hipMemcpyAsync(cnt, counters, 16, hipMemcpyDeviceToHost, m->s));
+	HIPCHK(hipStreamSynchronize(m->s));
+	out.n_chunks = (uint32_t)plan.size();
+	out.nonfinite_pairs = cnt[0];
+	out.excluded_hits = cnt[1];
+	out.ms_total = (wall_s() - t_begin) * 1e3;
+	if (st) *st = out;
 }
 
 }  // namespace
@@ -787,277 +945,75 @@ int vbfm_recommend(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *con
                    const uint32_t *excl_idx, const vbfm_recommend_opts *opts, int32_t *idx, double *score,
                    uint32_t *count, vbfm_recommend_stats *st)
 {
-	if (!m) return mfail(nullptr, "vbfm_recommend: null model");
-	if (!cs || !contexts || !opts) return mfail(m, "vbfm_recommend: null argument");
-	if (m->info.kind == VBFM_MODEL_MCMC_CHAIN)
-		return mfail(m, "vbfm_recommend: a chain of draws (VBFM_MODEL_MCMC_CHAIN) is scored, not ranked: "
-		                "recommendation takes a model of one set of parameters");
-	return mguarded(m, [&] {
-		const double t_begin = wall_s();
-		const vbfm_recommend_opts o = *opts;
-		if (cs->m != m) throw std::string("vbfm_recommend: the candidate set was made from another model");
-		if (o.topn < 1 || o.topn > VBFM_REC_MAX_TOPN)
-			throw std::string("vbfm_recommend: topn = ") + std::to_string(o.topn) + " is outside 1 .. " + std::to_string(VBFM_REC_MAX_TOPN);
-		require_model(m, "vbfm_recommend");
-		if (o.unknown_ids != 0 && o.unknown_ids != 1) throw std::string("vbfm_recommend: unknown_ids is 0 (refuse) or 1 (skip)");
-		const uint32_t B = contexts->num_rows, M = cs->M;
-		if (B && (!idx || !score || !count)) throw std::string("vbfm_recommend: null result array");
-		const size_t topn = (size_t)o.topn;
-		const int k = cs->k;
-		vbfm_recommend_stats out = {};
-		check_exclusions("vbfm_recommend", B, M, excl_ptr, excl_idx);
-		size_t need_in = 0, need_rows = 0;
-		const std::vector<ChunkPlan> plan = plan_chunks(contexts, o.chunk_bytes ? o.chunk_bytes : VBFM_SCORE_CHUNK_DEFAULT,
-		                                                "vbfm_recommend", &need_in, &need_rows);
-		// a chunk in a slot: [row_ptr slice | entries | excl_ptr slice | excl_idx slice]; its results
-		// [score | idx | count]
-		size_t need_part = 0;
-		for (const ChunkPlan &p : plan) {
-			const uint32_t nr = p.r1 - p.r0;
-			if (excl_ptr) {
-				const size_t rows_bytes = ((size_t)nr + 1) * 8 + (contexts->row_ptr[p.r1] - contexts->row_ptr[p.r0]) * 8;
-				need_in = std::max(need_in, rows_bytes + ((size_t)nr + 1) * 8 + (excl_ptr[p.r1] - excl_ptr[p.r0]) * 4);
-			}
-			need_part = std::max(need_part, (size_t)nr * pick_slices(nr, M));
-		}
-		const auto out_doubles = [&](size_t nr) { return nr * topn + (nr * topn * 4 + nr * 4 + 7) / 8; };
-		staging_reserve(m, need_in, out_doubles(need_rows));
-		const size_t rows_pad = round_up(need_rows, REC_CTX);
-		DevScratch<double> base_c(rows_pad), qc(rows_pad * (size_t)k), part_raw(need_part * topn);
-		DevScratch<uint32_t> part_idx(need_part * topn), part_cnt(need_part);
-		DevScratch<unsigned long long> counters(2);
-		HIPCHK(hipMemsetAsync(counters, 0, 16, m->s));
-		HIPCHK(hipMemsetAsync(base_c, 0, rows_pad * 8, m->s));
-		flags_reset(m);
-		PhaseEvents pe;
-		auto drain = [&](size_t i) {
-			vbfm_model::Slot &sl = m->slot[i & 1];
-			HIPCHK(hipEventSynchronize(sl.ev[SEV_DONE]));
-			const size_t r0 = plan[i].r0, nr = plan[i].r1 - plan[i].r0;
-			memcpy(score + r0 * topn, sl.h_out, nr * topn * 8);
-			memcpy(idx + r0 * topn, sl.h_out + nr * topn, nr * topn * 4);
-			memcpy(count + r0, (const uint8_t *)(sl.h_out + nr * topn) + nr * topn * 4, nr * 4);
-			out.ms_prepare += elapsed(pe.ev[i & 1][0], pe.ev[i & 1][1]);
-			out.ms_pairs += elapsed(pe.ev[i & 1][1], pe.ev[i & 1][2]);
-			out.ms_merge += elapsed(pe.ev[i & 1][2], pe.ev[i & 1][3]);
-		};
-		for (size_t i = 0; i < plan.size(); i++) {
-			vbfm_model::Slot &sl = m->slot[i & 1];
-			if (i >= 2) drain(i - 2);   // the slot's previous chunk has left both of its buffers
-			const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
-			size_t bytes = stage_rows(sl.h_in, contexts, r0, nr);
-			const size_t excl_off = bytes;
-			uint64_t xe0 = 0, nx = 0;
-			if (excl_ptr) {
-				xe0 = excl_ptr[r0];
-				nx = excl_ptr[r0 + nr] - xe0;
-				memcpy(sl.h_in + bytes, excl_ptr + r0, ((size_t)nr + 1) * 8);
-				bytes += ((size_t)nr + 1) * 8;
-				if (nx) memcpy(sl.h_in + bytes, excl_idx + xe0, nx * 4);
-				bytes += nx * 4;
-			}
-			// the copy runs on its own stream, under the kernels of the chunk before
-			HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, bytes, hipMemcpyHostToDevice, m->s_copy));
-			HIPCHK(hipEventRecord(sl.ev[SEV_C1], m->s_copy));
-			HIPCHK(hipStreamWaitEvent(m->s, sl.ev[SEV_C1], 0));
-			hipEvent_t *ev = pe.ev[i & 1];
-			HIPCHK(hipEventRecord(ev[0], m->s));
-			launch_prepare(m, sl.d_in, nr, contexts->row_ptr[r0], r0, base_c, qc, REC_CTX);
-			HIPCHK(hipEventRecord(ev[1], m->s));
-			PairArgs a = {};
-			a.nB = nr; a.M = M; a.Mpad = cs->Mpad;
-			a.k = k;
-			a.w0 = m->info.k0 ? m->info.w0_or_mu0 : 0.0;
-			a.topn = o.topn;
-			a.slices = pick_slices(nr, M);
-			a.slice_len = std::max<uint32_t>(REC_STEP, round_up(((uint64_t)M + a.slices - 1) / a.slices, REC_STEP));
-			if (excl_ptr) {
-				a.excl_ptr = (const uint64_t *)(sl.d_in + excl_off);
-				a.excl_idx = (const uint32_t *)(sl.d_in + excl_off + ((size_t)nr + 1) * 8);
-				a.excl_base = xe0;
-			}
-			a.part_raw = part_raw; a.part_idx = part_idx; a.part_cnt = part_cnt;
-			a.counters = counters;
-			HIPCHK(launch_pairs(qc, cs->qt, base_c, cs->base, a, m->s));
-			HIPCHK(hipEventRecord(ev[2], m->s));
-			MergeArgs g = {};
-			g.part_raw = part_raw; g.part_idx = part_idx; g.part_cnt = part_cnt;
-			g.nB = nr; g.slices = a.slices; g.topn = o.topn;
-			g.link = !o.clip ? 0 : (m->task == VBFM_TASK_CLASSIFICATION ? 2 : 1);
-			g.mn = m->info.min_target; g.mx = m->info.max_target;
-			g.score = sl.d_out;
-			g.idx = (int32_t *)(sl.d_out + (size_t)nr * topn);
-			g.count = (uint32_t *)(g.idx + (size_t)nr * topn);
-			HIPCHK(launch_merge(g, m->s));
-			HIPCHK(hipEventRecord(ev[3], m->s));
-			HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, out_doubles(nr) * 8, hipMemcpyDeviceToHost, m->s));
-			HIPCHK(hipEventRecord(sl.ev[SEV_DONE], m->s));
-			out.pairs += (uint64_t)nr * M;
-		}
-		for (size_t i = plan.size() >= 2 ? plan.size() - 2 : 0; i < plan.size(); i++) drain(i);
-		const ScoreFlags f = flags_read(m);
-		if (f.first != ~0ull && !o.unknown_ids) throw unknown_msg(m, f.first >> 32, (uint32_t)f.first);
-		unsigned long long cnt[2];
-		HIPCHK(hipMemcpyAsync(cnt, counters, 16, hipMemcpyDeviceToHost, m->s));
-		HIPCHK(hipStreamSynchronize(m->s));
-		out.n_chunks = (uint32_t)plan.size();
-		out.nonfinite_pairs = cnt[0];
-		out.excluded_hits = cnt[1];
-		out.ms_total = (wall_s() - t_begin) * 1e3;
-		if (st) *st = out;
+	const std::string who = "vbfm_recommend";
+	return ranking_guarded(who, m, cs, contexts, opts, [&] {
+		require_own_set(who, m, cs);
+		require_topn(who, opts->topn);
+		require_rest(who, m, opts->unknown_ids, contexts, idx && score && count);
+		Ranking d;
+		d.who = who.c_str();
+		d.planes = 1;
+		d.tb = false;
+		d.tile = [](size_t, int, int) { return (uint32_t)REC_CTX; };
+		d.pairs = [](uint32_t, const PairPtrs &p, const PairArgs &a, hipStream_t s) { return launch_pairs(p, a, s); };
+		// the merge forms the returned value from raw
+		d.link = !opts->clip ? 0 : (m->task == VBFM_TASK_CLASSIFICATION ? 2 : 1);
+		d.nvals = 1;
+		d.vals[0] = score;
+		rank_call(m, cs, contexts, excl_ptr, excl_idx, *opts, d, idx, count, st);
 	});
 }
 
-// vbfm_recommend's staging and phases with the variance sums beside the means: the preparation's
-// VAR form, k_ucb_pairs, the merge on key and k_ucb_finish for the returned values
+// vbfm_recommend's pipeline with the variance sums beside the means: the preparation's VAR form,
+// k_ucb_pairs, the merge on key and k_ucb_finish for the returned values
 int vbfm_recommend_ucb(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *contexts, const uint64_t *excl_ptr,
                        const uint32_t *excl_idx, const vbfm_recommend_ucb_opts *opts, int32_t *idx, double *key,
                        double *score, double *var, uint32_t *count, vbfm_recommend_stats *st)
 {
 	const std::string who = "vbfm_recommend_ucb";
-	if (!m) return mfail(nullptr, who + ": null model");
-	if (!cs || !contexts || !opts) return mfail(m, who + ": null argument");
-	if (m->info.kind == VBFM_MODEL_MCMC_CHAIN)
-		return mfail(m, who + ": a chain of draws (VBFM_MODEL_MCMC_CHAIN) is scored, not ranked: "
-		                "recommendation takes a model of one set of parameters");
-	return mguarded(m, [&] {
-		const double t_begin = wall_s();
+	return ranking_guarded(who, m, cs, contexts, opts, [&] {
 		const vbfm_recommend_ucb_opts o = *opts;
 		require_variance(m, who.c_str());
-		if (cs->m != m) throw who + ": the candidate set was made from another model";
-		if (!cs->tb) throw who + ": the candidate set holds no variance sums (it was made by vbfm_candidates_create; use vbfm_candidates_create_var)";
-		if (o.topn < 1 || o.topn > VBFM_REC_MAX_TOPN)
-			throw who + ": topn = " + std::to_string(o.topn) + " is outside 1 .. " + std::to_string(VBFM_REC_MAX_TOPN);
+		require_own_set(who, m, cs);
+		if (!cs->tb)
+			throw who + ": the candidate set holds no variance sums (it was made by vbfm_candidates_create; use vbfm_candidates_create_var)";
+		require_topn(who, o.topn);
 		if (!std::isfinite(o.beta)) throw who + ": beta = " + std::to_string(o.beta) + " is not a finite number";
 		if (o.noise != 0 && o.noise != 1) throw who + ": noise is 0 or 1";
-		require_model(m, who.c_str());
-		if (o.unknown_ids != 0 && o.unknown_ids != 1) throw who + ": unknown_ids is 0 (refuse) or 1 (skip)";
-		const uint32_t B = contexts->num_rows, M = cs->M;
-		if (B && (!idx || !count)) throw who + ": null result array";
-		const size_t topn = (size_t)o.topn;
-		const int k = cs->k;
-		vbfm_recommend_stats out = {};
-		check_exclusions(who, B, M, excl_ptr, excl_idx);
-		size_t need_in = 0, need_rows = 0;
-		const std::vector<ChunkPlan> plan = plan_chunks(contexts, o.chunk_bytes ? o.chunk_bytes : VBFM_SCORE_CHUNK_DEFAULT, who,
-		                                                &need_in, &need_rows);
-		const uint32_t ctx = ucb_ctx(need_rows, k, o.topn);
-		// a chunk in a slot: [row_ptr slice | entries | excl_ptr slice | excl_idx slice]; its results
-		// [key | score | var | idx | count]
-		size_t need_part = 0;
-		for (const ChunkPlan &p : plan) {
-			const uint32_t nr = p.r1 - p.r0;
-			if (excl_ptr) {
-				const size_t rows_bytes = ((size_t)nr + 1) * 8 + (contexts->row_ptr[p.r1] - contexts->row_ptr[p.r0]) * 8;
-				need_in = std::max(need_in, rows_bytes + ((size_t)nr + 1) * 8 + (excl_ptr[p.r1] - excl_ptr[p.r0]) * 4);
-			}
-			need_part = std::max(need_part, (size_t)nr * pick_slices(nr, M, ctx));
-		}
-		const auto out_doubles = [&](size_t nr) { return 3 * nr * topn + (nr * topn * 4 + nr * 4 + 7) / 8; };
-		staging_reserve(m, need_in, out_doubles(need_rows));
-		const size_t rows_pad = round_up(need_rows, ctx);
-		DevScratch<double> base_c(rows_pad), tb_c(rows_pad), qc(3 * rows_pad * (size_t)k), part_key(need_part * topn);
-		DevScratch<uint32_t> part_idx(need_part * topn), part_cnt(need_part);
-		DevScratch<unsigned long long> counters(2);
-		HIPCHK(hipMemsetAsync(counters, 0, 16, m->s));
-		HIPCHK(hipMemsetAsync(base_c, 0, rows_pad * 8, m->s));
-		HIPCHK(hipMemsetAsync(tb_c, 0, rows_pad * 8, m->s));
-		flags_reset(m);
-		PhaseEvents pe;
+		require_rest(who, m, o.unknown_ids, contexts, idx && count);
 		UcbArgs u;
 		u.s0 = m->info.k0 ? m->info.sigma_0_dash : 0.0;
 		u.na = o.noise ? 1.0 / m->info.alpha : 0.0;
 		u.beta = o.beta;
-		auto drain = [&](size_t i) {
-			vbfm_model::Slot &sl = m->slot[i & 1];
-			HIPCHK(hipEventSynchronize(sl.ev[SEV_DONE]));
-			const size_t r0 = plan[i].r0, nr = plan[i].r1 - plan[i].r0, n = nr * topn;
-			if (key) memcpy(key + r0 * topn, sl.h_out, n * 8);
-			if (score) memcpy(score + r0 * topn, sl.h_out + n, n * 8);
-			if (var) memcpy(var + r0 * topn, sl.h_out + 2 * n, n * 8);
-			memcpy(idx + r0 * topn, sl.h_out + 3 * n, n * 4);
-			memcpy(count + r0, (const uint8_t *)(sl.h_out + 3 * n) + n * 4, nr * 4);
-			out.ms_prepare += elapsed(pe.ev[i & 1][0], pe.ev[i & 1][1]);
-			out.ms_pairs += elapsed(pe.ev[i & 1][1], pe.ev[i & 1][2]);
-			out.ms_merge += elapsed(pe.ev[i & 1][2], pe.ev[i & 1][3]);
+		Ranking d;
+		d.who = who.c_str();
+		d.planes = 3;
+		d.tb = true;
+		d.tile = ucb_ctx;
+		d.pairs = [u](uint32_t ctx, const PairPtrs &p, const PairArgs &a, hipStream_t s) {
+			return launch_ucb_pairs(ctx, p, a, u, s);
 		};
-		for (size_t i = 0; i < plan.size(); i++) {
-			vbfm_model::Slot &sl = m->slot[i & 1];
-			if (i >= 2) drain(i - 2);   // the slot's previous chunk has left both of its buffers
-			const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
-			size_t bytes = stage_rows(sl.h_in, contexts, r0, nr);
-			const size_t excl_off = bytes;
-			uint64_t xe0 = 0, nx = 0;
-			if (excl_ptr) {
-				xe0 = excl_ptr[r0];
-				nx = excl_ptr[r0 + nr] - xe0;
-				memcpy(sl.h_in + bytes, excl_ptr + r0, ((size_t)nr + 1) * 8);
-				bytes += ((size_t)nr + 1) * 8;
-				if (nx) memcpy(sl.h_in + bytes, excl_idx + xe0, nx * 4);
-				bytes += nx * 4;
-			}
-			HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, bytes, hipMemcpyHostToDevice, m->s_copy));
-			HIPCHK(hipEventRecord(sl.ev[SEV_C1], m->s_copy));
-			HIPCHK(hipStreamWaitEvent(m->s, sl.ev[SEV_C1], 0));
-			hipEvent_t *ev = pe.ev[i & 1];
-			HIPCHK(hipEventRecord(ev[0], m->s));
-			launch_prepare_var(m, sl.d_in, nr, contexts->row_ptr[r0], r0, base_c, tb_c, qc, ctx);
-			HIPCHK(hipEventRecord(ev[1], m->s));
-			PairArgs a = {};
-			a.nB = nr; a.M = M; a.Mpad = cs->Mpad;
-			a.k = k;
-			a.w0 = m->info.k0 ? m->info.w0_or_mu0 : 0.0;
-			a.topn = o.topn;
-			a.slices = pick_slices(nr, M, ctx);
-			a.slice_len = std::max<uint32_t>(REC_STEP, round_up(((uint64_t)M + a.slices - 1) / a.slices, REC_STEP));
-			if (excl_ptr) {
-				a.excl_ptr = (const uint64_t *)(sl.d_in + excl_off);
-				a.excl_idx = (const uint32_t *)(sl.d_in + excl_off + ((size_t)nr + 1) * 8);
-				a.excl_base = xe0;
-			}
-			a.part_raw = part_key; a.part_idx = part_idx; a.part_cnt = part_cnt;
-			a.counters = counters;
-			HIPCHK(launch_ucb_pairs(ctx, qc, cs->qt, cs->zt, cs->ut, base_c, cs->base, tb_c, cs->tb, a, u, m->s));
-			HIPCHK(hipEventRecord(ev[2], m->s));
-			const size_t n = (size_t)nr * topn;
-			MergeArgs g = {};
-			g.part_raw = part_key; g.part_idx = part_idx; g.part_cnt = part_cnt;
-			g.nB = nr; g.slices = a.slices; g.topn = o.topn;
-			g.link = 0;                       // the lists' keys as they are; k_ucb_finish forms what is returned
-			g.score = sl.d_out;
-			g.idx = (int32_t *)(sl.d_out + 3 * n);
-			g.count = (uint32_t *)(g.idx + n);
-			HIPCHK(launch_merge(g, m->s));
+		d.link = 0;   // the lists' keys as they are; k_ucb_finish forms what is returned
+		d.nvals = 3;
+		d.vals[0] = key; d.vals[1] = score; d.vals[2] = var;
+		d.finish = [&, u](uint32_t ctx, const PairPtrs &p, const PairArgs &a, const MergeArgs &g, hipStream_t s) {
+			const size_t n = (size_t)a.nB * a.topn;
+			if (!n) return;
 			FinishArgs fa = {};
-			fa.ctx_all = qc; fa.ctx = ctx;
-			fa.qt = cs->qt; fa.zt = cs->zt; fa.ut = cs->ut;
-			fa.base_c = base_c; fa.base_j = cs->base; fa.tb_c = tb_c; fa.tb_j = cs->tb;
-			fa.nB = nr; fa.Mpad = cs->Mpad; fa.k = k; fa.topn = o.topn;
+			fa.ctx_all = p.ctx_all; fa.ctx = ctx;
+			fa.qt = p.qt; fa.zt = p.zt; fa.ut = p.ut;
+			fa.base_c = p.base_c; fa.base_j = p.base_j; fa.tb_c = p.tb_c; fa.tb_j = p.tb_j;
+			fa.nB = a.nB; fa.Mpad = a.Mpad; fa.k = a.k; fa.topn = a.topn;
 			fa.w0 = a.w0; fa.u = u;
 			fa.clip = o.clip != 0;
 			fa.mn = m->info.min_target; fa.mx = m->info.max_target;
 			fa.idx = g.idx; fa.count = g.count;
-			fa.key = sl.d_out; fa.score = sl.d_out + n; fa.var = sl.d_out + 2 * n;
-			if (n) {
-				k_ucb_finish<<<(unsigned)((n + 255) / 256), 256, 0, m->s>>>(fa);
-				HIPCHK(hipGetLastError());
-			}
-			HIPCHK(hipEventRecord(ev[3], m->s));
-			HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, out_doubles(nr) * 8, hipMemcpyDeviceToHost, m->s));
-			HIPCHK(hipEventRecord(sl.ev[SEV_DONE], m->s));
-			out.pairs += (uint64_t)nr * M;
-		}
-		for (size_t i = plan.size() >= 2 ? plan.size() - 2 : 0; i < plan.size(); i++) drain(i);
-		const ScoreFlags f = flags_read(m);
-		if (f.first != ~0ull && !o.unknown_ids) throw unknown_msg(m, f.first >> 32, (uint32_t)f.first);
-		unsigned long long cnt[2];
-		HIPCHK(hipMemcpyAsync(cnt, counters, 16, hipMemcpyDeviceToHost, m->s));
-		HIPCHK(hipStreamSynchronize(m->s));
-		out.n_chunks = (uint32_t)plan.size();
-		out.nonfinite_pairs = cnt[0];
-		out.excluded_hits = cnt[1];
-		out.ms_total = (wall_s() - t_begin) * 1e3;
-		if (st) *st = out;
+			fa.key = g.score; fa.score = g.score + n; fa.var = g.score + 2 * n;
+			k_ucb_finish<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(fa);
+			HIPCHK(hipGetLastError());
+		};
+		rank_call(m, cs, contexts, excl_ptr, excl_idx, vbfm_recommend_opts{o.topn, o.clip, o.unknown_ids, o.chunk_bytes}, d, idx,
+		          count, st);
 	});
 }
 

@@ -487,4 +487,34 @@ inline size_t stage_rows(uint8_t *h_in, const vbfm_csr *rows, uint32_t r0, uint3
 	return ptr_bytes + ne * 8;
 }
 
+// The two-slot rotation of a call's n chunks (vbfm_score, vbfm_recommend, vbfm_recommend_ucb): chunk i
+// lives in slot i & 1, its copy to the device runs on s_copy under the kernels of the chunk before, and
+// a slot is staged again only after its previous chunk has left both of its buffers (h_in by the copy,
+// h_out by collect). The caller supplies
+//   stage(i, slot)   -> the bytes of chunk i it wrote to slot.h_in; what it enqueues on s_copy runs
+//                       ahead of the copy (vbfm_score's SEV_C0, the start of its ms_copy);
+//   enqueue(i, slot):   chunk i's kernels on s (slot.d_in is complete there) and the copy of its results
+//                       to slot.h_out, also on s;
+//   collect(i, slot):   chunk i's results are in slot.h_out and its events have completed.
+template <class Stage, class Enqueue, class Collect>
+inline void rotate_chunks(vbfm_model *m, size_t n, Stage &&stage, Enqueue &&enqueue, Collect &&collect)
+{
+	auto drain = [&](size_t i) {
+		vbfm_model::Slot &sl = m->slot[i & 1];
+		HIPCHK(hipEventSynchronize(sl.ev[SEV_DONE]));
+		collect(i, sl);
+	};
+	for (size_t i = 0; i < n; i++) {
+		vbfm_model::Slot &sl = m->slot[i & 1];
+		if (i >= 2) drain(i - 2);
+		const size_t bytes = stage(i, sl);
+		HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, bytes, hipMemcpyHostToDevice, m->s_copy));
+		HIPCHK(hipEventRecord(sl.ev[SEV_C1], m->s_copy));
+		HIPCHK(hipStreamWaitEvent(m->s, sl.ev[SEV_C1], 0));
+		enqueue(i, sl);
+		HIPCHK(hipEventRecord(sl.ev[SEV_DONE], m->s));
+	}
+	for (size_t i = n >= 2 ? n - 2 : 0; i < n; i++) drain(i);
+}
+
 }  // namespace vbs

@@ -368,43 +368,36 @@ int vbfm_score(vbfm_model *m, const vbfm_csr *rows, const vbfm_score_opts *opts,
 		staging_reserve(m, need_in, need_rows * (var ? 2 : 1));
 		flags_reset(m);
 		const bool group = group_order(m, o, rows->nnz);
-		// chunk i's results back in the caller's arrays, its times added
-		auto drain = [&](size_t i) {
-			vbfm_model::Slot &sl = m->slot[i & 1];
-			HIPCHK(hipEventSynchronize(sl.ev[SEV_DONE]));
-			const uint32_t nr = plan[i].r1 - plan[i].r0;
-			memcpy(mean + plan[i].r0, sl.h_out, (size_t)nr * 8);
-			if (var) memcpy(var + plan[i].r0, sl.h_out + nr, (size_t)nr * 8);
-			out.ms_copy += elapsed(sl.ev[SEV_C0], sl.ev[SEV_C1]);
-			out.ms_kernel += elapsed(sl.ev[SEV_K0], sl.ev[SEV_K1]);
-		};
-		for (size_t i = 0; i < plan.size(); i++) {
-			vbfm_model::Slot &sl = m->slot[i & 1];
-			if (i >= 2) drain(i - 2);   // the slot's previous chunk has left both of its buffers
-			const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
-			const uint64_t e0 = rows->row_ptr[r0];
-			const size_t ptr_bytes = ((size_t)nr + 1) * 8;
-			const size_t in_bytes = stage_rows(sl.h_in, rows, r0, nr);
-			// the copy runs on its own stream, under the kernel of the chunk before
-			HIPCHK(hipEventRecord(sl.ev[SEV_C0], m->s_copy));
-			HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, in_bytes, hipMemcpyHostToDevice, m->s_copy));
-			HIPCHK(hipEventRecord(sl.ev[SEV_C1], m->s_copy));
-			HIPCHK(hipStreamWaitEvent(m->s, sl.ev[SEV_C1], 0));
-			ScoreArgs a = score_args(m, o.clip);
-			a.row_ptr = (const uint64_t *)sl.d_in;
-			a.ent = (const uint2 *)(sl.d_in + ptr_bytes);
-			a.ent_base = e0;
-			a.mean = sl.d_out;
-			a.var = var ? sl.d_out + nr : nullptr;
-			a.n = nr;
-			a.row0 = r0;
-			HIPCHK(hipEventRecord(sl.ev[SEV_K0], m->s));
-			score_rows(m, o, a, group, m->s);
-			HIPCHK(hipEventRecord(sl.ev[SEV_K1], m->s));
-			HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, (size_t)nr * (var ? 2 : 1) * 8, hipMemcpyDeviceToHost, m->s));
-			HIPCHK(hipEventRecord(sl.ev[SEV_DONE], m->s));
-		}
-		for (size_t i = plan.size() >= 2 ? plan.size() - 2 : 0; i < plan.size(); i++) drain(i);
+		rotate_chunks(
+		    m, plan.size(),
+		    [&](size_t i, vbfm_model::Slot &sl) {
+			    const size_t in_bytes = stage_rows(sl.h_in, rows, plan[i].r0, plan[i].r1 - plan[i].r0);
+			    HIPCHK(hipEventRecord(sl.ev[SEV_C0], m->s_copy));   // ms_copy: from here to the copy's end (SEV_C1)
+			    return in_bytes;
+		    },
+		    [&](size_t i, vbfm_model::Slot &sl) {
+			    const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
+			    ScoreArgs a = score_args(m, o.clip);
+			    a.row_ptr = (const uint64_t *)sl.d_in;
+			    a.ent = (const uint2 *)(sl.d_in + ((size_t)nr + 1) * 8);
+			    a.ent_base = rows->row_ptr[r0];
+			    a.mean = sl.d_out;
+			    a.var = var ? sl.d_out + nr : nullptr;
+			    a.n = nr;
+			    a.row0 = r0;
+			    HIPCHK(hipEventRecord(sl.ev[SEV_K0], m->s));
+			    score_rows(m, o, a, group, m->s);
+			    HIPCHK(hipEventRecord(sl.ev[SEV_K1], m->s));
+			    HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, (size_t)nr * (var ? 2 : 1) * 8, hipMemcpyDeviceToHost, m->s));
+		    },
+		    // chunk i's results back in the caller's arrays, its times added
+		    [&](size_t i, vbfm_model::Slot &sl) {
+			    const uint32_t nr = plan[i].r1 - plan[i].r0;
+			    memcpy(mean + plan[i].r0, sl.h_out, (size_t)nr * 8);
+			    if (var) memcpy(var + plan[i].r0, sl.h_out + nr, (size_t)nr * 8);
+			    out.ms_copy += elapsed(sl.ev[SEV_C0], sl.ev[SEV_C1]);
+			    out.ms_kernel += elapsed(sl.ev[SEV_K0], sl.ev[SEV_K1]);
+		    });
 		const ScoreFlags f = flags_read(m);
 		if (f.first != ~0ull && !o.unknown_ids)
 			throw unknown_msg(m, f.first >> 32, (uint32_t)f.first);

@@ -1190,20 +1190,26 @@ class Model:
         count; count [B] uint32), best first. A pair is valued as the mean of one row holding the
         context's and the candidate's entries. exclude: None, a list with one integer array of
         candidate indices (ascending) per context, or a (ptr, idx) pair."""
+        o = RecommendOpts(int(topn), int(bool(clip)), UNKNOWN_IDS[unknown_ids], int(chunk_bytes))
+        idx, (score,), count = self._rank(lib().vbfm_recommend, o, 1, contexts, candidates, topn, exclude)
+        return idx, score, count
+
+    def _rank(self, call, opts, nvals, contexts, candidates, topn, exclude):
+        """A ranking call of the library (vbfm_recommend, vbfm_recommend_ucb: the same arguments around
+        nvals [B, topn] float64 results): the rows, the exclusion arrays, the result arrays, the call
+        and its stats. Returns (idx, the nvals arrays, count)."""
         rows, _keep = self._rows(contexts)
-        B, topn = rows.num_rows, int(topn)
+        B, shape = rows.num_rows, max(int(topn), 0)
         xp, xi = self._exclusions(exclude, B)
-        shape = max(topn, 0)
         idx = np.full((B, shape), -1, dtype=np.int32)
-        score = np.full((B, shape), np.nan)
+        vals = [np.full((B, shape), np.nan) for _ in range(nvals)]
         count = np.zeros(B, dtype=np.uint32)
         st = RecommendStats()
-        o = RecommendOpts(topn, int(bool(clip)), UNKNOWN_IDS[unknown_ids], int(chunk_bytes))
-        self._mcheck(lib().vbfm_recommend(self._m, candidates._c, C.byref(rows), _ptr(xp, P_u64), _ptr(xi, P_u32),
-                                          C.byref(o), idx.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(score, P_f64),
-                                          _ptr(count, P_u32), C.byref(st)))
+        self._mcheck(call(self._m, candidates._c, C.byref(rows), _ptr(xp, P_u64), _ptr(xi, P_u32), C.byref(opts),
+                          idx.ctypes.data_as(C.POINTER(C.c_int32)), *[_ptr(v, P_f64) for v in vals], _ptr(count, P_u32),
+                          C.byref(st)))
         self.last_recommend_stats = st.as_dict()
-        return idx, score, count
+        return idx, vals, count
 
     @staticmethod
     def _exclusions(exclude, B):
@@ -1234,19 +1240,8 @@ class Model:
         key the value ranked on, score as recommend returns it, var the pair's T without the noise
         term; sd is sqrt(T), with noise=True sqrt(T + 1 / alpha). A negative beta ranks on a lower
         bound. exclude as recommend takes it."""
-        rows, _keep = self._rows(contexts)
-        B, topn = rows.num_rows, int(topn)
-        xp, xi = self._exclusions(exclude, B)
-        shape = max(topn, 0)
-        idx = np.full((B, shape), -1, dtype=np.int32)
-        key, score, var = (np.full((B, shape), np.nan) for _ in range(3))
-        count = np.zeros(B, dtype=np.uint32)
-        st = RecommendStats()
-        o = RecommendUcbOpts(topn, int(bool(clip)), UNKNOWN_IDS[unknown_ids], int(chunk_bytes), float(beta), int(bool(noise)))
-        self._mcheck(lib().vbfm_recommend_ucb(self._m, candidates._c, C.byref(rows), _ptr(xp, P_u64), _ptr(xi, P_u32),
-                                              C.byref(o), idx.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(key, P_f64),
-                                              _ptr(score, P_f64), _ptr(var, P_f64), _ptr(count, P_u32), C.byref(st)))
-        self.last_recommend_stats = st.as_dict()
+        o = RecommendUcbOpts(int(topn), int(bool(clip)), UNKNOWN_IDS[unknown_ids], int(chunk_bytes), float(beta), int(bool(noise)))
+        idx, (key, score, var), count = self._rank(lib().vbfm_recommend_ucb, o, 3, contexts, candidates, topn, exclude)
         return idx, key, score, var, count
 
     def close(self):

@@ -16,91 +16,16 @@ import subprocess
 import numpy as np
 import pytest
 
-import synth
 import vbfm
 from conftest import GOLDEN, ROOT
+from recommend_cases import ALS, D_SYNTH, F, MCMC_DRAW, VB, bits, candidates, contexts, expand, make_model, same
 
 pytestmark = pytest.mark.gpu
 REL = 1e-9
 CLI = os.path.join(ROOT, "scalable-variational-bayesian-factorization-machine_amd", "bin", "libFM")
-F, S = 5, 50                      # contexts: synth.generate's 5 fields x 50 ids
-D_SYNTH = F * S + 1               # id 250 is in the model and in no context
 # the pair kernel's geometry (csrc/vbfm_recommend.hip): a wave owns REC_CTX contexts, a workgroup
 # REC_TILE_B (half of it when topn > 64); a wave step takes REC_STEP candidates, slices are whole steps
 REC_CTX, REC_TILE_B, REC_STEP = 16, 64, 128
-VB, ALS, MCMC_DRAW = 0, 2, 3
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def same(a, b):
-    """idx, score, count triples bit for bit."""
-    return (np.array_equal(a[0], b[0]) and np.array_equal(bits(a[1]), bits(b[1])) and np.array_equal(a[2], b[2]))
-
-
-def make_model(tmp_path, kind, k, k0, k1, D=D_SYNTH, seed=1, task="r", mn=-1.0, mx=1.5, edit=None):
-    rng = np.random.default_rng(1000 * seed + k)
-    vbk = kind in (0, 1)
-    info = dict(kind=kind, k0=k0, k1=k1, num_factor=k, num_attribute=D, min_target=mn, max_target=mx, iter=1,
-                has_variance=int(vbk), w0_or_mu0=0.37, sigma_0_dash=0.02 if vbk else 0.0, alpha=1.5)
-    w, v = 0.3 * rng.standard_normal(D), 0.3 * rng.standard_normal(k * D)
-    if edit:
-        edit(w, v)
-    if vbk:
-        p = {"mu_w": w, "sigma_w": 0.01 + 0.05 * rng.random(D), "mu_v": v, "sigma_v": 0.01 + 0.05 * rng.random(k * D)}
-    else:
-        p = {"w": w, "v": v}
-    path = str(tmp_path / ("m_%d_%d_%d%d_%s.vbfm" % (kind, k, k0, k1, task)))
-    vbfm.Model.write_params(path, info, p, task=task)
-    return vbfm.Model.load(path)
-
-
-_CTX = {}
-
-
-def contexts(B, seed=3):
-    """synth.generate rows (non-unit x), every third value negated."""
-    if (B, seed) not in _CTX:
-        rp, f, v, _ = synth.generate(B, F, S, seed, 1)
-        v = v.copy()
-        v[::3] *= -1.0
-        _CTX[(B, seed)] = (rp, f, v)
-    return _CTX[(B, seed)]
-
-
-def candidates(M, seed=5, D=D_SYNTH):
-    """M rows of 1-3 entries over the contexts' id range (so candidates share ids with contexts),
-    non-unit and negative x, a repeated id now and then; row 1 (when there is one) is empty."""
-    rng = np.random.default_rng(seed)
-    n = rng.integers(1, 4, size=M)
-    if M > 1:
-        n[1] = 0
-    rp = np.zeros(M + 1, dtype=np.uint64)
-    np.cumsum(n, out=rp[1:])
-    f = rng.integers(0, D - 1, size=int(rp[-1])).astype(np.uint32)
-    v = (rng.standard_normal(int(rp[-1])) + 0.25).astype(np.float32)
-    return rp, f, v
-
-
-def expand(ctx, cand):
-    """The B * M rows (context entries, then candidate entries), context-major."""
-    crp, cf, cv = ctx
-    jrp, jf, jv = cand
-    B, M = len(crp) - 1, len(jrp) - 1
-    crp, jrp = crp.astype(np.int64), jrp.astype(np.int64)
-    fs, vs, lens = [], [], np.zeros(B * M, dtype=np.int64)
-    for c in range(B):
-        a_f, a_v = cf[crp[c]:crp[c + 1]], cv[crp[c]:crp[c + 1]]
-        for j in range(M):
-            fs += [a_f, jf[jrp[j]:jrp[j + 1]]]
-            vs += [a_v, jv[jrp[j]:jrp[j + 1]]]
-            lens[c * M + j] = len(a_f) + jrp[j + 1] - jrp[j]
-    rp = np.zeros(B * M + 1, dtype=np.uint64)
-    np.cumsum(lens, out=rp[1:])
-    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dtype=dt)
-    return rp, cat(fs, np.uint32), cat(vs, np.float32)
 
 
 def reference(m, ctx, cand, clip=False, unknown_ids="refuse"):
@@ -209,7 +134,8 @@ def test_results_do_not_depend_on_chunks_slices_or_reuse(tmp_path, monkeypatch):
     cs = m.candidates(cand)
     monkeypatch.delenv("VBFM_REC_SLICES", raising=False)
     base = m.recommend(ctx, cs, topn, exclude=excl)
-    check(m.recommend(ctx, cs, topn, exclude=excl, clip=False), reference(m, ctx, cand), topn, excl, "geometry base")
+    ref = reference(m, ctx, cand)
+    check(m.recommend(ctx, cs, topn, exclude=excl, clip=False), ref, topn, excl, "geometry base")
     assert m.last_recommend_stats["n_chunks"] == 1
     again = m.recommend(ctx, cs, topn, exclude=excl)           # the candidate set reused
     assert same(base, again)
@@ -222,6 +148,12 @@ def test_results_do_not_depend_on_chunks_slices_or_reuse(tmp_path, monkeypatch):
         monkeypatch.setenv("VBFM_REC_SLICES", slices)
         assert same(base, m.recommend(ctx, cs, topn, exclude=excl)), slices
         assert same(base, m.recommend(ctx, cs, topn, exclude=excl, chunk_bytes=8 + 3 * row_bytes)), slices
+    for big in (64, 100):                                      # the other list capacities' workgroups, with exclusions
+        monkeypatch.delenv("VBFM_REC_SLICES")
+        want = m.recommend(ctx, cs, big, exclude=excl, clip=False)
+        check(want, ref, big, excl, "geometry topn=%d" % big)
+        monkeypatch.setenv("VBFM_REC_SLICES", "7")
+        assert same(want, m.recommend(ctx, cs, big, exclude=excl, clip=False)), big
     cs.close()
     m.close()
 
@@ -269,8 +201,8 @@ def test_a_nonfinite_candidate_is_never_returned(tmp_path):
     f[int(rp[special])] = D_SYNTH - 1                          # the only row that holds id 250; no context does
     cand = (rp, f, v)
 
-    def inf_weight(w, v_):
-        w[D_SYNTH - 1] = np.inf
+    def inf_weight(p):
+        p["w"][D_SYNTH - 1] = np.inf
 
     (tmp_path / "a").mkdir()
     (tmp_path / "b").mkdir()
