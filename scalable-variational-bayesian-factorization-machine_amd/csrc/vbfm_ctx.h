@@ -1,6 +1,6 @@
 // vbfm_ctx.h -- the learner context behind include/vbfm.h and the host-side helpers its
 // front ends share: the VB learner (vbfm_capi.hip), the MCMC / ALS learner (vbfm_mcmc_capi.hip)
-// and the online learner (vbfm_online.hip), over the exchange (vbfm_comm.hip), the schedule
+// and the online learner (vbfm_online_capi.hip), over the exchange (vbfm_comm.hip), the schedule
 // (vbfm_schedule.hip), the row stores (vbfm_store.hip), checkpoints (vbfm_ckpt.hip) and the
 // synthetic data (vbfm_synth.hip). Internal to libvbfm; not part of the ABI.
 #pragma once
@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 extern "C" const char *vbfm_host_last_error(void);
@@ -32,7 +33,7 @@ extern "C" int vbfm_host_model_read_raw(const char *path, vbfm_model_info *info,
                                         void *user);
 
 struct McState;   // vbfm_mcmc_capi.hip
-struct OvState;   // vbfm_online.hip
+struct OvState;   // vbfm_online.h
 
 namespace vbi {
 
@@ -72,17 +73,37 @@ template <class T> inline void dfree(T *&p)
 	p = nullptr;
 }
 
-// a device buffer freed when its scope ends, normally or by an exception (dfree(buf.p) frees it
-// early; a default-constructed one adopts whatever is put into p); it passes for its pointer
-template <class T> struct DevScratch {
+// an owning device buffer: freed when its scope (or its owner) ends, normally or by an exception;
+// it passes for its pointer. reserve(n) reallocates only when n exceeds the capacity and alloc(n)
+// always; neither keeps the contents. dfree(buf.p) frees it early, std::exchange(buf.p, nullptr)
+// hands the memory to another owner, and an empty one adopts whatever is put into p (cap stays 0)
+template <class T> struct DevBuf {
 	T *p = nullptr;
-	DevScratch() = default;
-	explicit DevScratch(size_t n) : p(dalloc<T>(n)) {}
-	~DevScratch() { dfree(p); }
+	size_t cap = 0;   // elements asked for by the last alloc / reserve
+	DevBuf() = default;
+	explicit DevBuf(size_t n) { alloc(n); }
+	~DevBuf() { dfree(p); }
+	DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+	DevBuf &operator=(DevBuf &&o) noexcept
+	{
+		std::swap(p, o.p);
+		std::swap(cap, o.cap);
+		return *this;
+	}
 	operator T *() const { return p; }
-	DevScratch(const DevScratch &) = delete;
-	DevScratch &operator=(const DevScratch &) = delete;
+	void alloc(size_t n)
+	{
+		dfree(p);
+		cap = 0;
+		p = dalloc<T>(n);
+		cap = n;
+	}
+	void reserve(size_t n)
+	{
+		if (n > cap) alloc(n);
+	}
 };
+template <class T> using DevScratch = DevBuf<T>;   // the name its scoped uses keep
 
 enum { EV_BEGIN, EV_W0, EV_W, EV_V, EV_HYPER, EV_TEST, EV_TP0, EV_TP1, EV_N };
 
@@ -105,7 +126,8 @@ inline int defer_nt_bits()
 }
 
 // test hook: VBFM_FAULT=<where> makes the named step throw as a failed HIP call would (the error
-// paths of the store build and the per-level steps, tests/test_placement_gpu.py)
+// paths of the store build and the per-level steps, tests/test_placement_gpu.py; online_init: a
+// vbfm_online_init that fails with its state half built, tests/test_lifecycle_gpu.py)
 inline bool fault_at(const char *where)
 {
 	const char *e = getenv("VBFM_FAULT");
@@ -474,7 +496,7 @@ void mc_model_scalars(vbfm_ctx *c, double *w0, double *alpha, bool *sample);
 // the train targets changed under the row caches (vbfm_synth_binarize): vbfm_mcmc_init_caches again
 void mc_drop_caches(vbfm_ctx *c);
 
-// ---- vbfm_online.hip: the online VB learner ---------------------------------------------------
+// ---- vbfm_online_capi.hip: the online VB learner ----------------------------------------------
 void ov_free(vbfm_ctx *c);
 // the per-feature fields of LevelArgs for the w sweep or factor f
 void ov_level_args(vbfm_ctx *c, LevelArgs &a, bool is_w, int f);

@@ -35,19 +35,20 @@ constexpr uint32_t MC_RED_BLOCKS = 512;
 }  // namespace
 
 struct McState {
+	template <class T> using DevBuf = vbi::DevBuf<T>;   // every device buffer frees itself (mc_free)
 	int sample = 0, multilevel = 0, rng = VBFM_RNG_REFERENCE;
 	uint32_t seed = 1;
 	vbrng::Glibc stream;
 	double w0 = 0.0, alpha = 1.0, reg0 = 0.0;
 	std::vector<double> w_mu, w_lambda, v_mu, v_lambda;   // [G], [G], [G*k], [G*k] ([g][f])
-	double *hyp_d = nullptr;                              // the four arrays, in that order
-	double *z_d = nullptr;                                // [D] normals of one sweep (reference RNG)
+	DevBuf<double> hyp_d;                                 // the four arrays, in that order
+	DevBuf<double> z_d;                                   // [D] normals of one sweep (reference RNG)
 	std::vector<double> z_h;
 	std::vector<uint8_t> col_nonempty;                    // [train nf] over all shards
-	double *pred_this = nullptr, *pred_sum = nullptr;     // [test rows]
-	double *vc = nullptr;                                 // [k*D] compact v for the re-prediction
-	double *pc = nullptr;                                 // [2*D] last factor's v and w (fused re-prediction)
-	double *red_d = nullptr;                              // [4 * MC_RED_BLOCKS]
+	DevBuf<double> pred_this, pred_sum;                   // [test rows]
+	DevBuf<double> vc;                                    // [k*D] compact v for the re-prediction
+	DevBuf<double> pc;                                    // [2*D] last factor's v and w (fused re-prediction)
+	DevBuf<double> red_d;                                 // [4 * MC_RED_BLOCKS]
 	std::vector<double> red_h;
 	uint32_t iter = 0;
 	bool caches = false;
@@ -56,24 +57,22 @@ struct McState {
 	// device draws), the latent targets drawn from the reference's stream
 	vbfm_mcmc_class_stats cls = {};
 	uint64_t row0 = 0;
-	double *s_d = nullptr;                                // [s_cap]: grows with the train set (class_train_step)
-	size_t s_cap = 0;
+	DevBuf<double> s_d;                                   // grows with the train set (class_train_step)
 	std::vector<double> s_h;
 	uint32_t hc[HC_N] = {};
 	hipEvent_t ev[MEV_N] = {};
+	~McState()
+	{
+		for (hipEvent_t e : ev)
+			if (e) (void)hipEventDestroy(e);
+	}
 };
 
 namespace vbi {
 
 void mc_free(vbfm_ctx *c)
 {
-	McState *m = c->mc;
-	if (!m) return;
-	dfree(m->hyp_d); dfree(m->z_d); dfree(m->pred_this); dfree(m->pred_sum); dfree(m->red_d); dfree(m->vc); dfree(m->pc);
-	dfree(m->s_d);
-	for (int i = 0; i < MEV_N; i++)
-		if (m->ev[i]) (void)hipEventDestroy(m->ev[i]);
-	delete m;
+	delete c->mc;   // McState frees its buffers and events
 	c->mc = nullptr;
 }
 
@@ -425,7 +424,7 @@ void mc_predict(vbfm_ctx *c, bool train = true)
 	// (half the bytes of every entry's k factors), refreshed once per re-prediction
 	const size_t kd = (size_t)c->k * c->D;
 	const int btr = blocked_predict(c, c->tr), bte = c->e_test ? blocked_predict(c, c->te) : 0;
-	if ((btr == 2 || bte == 2) && c->k <= 256 && kd && !m.vc) m.vc = dalloc<double>(kd);
+	if ((btr == 2 || bte == 2) && c->k <= 256 && kd && !m.vc) m.vc.alloc(kd);
 	bool fresh = false;
 	if (train) {
 		HIPCHK(vbk::predict_e_compact(c->tr.row_ptr, c->tr.csr, c->ms_v, c->ms_w, c->k, c->k1, c->k0, m.w0,
@@ -441,10 +440,8 @@ void require_test(vbfm_ctx *c)
 {
 	if (!c->e_test) throw std::string("no test data set (vbfm_set_test)");
 	McState &m = *c->mc;
-	dfree(m.pred_this);
-	dfree(m.pred_sum);
-	m.pred_this = dalloc<double>(c->te.n);
-	m.pred_sum = dalloc<double>(c->te.n);
+	m.pred_this.alloc(c->te.n);
+	m.pred_sum.alloc(c->te.n);
 	HIPCHK(hipMemsetAsync(m.pred_sum, 0, (size_t)std::max(c->te.n, 1u) * 8, c->s));
 	HIPCHK(hipMemsetAsync(m.pred_this, 0, (size_t)std::max(c->te.n, 1u) * 8, c->s));
 }
@@ -513,12 +510,7 @@ double class_train_step(vbfm_ctx *c)
 				      " (the reference's truncated-normal draw would not return)";
 			m.s_h[r] = y[r] >= 0.0f ? m.stream.left_tgaussian(0.0, yh[r], 1.0) : m.stream.right_tgaussian(0.0, yh[r], 1.0);
 		}
-		if (n > m.s_cap) {   // a larger train set than the buffer was made for
-			dfree(m.s_d);
-			m.s_cap = 0;
-			m.s_d = dalloc<double>(n);
-			m.s_cap = n;
-		}
+		m.s_d.reserve(n);   // grows for a larger train set than the buffer was made for
 		if (n) HIPCHK(hipMemcpyAsync(m.s_d, m.s_h.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->s));
 	} else if (m.sample) {
 		mode = VBFM_CLASS_DEVICE;
@@ -556,9 +548,9 @@ int vbfm_mcmc_init(vbfm_ctx *c, const vbfm_mcmc_config *cfg)
 		m.alpha = 1.0;
 		m.w0 = 0.0;
 		apply_regular(c, cfg->regular, cfg->num_regular);
-		m.hyp_d = dalloc<double>(2 * G_(c) + 2 * GK(c));
-		m.z_d = dalloc<double>(c->D);
-		m.red_d = dalloc<double>(4 * MC_RED_BLOCKS);
+		m.hyp_d.alloc(2 * G_(c) + 2 * GK(c));
+		m.z_d.alloc(c->D);
+		m.red_d.alloc(4 * MC_RED_BLOCKS);
 		m.red_h.assign(4 * MC_RED_BLOCKS, 0.0);
 		upload_hyper(c);
 		// srand(seed); fm.v ~ N(0, init_stdev) (fm_model.h:97), then fm.w (libfm.cpp:298)
@@ -719,7 +711,7 @@ int vbfm_mcmc_iterate(vbfm_ctx *c, vbfm_mcmc_stats *o)
 		for (uint32_t b = 0; b < MC_RED_BLOCKS; b++)
 			for (int q = 0; q < 4; q++) tm[q] += m.red_h[4 * b + q];
 		if (fused) {   // yhat of train from the sweeps' accumulators + the last factor and w
-			if (!m.pc) m.pc = dalloc<double>(2 * (size_t)c->D);
+			if (!m.pc) m.pc.alloc(2 * (size_t)c->D);
 			HIPCHK(vbk::mc_pred_final(c->tr.row_ptr, c->tr.csr, c->ms_v, c->ms_w, c->k, c->k1, c->k0, m.w0, c->k >= 2,
 			                          c->rows, c->store.rows_lorder ? c->store.lpos0 : nullptr, c->tr.n, c->D, m.pc, c->scratch_n,
 			                          c->s));

@@ -194,7 +194,8 @@ def test_attribute_groups_vs_oracle(name, nb, form, monkeypatch):
 def test_wide_vs_oracle(form, xmode, monkeypatch):
     """Columns up to 520 entries in one batch: the 256-lane column kernel (form column), and on the
     store k_ov_lord<64> with runs beyond OV_CAP, read and written past the staged records. With
-    nothing set (form padded) k_ov_pad_check sends the batch to the packed layout."""
+    nothing set (form padded) k_ov_pad_check (csrc/vbfm_online_batch.hip) sends the batch to the packed
+    layout."""
     _vs_oracle("wide", 1, 3, xmode, form, False, monkeypatch)
 
 
