@@ -34,9 +34,9 @@ double finish_sum(vbfm_ctx *c, uint32_t nblocks)
 	return s;
 }
 
-void free_data(DevData &d)
+void free_data(DataBuf &b, DevData &d)
 {
-	dfree(d.col_ptr); dfree(d.csc); dfree(d.row_ptr); dfree(d.csr); dfree(d.target);
+	b = DataBuf();
 	d = DevData();
 }
 
@@ -54,9 +54,9 @@ void check_csc(const vbfm_csc *in)
 }
 
 // pad col_ptr to nf_pad columns (trailing empty columns), upload data set
-void upload(vbfm_ctx *c, DevData &d, const vbfm_csc *in, uint32_t nf_pad)
+void upload(vbfm_ctx *c, DataBuf &b, DevData &d, const vbfm_csc *in, uint32_t nf_pad)
 {
-	free_data(d);
+	free_data(b, d);
 	d.n = in->num_rows;
 	d.nf_local = in->num_feature;
 	d.nf = std::max(nf_pad, in->num_feature);
@@ -64,11 +64,11 @@ void upload(vbfm_ctx *c, DevData &d, const vbfm_csc *in, uint32_t nf_pad)
 	std::vector<uint64_t> cp((size_t)d.nf + 1, in->nnz);
 	if (in->num_feature) memcpy(cp.data(), in->col_ptr, ((size_t)in->num_feature + 1) * sizeof(uint64_t));
 	else cp[0] = 0;
-	d.col_ptr = dalloc<uint64_t>(cp.size());
-	d.csc = dalloc<uint2>(d.nnz);
-	d.row_ptr = dalloc<uint64_t>((size_t)d.n + 1);
-	d.csr = dalloc<uint2>(d.nnz);
-	d.target = dalloc<float>(d.n);
+	d.col_ptr = b.col_ptr.alloc(cp.size());
+	d.csc = b.csc.alloc(d.nnz);
+	d.row_ptr = b.row_ptr.alloc((size_t)d.n + 1);
+	d.csr = b.csr.alloc(d.nnz);
+	d.target = b.target.alloc(d.n);
 	HIPCHK(hipMemcpyAsync(d.col_ptr, cp.data(), cp.size() * 8, hipMemcpyHostToDevice, c->s));
 	if (d.nnz) HIPCHK(hipMemcpyAsync(d.csc, in->col_ent, d.nnz * 8, hipMemcpyHostToDevice, c->s));
 	HIPCHK(vbk::build_csr(d.col_ptr, d.csc, d.nf_local, d.n, d.nnz, d.row_ptr, d.csr, c->s));
@@ -101,15 +101,15 @@ void build_chunks(vbfm_ctx *c)
 	}
 	gchunk[c->G] = (uint32_t)c->chunks_h.size();
 	const size_t nc = c->chunks_h.size();
-	c->perm_d = dalloc<uint32_t>(c->D);
+	c->perm_d.alloc(c->D);
 	if (c->D) HIPCHK(hipMemcpy(c->perm_d, perm.data(), c->D * 4, hipMemcpyHostToDevice));
-	c->chunks_d = dalloc<vbk::Chunk>(nc);
+	c->chunks_d.alloc(nc);
 	if (nc) HIPCHK(hipMemcpy(c->chunks_d, c->chunks_h.data(), nc * sizeof(vbk::Chunk), hipMemcpyHostToDevice));
-	c->gchunk_d = dalloc<uint32_t>(gchunk.size());
+	c->gchunk_d.alloc(gchunk.size());
 	HIPCHK(hipMemcpy(c->gchunk_d, gchunk.data(), gchunk.size() * 4, hipMemcpyHostToDevice));
-	c->chunk_out_d = dalloc<double>(nc + (size_t)c->k * c->G);   // w partials, then the factor sums
+	c->chunk_out_d.alloc(nc + (size_t)c->k * c->G);   // w partials, then the factor sums
 	c->vseg_d = c->chunk_out_d + nc;
-	c->vpart_d = dalloc<double>(nc * (size_t)std::max(c->k, 1));
+	c->vpart_d.alloc(nc * (size_t)std::max(c->k, 1));
 }
 
 // w: chunk results summed per group in chunk order on the host; factors: k_vsums (fixed
@@ -226,9 +226,8 @@ size_t prof_begin(vbfm_ctx *c, int kind, hipStream_t st)
 		for (size_t i = 0; i < add; i++) {
 			// timestamps only: no system-scope release / acquire (a default event's cache
 			// writeback + invalidate costs ~4 us per record between short level launches)
-			hipEvent_t e;
-			HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-			c->prof.pev.push_back(e);
+			c->prof.pev.emplace_back();
+			c->prof.pev.back().create(hipEventDisableSystemFence);
 		}
 	}
 	const size_t a = c->prof.pev_used;
@@ -241,12 +240,6 @@ size_t prof_begin(vbfm_ctx *c, int kind, hipStream_t st)
 void prof_end(vbfm_ctx *c, size_t a, hipStream_t st)
 {
 	if (c->prof.on && a != NO_SPAN) HIPCHK(hipEventRecord(c->prof.pev[a + 1], st ? st : c->s));
-}
-
-void prof_free(vbfm_ctx *c)
-{
-	for (hipEvent_t e : c->prof.pev) (void)hipEventDestroy(e);
-	c->prof = {};
 }
 
 // the long columns of level l (fused single-rank sweep of either layout)
@@ -600,10 +593,10 @@ float ev_ms(vbfm_ctx *c, int a, int b)
 void alloc_rows(vbfm_ctx *c)
 {
 	lord_release(c, false);   // a new train set: the old records are discarded
-	dfree(c->rows);
-	dfree(c->scratch_n);
-	c->rows = dalloc<RowRec>(c->tr.n);
-	c->scratch_n = dalloc<double>(c->tr.n);
+	c->rec_release(c->rows);
+	c->scratch_n.reset();
+	c->rows = c->rec_alloc(c->tr.n);
+	c->scratch_n.alloc(c->tr.n);
 	HIPCHK(hipMemsetAsync(c->rows, 0, (size_t)std::max(c->tr.n, 1u) * sizeof(RowRec), c->s));
 	uint64_t n = c->tr.n;
 	c->n_global = n;
@@ -620,7 +613,7 @@ void alloc_rows(vbfm_ctx *c)
 uint32_t global_nf(vbfm_ctx *c, uint32_t nf)
 {
 	if (!c->multi()) return nf;
-	DevScratch<uint32_t> w(1);
+	DevBuf<uint32_t> w(1);
 	HIPCHK(hipMemcpyAsync(w, &nf, 4, hipMemcpyHostToDevice, c->s));
 	allreduce_dev(c, w, 1, ncclUint32, ncclMax);
 	uint32_t out = 0;
@@ -678,9 +671,9 @@ int vbfm_create(vbfm_ctx **out, const vbfm_config *cfg)
 		c->debug_skew = sk && sk[0] == '1';
 	}
 	int rc = guarded(c, [&] {
-		HIPCHK(hipStreamCreateWithFlags(&c->s, hipStreamNonBlocking));
-		HIPCHK(hipStreamCreateWithFlags(&c->s_test, hipStreamNonBlocking));
-		for (int i = 0; i < EV_N; i++) HIPCHK(hipEventCreate(&c->ev[i]));
+		c->s.create();
+		c->s_test.create();
+		for (Event &e : c->ev) e.create();
 		c->group_h.assign(c->D, 0);
 		if (cfg->attr_group)
 			for (uint32_t i = 0; i < c->D; i++) {
@@ -689,12 +682,12 @@ int vbfm_create(vbfm_ctx **out, const vbfm_config *cfg)
 			}
 		c->per_group.assign(c->G, 0);
 		for (uint32_t i = 0; i < c->D; i++) c->per_group[c->group_h[i]]++;
-		c->group_d = dalloc<uint32_t>(c->D);
+		c->group_d.alloc(c->D);
 		if (c->D) HIPCHK(hipMemcpy(c->group_d, c->group_h.data(), c->D * 4, hipMemcpyHostToDevice));
-		c->ms_v = dalloc<double2>((size_t)c->k * c->D);
-		c->ms_w = dalloc<double2>(c->D);
-		c->hyp_w_d = dalloc<double>(c->G);
-		c->hyp_v_d = dalloc<double>((size_t)c->G * c->k);
+		c->ms_v.alloc((size_t)c->k * c->D);
+		c->ms_w.alloc(c->D);
+		c->hyp_w_d.alloc(c->G);
+		c->hyp_v_d.alloc((size_t)c->G * c->k);
 		c->hyp_w.assign(c->G, 1.0);               // fm_learn_vb.h:707-708
 		c->hyp_v.assign((size_t)c->G * c->k, 1.0);
 		upload_hyp(c);
@@ -703,9 +696,9 @@ int vbfm_create(vbfm_ctx **out, const vbfm_config *cfg)
 		if ((size_t)c->k * c->D)
 			HIPCHK(hipMemcpy(c->ms_v, init.data(), (size_t)c->k * c->D * 16, hipMemcpyHostToDevice));
 		if (c->D) HIPCHK(hipMemcpy(c->ms_w, init.data(), (size_t)c->D * 16, hipMemcpyHostToDevice));
-		c->red_d = dalloc<double>(2 * vbfm_ctx::RED_BLOCKS);
+		c->red_d.alloc(2 * vbfm_ctx::RED_BLOCKS);
 		c->red_h.assign(2 * vbfm_ctx::RED_BLOCKS, 0.0);
-		c->counters = dalloc<uint32_t>(CNT_N);
+		c->counters.alloc(CNT_N);
 		HIPCHK(hipMemset(c->counters, 0, CNT_N * 4));
 		build_chunks(c);
 	});
@@ -718,37 +711,27 @@ int vbfm_create(vbfm_ctx **out, const vbfm_config *cfg)
 	return 0;
 }
 
+// the learner states first (their events and buffers), the communicator, then the members, last to first
+vbfm_ctx::~vbfm_ctx()
+{
+	mc_free(this);
+	ov_free(this);
+	if (net.comm) ncclCommDestroy(net.comm);
+}
+
 void vbfm_destroy(vbfm_ctx *c)
 {
 	if (!c) return;
 	(void)hipSetDevice(c->dev);
 	if (c->net.failed && c->s) {
 		// an aborted communicator: RCCL's kernels leave on the abort, but a stream still busy after
-		// 10 s is left to the process's exit (freeing under it would block in a device synchronise)
+		// 10 s is left to the process's exit with everything the context owns, the context itself
+		// included (freeing under it would block in a device synchronise)
 		const double end = wall_s() + 10.0;
 		while (hipStreamQuery(c->s) == hipErrorNotReady && wall_s() < end) usleep(1000);
-		if (hipStreamQuery(c->s) == hipErrorNotReady) {
-			delete c;
-			return;
-		}
+		if (hipStreamQuery(c->s) == hipErrorNotReady) return;
 	}
 	if (c->s) (void)hipStreamSynchronize(c->s);
-	free_data(c->tr);
-	free_data(c->te);
-	dfree(c->rows); dfree(c->scratch_n); dfree(c->e_test); dfree(c->pred_test);
-	dfree(c->ms_v); dfree(c->ms_w); dfree(c->hyp_w_d); dfree(c->hyp_v_d); dfree(c->group_d);
-	dfree(c->level_feats); dfree(c->dup); dfree(c->red_d); dfree(c->perm_d); dfree(c->chunks_d);
-	dfree(c->chunk_out_d); c->vseg_d = nullptr; dfree(c->gchunk_d); dfree(c->vpart_d); dfree(c->counters); dfree(c->stats);
-	store_release(c);
-	fs_free(c);
-	mc_free(c);
-	ov_free(c);
-	prof_free(c);
-	comm_free(c);
-	for (int i = 0; i < EV_N; i++)
-		if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-	if (c->s) (void)hipStreamDestroy(c->s);
-	if (c->s_test) (void)hipStreamDestroy(c->s_test);
 	delete c;
 }
 
@@ -760,7 +743,7 @@ int vbfm_set_train(vbfm_ctx *c, const vbfm_csc *in)
 		check_csc(in);
 		const uint32_t nf = global_nf(c, in->num_feature);
 		if (nf > c->D) throw std::string("train num_feature exceeds num_attribute");
-		upload(c, c->tr, in, nf);
+		upload(c, c->tr_buf, c->tr, in, nf);
 		if (c->tr.n > ROW_MASK) throw std::string("too many rows for one shard (max 2^31-1)");
 		HIPCHK(vbk::mark_first(c->tr.row_ptr, c->tr.csr, c->tr.col_ptr, c->tr.csc, c->tr.n, c->s));
 		alloc_rows(c);
@@ -775,11 +758,11 @@ int vbfm_set_test(vbfm_ctx *c, const vbfm_csc *in)
 	return guarded(c, [&] {
 		check_csc(in);
 		if (in->num_feature > c->D) throw std::string("test num_feature exceeds num_attribute");
-		upload(c, c->te, in, in->num_feature);
-		dfree(c->e_test);
-		dfree(c->pred_test);
-		c->e_test = dalloc<double>(c->te.n);
-		c->pred_test = dalloc<double>(c->te.n);
+		upload(c, c->te_buf, c->te, in, in->num_feature);
+		c->e_test.reset();
+		c->pred_test.reset();
+		c->e_test.alloc(c->te.n);
+		c->pred_test.alloc(c->te.n);
 		double v = c->te.n;
 		allreduce_host(c, &v, 1);
 		c->test_n_global = (uint32_t)v;
@@ -827,7 +810,7 @@ int vbfm_set_params(vbfm_ctx *c, const vbfm_params *p)
 		const size_t kd = (size_t)c->k * c->D;
 		if (!p->mu_w || !p->sigma_w || (kd && (!p->mu_v || !p->sigma_v)))
 			throw std::string("vbfm_set_params: parameter arrays missing");
-		DevScratch<double> tmp(2 * std::max(kd, (size_t)c->D));
+		DevBuf<double> tmp(2 * std::max(kd, (size_t)c->D));
 		HIPCHK(hipMemcpyAsync(tmp, p->mu_w, c->D * 8, hipMemcpyHostToDevice, c->s));
 		HIPCHK(hipMemcpyAsync(tmp + c->D, p->sigma_w, c->D * 8, hipMemcpyHostToDevice, c->s));
 		HIPCHK(vbk::pack_pairs(tmp, tmp + c->D, c->ms_w, 1, c->D, c->s));
@@ -852,7 +835,7 @@ int vbfm_get_params(vbfm_ctx *c, vbfm_params *p)
 	if (!c || !p) return fail(c, "null argument");
 	return guarded(c, [&] {
 		const size_t kd = (size_t)c->k * c->D;
-		DevScratch<double> tmp(2 * std::max(kd, (size_t)c->D));
+		DevBuf<double> tmp(2 * std::max(kd, (size_t)c->D));
 		HIPCHK(vbk::unpack_pairs(c->ms_w, tmp, tmp + c->D, 1, c->D, c->s));
 		if (p->mu_w) HIPCHK(d2h(c, p->mu_w, tmp, c->D * 8));
 		if (p->sigma_w) HIPCHK(d2h(c, p->sigma_w, tmp + c->D, c->D * 8));

@@ -26,9 +26,9 @@ struct vbfm_chain {
 	float min_target = 0, max_target = 0;
 	int rank = 0;                     // of the context that added last: rank 0 writes the file
 	uint32_t cap = 0, n = 0;          // draws the tables hold room for; draws added
-	double *cw = nullptr, *cv = nullptr, *cw0 = nullptr;   // [D*cap], [D*cap*k], [2*cap]: w0 then alpha
+	Stream s;                         // vbfm_model_from_chain's copies
+	DevBuf<double> cw, cv, cw0;       // [D*cap], [D*cap*k], [2*cap]: w0 then alpha
 	std::vector<double> w0, alpha;    // the draws' scalars, [n]
-	hipStream_t s = nullptr;          // vbfm_model_from_chain's copies
 };
 
 namespace {
@@ -287,8 +287,6 @@ void chain_free(vbfm_chain *ch)
 {
 	if (!ch) return;
 	(void)hipSetDevice(ch->dev);
-	dfree(ch->cw); dfree(ch->cv); dfree(ch->cw0);
-	if (ch->s) (void)hipStreamDestroy(ch->s);
 	delete ch;
 }
 
@@ -391,7 +389,7 @@ void chain_table_to_host(const vbfm_chain *ch, const double *src, uint32_t per, 
 		HIPCHK(hipMemcpy(out.data(), src, n * 8, hipMemcpyDeviceToHost));
 		return;
 	}
-	DevScratch<double> piece(std::min(n, SAVE_PIECE));
+	DevBuf<double> piece(std::min(n, SAVE_PIECE));
 	for (size_t o = 0; o < n; o += SAVE_PIECE) {
 		const size_t m = std::min(SAVE_PIECE, n - o);
 		k_chain_compact<<<(unsigned)((m + 255) / 256), 256, 0, ch->s>>>(src, piece, o, m, per, ch->n, ch->cap);
@@ -485,10 +483,10 @@ int vbfm_chain_create(vbfm_chain **out, vbfm_ctx *c, uint32_t capacity)
 			ch->rank = c->net.rank;
 			ch->cap = capacity;
 			const size_t nw = (size_t)c->D * capacity;
-			ch->cw = dalloc<double>(nw);
-			ch->cv = dalloc<double>(nw * (size_t)c->k);
-			ch->cw0 = dalloc<double>(2 * (size_t)capacity);
-			HIPCHK(hipStreamCreateWithFlags(&ch->s, hipStreamNonBlocking));
+			ch->cw.alloc(nw);
+			ch->cv.alloc(nw * (size_t)c->k);
+			ch->cw0.alloc(2 * (size_t)capacity);
+			ch->s.create();
 		} catch (...) {
 			chain_free(ch);
 			throw;

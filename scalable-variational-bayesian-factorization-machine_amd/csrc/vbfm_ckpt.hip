@@ -67,7 +67,7 @@ constexpr size_t IO_CHUNK = (size_t)64 << 20;
 
 uint64_t train_fingerprint(vbfm_ctx *c)
 {
-	DevScratch<unsigned long long> d(1);
+	DevBuf<unsigned long long> d(1);
 	HIPCHK(hipMemsetAsync(d, 0, 8, c->s));
 	HIPCHK(vbk::fingerprint(c->tr.col_ptr, (uint64_t)c->tr.nf + 1, 8, 1, d, c->s));
 	HIPCHK(vbk::fingerprint(c->tr.csc, c->tr.nnz, 8, 2, d, c->s));

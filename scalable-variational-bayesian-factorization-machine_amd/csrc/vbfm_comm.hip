@@ -27,7 +27,7 @@ static std::string x_where(vbfm_ctx *c)
 static void stall_release(vbfm_ctx *c, double grace_s)
 {
 	if (!c->net.stall_flag) return;
-	__atomic_store_n(c->net.stall_flag, 1u, __ATOMIC_SEQ_CST);
+	__atomic_store_n(c->net.stall_flag.p, 1u, __ATOMIC_SEQ_CST);
 	const double end = wall_s() + grace_s;
 	while (hipStreamQuery(c->s) == hipErrorNotReady && wall_s() < end) usleep(1000);
 }
@@ -158,7 +158,7 @@ static void comm_fault_hooks(vbfm_ctx *c)
 	}
 	if (fault_at("comm_stall") && c->net.comm && !c->net.stall_done) {
 		c->net.stall_done = true;
-		if (!c->net.stall_flag) HIPCHK(hipHostMalloc((void **)&c->net.stall_flag, 4, hipHostMallocCoherent | hipHostMallocMapped));
+		if (!c->net.stall_flag) c->net.stall_flag.alloc(1, hipHostMallocCoherent | hipHostMallocMapped);
 		*c->net.stall_flag = 0;
 		uint32_t *dflag = nullptr;
 		HIPCHK(hipHostGetDevicePointer((void **)&dflag, c->net.stall_flag, 0));
@@ -224,9 +224,9 @@ void allreduce_chunk(vbfm_ctx *c, double2 *buf, size_t n, uint32_t i)
 		return;
 	}
 	if (!c->net.s_comm) {
-		HIPCHK(hipStreamCreateWithFlags(&c->net.s_comm, hipStreamNonBlocking));
-		for (auto &e : c->net.ev_ar) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-		HIPCHK(hipEventCreateWithFlags(&c->net.ev_arj, hipEventDisableTiming));
+		c->net.s_comm.create();
+		for (Event &e : c->net.ev_ar) e.create(hipEventDisableTiming);
+		c->net.ev_arj.create(hipEventDisableTiming);
 	}
 	HIPCHK(hipEventRecord(c->net.ev_ar[i], c->s));
 	HIPCHK(hipStreamWaitEvent(c->net.s_comm, c->net.ev_ar[i], 0));
@@ -254,18 +254,6 @@ void allreduce_host(vbfm_ctx *c, double *v, int n)
 	allreduce_dev(c, c->red_d, n, ncclDouble, ncclSum);
 	HIPCHK(d2h(c, v, c->red_d, n * sizeof(double)));
 	sync(c);
-}
-
-void comm_free(vbfm_ctx *c)
-{
-	vbfm_ctx::Net &x = c->net;
-	if (x.comm) ncclCommDestroy(x.comm);
-	if (x.stall_flag) (void)hipHostFree(x.stall_flag);
-	for (hipEvent_t e : x.ev_ar)
-		if (e) (void)hipEventDestroy(e);
-	if (x.ev_arj) (void)hipEventDestroy(x.ev_arj);
-	if (x.s_comm) (void)hipStreamDestroy(x.s_comm);
-	x = {};
 }
 
 }  // namespace vbi

@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -60,50 +61,103 @@ struct HipError {
 		if (_e != hipSuccess) throw HipError{_e, #x};               \
 	} while (0)
 
-template <class T> inline T *dalloc(size_t n)
-{
-	void *p = nullptr;
-	HIPCHK(hipMalloc(&p, (n ? n : 1) * sizeof(T)));
-	return (T *)p;
-}
+// The owners. A device pointer is either an owner or a view: an owner is a DevBuf, the only code
+// that allocates or frees device memory; a view is a raw pointer that never frees, and the comment
+// on its declaration names its owner. Every owner is move-only, empty by default, released when its
+// scope or its group ends (normally or by an exception), and passes for what it owns. Assigning a
+// fresh group (st = {st.layout_req}) releases a group's members in the order they are declared.
+// Where several buffers of a scope end together they are reset() by hand, oldest first: the order
+// of frees decides where the driver places what is allocated next.
 
-template <class T> inline void dfree(T *&p)
-{
-	if (p) (void)hipFree((void *)p);
-	p = nullptr;
-}
-
-// an owning device buffer: freed when its scope (or its owner) ends, normally or by an exception;
-// it passes for its pointer. reserve(n) reallocates only when n exceeds the capacity and alloc(n)
-// always; neither keeps the contents. dfree(buf.p) frees it early, std::exchange(buf.p, nullptr)
-// hands the memory to another owner, and an empty one adopts whatever is put into p (cap stays 0)
+// a device buffer. alloc(n) always reallocates, reserve(n) only when n exceeds the capacity;
+// neither keeps the contents. try_alloc is for callers that tolerate a refusal (the placement search)
 template <class T> struct DevBuf {
 	T *p = nullptr;
 	size_t cap = 0;   // elements asked for by the last alloc / reserve
 	DevBuf() = default;
 	explicit DevBuf(size_t n) { alloc(n); }
-	~DevBuf() { dfree(p); }
-	DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-	DevBuf &operator=(DevBuf &&o) noexcept
+	~DevBuf() { reset(); }
+	DevBuf(DevBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+	DevBuf &operator=(DevBuf &&o) noexcept   // frees its own first: a group assigned anew releases in member order
 	{
-		std::swap(p, o.p);
-		std::swap(cap, o.cap);
+		reset();
+		p = std::exchange(o.p, nullptr);
+		cap = std::exchange(o.cap, 0);
 		return *this;
 	}
 	operator T *() const { return p; }
-	void alloc(size_t n)
+	void reset() { if (p) (void)hipFree((void *)p); p = nullptr; cap = 0; }
+	T *alloc(size_t n)
 	{
-		dfree(p);
-		cap = 0;
-		p = dalloc<T>(n);
+		reset();
+		HIPCHK(hipMalloc((void **)&p, (n ? n : 1) * sizeof(T)));
 		cap = n;
+		return p;
 	}
-	void reserve(size_t n)
+	bool try_alloc(size_t n)
 	{
-		if (n > cap) alloc(n);
+		reset();
+		if (hipMalloc((void **)&p, (n ? n : 1) * sizeof(T)) != hipSuccess) {
+			(void)hipGetLastError();
+			p = nullptr;
+			return false;
+		}
+		cap = n;
+		return true;
+	}
+	void reserve(size_t n) { if (n > cap) alloc(n); }
+};
+
+// pinned host memory
+template <class T> struct HostBuf {
+	T *p = nullptr;
+	HostBuf() = default;
+	~HostBuf() { reset(); }
+	HostBuf(HostBuf &&o) noexcept : p(std::exchange(o.p, nullptr)) {}
+	HostBuf &operator=(HostBuf &&o) noexcept { std::swap(p, o.p); return *this; }   // (the old memory goes with o)
+	operator T *() const { return p; }
+	void reset() { if (p) (void)hipHostFree((void *)p); p = nullptr; }
+	void alloc(size_t n, unsigned flags = hipHostMallocDefault)
+	{
+		reset();
+		HIPCHK(hipHostMalloc((void **)&p, (n ? n : 1) * sizeof(T), flags));
 	}
 };
-template <class T> using DevScratch = DevBuf<T>;   // the name its scoped uses keep
+
+struct Event {
+	hipEvent_t e = nullptr;
+	Event() = default;
+	~Event() { if (e) (void)hipEventDestroy(e); }
+	Event(Event &&o) noexcept : e(std::exchange(o.e, nullptr)) {}
+	Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }   // (the old event goes with o)
+	operator hipEvent_t() const { return e; }
+	// (a live handle is destroyed first, as alloc resets)
+	void create(unsigned flags = hipEventDefault) { *this = Event(); HIPCHK(hipEventCreateWithFlags(&e, flags)); }
+};
+
+struct Stream {
+	hipStream_t s = nullptr;
+	Stream() = default;
+	~Stream() { if (s) (void)hipStreamDestroy(s); }
+	Stream(Stream &&o) noexcept : s(std::exchange(o.s, nullptr)) {}
+	Stream &operator=(Stream &&o) noexcept { std::swap(s, o.s); return *this; }   // (the old stream goes with o)
+	operator hipStream_t() const { return s; }
+	void create() { *this = Stream(); HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+};
+
+// the five arrays of an uploaded or generated data set; the DevData beside it (c->tr, c->te) is
+// the view every launch reads
+struct DataBuf {
+	DevBuf<uint64_t> col_ptr;
+	DevBuf<uint2> csc;
+	DevBuf<uint64_t> row_ptr;
+	DevBuf<uint2> csr;
+	DevBuf<float> target;
+};
+
+static_assert(std::is_trivially_copyable<DevData>::value, "DevData is a view: launches take it by value");
+static_assert(!std::is_copy_constructible<DevBuf<char>>::value && !std::is_copy_constructible<DataBuf>::value,
+              "owners do not copy");
 
 enum { EV_BEGIN, EV_W0, EV_W, EV_V, EV_HYPER, EV_TEST, EV_TP0, EV_TP1, EV_N };
 
@@ -127,7 +181,8 @@ inline int defer_nt_bits()
 
 // test hook: VBFM_FAULT=<where> makes the named step throw as a failed HIP call would (the error
 // paths of the store build and the per-level steps, tests/test_placement_gpu.py; online_init: a
-// vbfm_online_init that fails with its state half built, tests/test_lifecycle_gpu.py)
+// vbfm_online_init that fails with its state half built, replay: the first attempt of
+// vbfm_init_params_replay with all its buffers allocated, tests/test_lifecycle_gpu.py)
 inline bool fault_at(const char *where)
 {
 	const char *e = getenv("VBFM_FAULT");
@@ -154,20 +209,38 @@ struct vbfm_ctx {
 	using DevData = vbi::DevData;
 	std::string err;
 	int dev = 0;
-	hipStream_t s = nullptr;
-	hipStream_t s_test = nullptr;   // the test prediction, overlapping the hyper-parameter step
+	// members are released last to first, so these two streams and ev[] outlive every buffer below
+	// (the exchange's stream and events in net, and prof's events, go in their place among them)
+	vbi::Stream s;
+	vbi::Stream s_test;   // the test prediction, overlapping the hyper-parameter step
+	vbi::Event ev[vbi::EV_N];
 	int k0 = 1, k1 = 1, k = 0;
 	uint32_t D = 0, G = 1;
 	std::vector<uint32_t> group_h, per_group;
-	uint32_t *group_d = nullptr;
+	vbi::DevBuf<uint32_t> group_d;
 	float min_target = 0, max_target = 0;
 	int task = VBFM_TASK_REGRESSION;   // VBFM_TASK_*: classification runs on the MCMC / ALS learner only
-	DevData tr, te;
+	DevData tr, te;                // views of tr_buf / te_buf (the online learner points tr at a mini-batch)
+	vbi::DataBuf tr_buf, te_buf;
+	// the records: rows (and store.rows_alt) are views of rec[] that trade places at every level; the
+	// online learner points rows at its batch buffers and puts it back
 	RowRec *rows = nullptr;
-	double *scratch_n = nullptr;   // yhat of train at init
-	double *e_test = nullptr, *pred_test = nullptr;
-	double2 *ms_v = nullptr, *ms_w = nullptr;
-	double *hyp_w_d = nullptr, *hyp_v_d = nullptr;
+	vbi::DevBuf<RowRec> rec[2];
+	RowRec *rec_alloc(size_t n)    // a record buffer in the owner that is free
+	{
+		if (rec[0] && rec[1]) throw std::string("internal: a third record buffer");
+		return rec[rec[0] ? 1 : 0].alloc(n);
+	}
+	void rec_release(RowRec *&view)   // (a view of someone else's buffer is only cleared)
+	{
+		for (auto &b : rec)
+			if (b.p == view) b.reset();
+		view = nullptr;
+	}
+	vbi::DevBuf<double> scratch_n;   // yhat of train at init
+	vbi::DevBuf<double> e_test, pred_test;
+	vbi::DevBuf<double2> ms_v, ms_w;
+	vbi::DevBuf<double> hyp_w_d, hyp_v_d;
 	std::vector<double> hyp_w, hyp_v;
 	double alpha = 1.0, sigma_0 = 1.0, mu0 = 0.0, s0d = 0.02;
 	// schedule
@@ -192,36 +265,36 @@ struct vbfm_ctx {
 	int prefetch = -1;              // the level kernels touch the next level's column bounds (VBFM_PREFETCH; -1: not read yet)
 	// host wall seconds of the set-up steps (vbfm_setup_info)
 	double t_set_train = 0, t_schedule = 0, t_store = 0, t_place = 0;
-	uint32_t *level_feats = nullptr;
-	uint8_t *dup = nullptr;
+	vbi::DevBuf<uint32_t> level_feats;
+	vbi::DevBuf<uint8_t> dup;
 	bool sched_ready = false;
 	int sched_rounds = 0;          // relaxation rounds (+ Kahn rounds queued) of the last schedule
 	bool sched_kahn = false;       // the last schedule came from Kahn's order
 	// reductions
 	static constexpr uint32_t RED_BLOCKS = 512;
-	double *red_d = nullptr;
+	vbi::DevBuf<double> red_d;
 	std::vector<double> red_h;
-	uint32_t *perm_d = nullptr;
-	vbk::Chunk *chunks_d = nullptr;
+	vbi::DevBuf<uint32_t> perm_d;
+	vbi::DevBuf<vbk::Chunk> chunks_d;
 	std::vector<vbk::Chunk> chunks_h;   // attribute chunks, group by group (build_chunks)
-	uint32_t *gchunk_d = nullptr;       // [G+1] each group's chunk range
-	double *chunk_out_d = nullptr;      // [chunks] w partials
-	double *vpart_d = nullptr;          // [chunks * k] factor partials
-	double *vseg_d = nullptr;           // [k * G] factor sums (inside chunk_out_d)
-	uint32_t *counters = nullptr;
+	vbi::DevBuf<uint32_t> gchunk_d;     // [G+1] each group's chunk range
+	vbi::DevBuf<double> chunk_out_d;    // [chunks] w partials
+	vbi::DevBuf<double> vpart_d;        // [chunks * k] factor partials
+	double *vseg_d = nullptr;           // [k * G] factor sums (a view into chunk_out_d)
+	vbi::DevBuf<uint32_t> counters;
 	bool force_split = false;      // VBFM_FORCE_SPLIT=1: the multi-rank kernels on one rank
 	int debug_skew = 0;            // VBFM_DEBUG_SKEW=1: late waves in the split forms' posterior kernels
 	static constexpr int AR_MAX_CHUNKS = 8;
-	// the exchange between ranks (vbfm_comm.hip; released by comm_free)
+	// the exchange between ranks (vbfm_comm.hip)
 	struct Net {
 		// row-sharded multi-GPU
 		int nranks = 1, rank = 0;
 		ncclComm_t comm = nullptr;
 		// row shards over RCCL: the per-level all-reduce of chunk i of a level's statistics runs on
 		// s_comm while chunk i+1 computes on s (stats_exchange); events order the two
-		hipStream_t s_comm = nullptr;
-		hipEvent_t ev_ar[AR_MAX_CHUNKS] = {};
-		hipEvent_t ev_arj = nullptr;
+		vbi::Stream s_comm;
+		vbi::Event ev_ar[AR_MAX_CHUNKS];
+		vbi::Event ev_arj;
 		// communicator health: RCCL runs non-blocking (its errors surface through
 		// ncclCommGetAsyncError), polled against a deadline wherever the host waits on work that holds a
 		// collective (comm_wait); a failure or a missed deadline aborts the communicator, and every
@@ -235,70 +308,69 @@ struct vbfm_ctx {
 		int x_f = -1, x_l = -1;
 		std::string x_pending;           // the first exchange issued since the last completed wait (x_where)
 		vbfm_exchange_stats xs = {};     // this iteration's exchanges (vbfm_exchange_info)
-		uint32_t *stall_flag = nullptr;  // VBFM_FAULT=comm_stall: host flag that releases the stall kernel
+		vbi::HostBuf<uint32_t> stall_flag;  // VBFM_FAULT=comm_stall: host flag that releases the stall kernel
 		bool stall_done = false;
 		vbfm_exchange_fn xfn = nullptr; // vbfm_comm_init_host: all-reduces through the caller
 		void *xuser = nullptr;
 		std::vector<uint8_t> xbuf;      // host staging of a host-exchange all-reduce
 	} net;
-	double2 *stats = nullptr;
-	uint32_t stats_cap = 0;
+	vbi::DevBuf<double2> stats;      // [stats.cap >= the widest level] split sweeps
 	uint64_t n_global = 0;
 	uint32_t test_n_global = 0;
-	hipEvent_t ev[vbi::EV_N] = {};
-	// per-launch profiling (vbfm_set_profiling; released by prof_free)
+	// per-launch profiling (vbfm_set_profiling)
 	struct Prof {
 		bool on = false;
 		int stride = 1;                  // event pair around every stride-th launch of a kind
 		uint64_t tick[4] = {0, 0, 0, 0};
-		std::vector<hipEvent_t> pev;
+		std::vector<vbi::Event> pev;
 		size_t pev_used = 0;
 		struct Span { size_t a; int kind; };   // kind 0 = v level, 1 = w level, 2 = qcache, 3 = exchange
 		std::vector<Span> spans;
 	} prof;
-	// level-ordered row store (vbfm_store.hip, kernels in vbfm_lorder.hip; released by store_release)
+	// level-ordered row store (vbfm_store.hip, kernels in vbfm_lorder.hip; store_release
+	// starts it over, its owners in this order)
 	struct Store {
 		int layout_req = VBFM_LAYOUT_AUTO;   // a request, not a build product: kept across a release
 		bool lord = false;             // built for the current train set and in use
 		bool estore = false;           // ... as the entry store (levels that miss rows: build_estore);
 		                               // lpos0 then holds each row's slot between sweeps, lrow0 is unused
 		bool rows_lorder = false;      // rows currently hold level-0 order (else row order)
-		RowRec *rows_alt = nullptr;    // second record buffer (each level moves rows -> rows_alt)
-		uint64_t *lcp = nullptr;       // [nf+1] global position of each level feature's run
-		float *lx = nullptr;           // [nnz] x per level-ordered entry
-		uint32_t *lnext = nullptr;     // [nnz] position of the entry's row in the next level
-		uint32_t *lrow0 = nullptr;     // [n] row at each level-0 position
-		uint32_t *lpos0 = nullptr;     // [n] level-0 position of each row
-		uint32_t *lpidx = nullptr;     // [nnz] split form: the row's previous-level feature (index in its level)
-		float *lpx = nullptr;          // [nnz] ... and its x (deferred correction)
-		uint2 *lpay2 = nullptr;        // [nnz] ... {lnext, lpidx} instead when every x is 1 (no lx)
-		uint4 *lpay = nullptr;         // [nnz] deferred split: {x, lnext, lpidx, lpx} of every entry in one
+		RowRec *rows_alt = nullptr;    // second record buffer (each level moves rows -> rows_alt): a view of c->rec[]
+		vbi::DevBuf<uint64_t> lcp;     // [nf+1] global position of each level feature's run
+		vbi::DevBuf<float> lx;         // [nnz] x per level-ordered entry
+		vbi::DevBuf<uint32_t> lnext;   // [nnz] position of the entry's row in the next level
+		vbi::DevBuf<uint32_t> lrow0;   // [n] row at each level-0 position
+		vbi::DevBuf<uint32_t> lpos0;   // [n] level-0 position of each row
+		vbi::DevBuf<uint32_t> lpidx;   // [nnz] split form: the row's previous-level feature (index in its level)
+		vbi::DevBuf<float> lpx;        // [nnz] ... and its x (deferred correction)
+		vbi::DevBuf<PostT> post_tab;   // [max level width] posteriors of the last level swept
+		vbi::DevBuf<uint4> lpay;       // [nnz] deferred split: {x, lnext, lpidx, lpx} of every entry in one
 		                               // 16-B load (lx / lnext / lpidx / lpx are freed once packed)
-		PostT *post_tab = nullptr;     // [max level width] posteriors of the last level swept
+		vbi::DevBuf<uint2> lpay2;      // [nnz] ... {lnext, lpidx} instead when every x is 1 (no lx)
 		// long columns of the level store (fused single-rank sweep): segments of every level
 		uint32_t long_min = 0;         // nonzero: some level has long columns split into segments
 		std::vector<uint32_t> long_min_l;  // [L] each level's threshold (0: no segments in the level)
 		std::vector<uint32_t> seg_ptr; // [L+1] each level's segments in long_segs
-		LongSeg *long_segs = nullptr;
-		double2 *seg_part = nullptr;   // [2 * max segments of a level]
+		vbi::DevBuf<LongSeg> long_segs;
+		vbi::DevBuf<double2> seg_part;   // [2 * max segments of a level]
 	} store;
 	// deferred split across sweeps (vbfm_iterate only): the last level's correction of a sweep is
 	// left to level 0 of the next one instead of a flush pass. carry: 0 none, 1 / 2 = v sweep of
 	// q-cache slot 0 / 1, 3 = w sweep
 	int carry_ok = 0, carry = 0;
 	// feature-sharded mode (vbfm_set_shard_mode): shards own column chunks of every level
-	// (vbfm_schedule.hip; released by fs_free)
+	// (vbfm_schedule.hip; fs_free starts it over)
 	struct FeatShards {
 		int mode = VBFM_SHARD_ROWS;
 		int req = 1;                   // shards requested (no communicator: run one after another here)
 		int n = 1;                     // shards in use
 		std::vector<uint32_t> lo;      // [L * (n + 1)] chunk bounds of each level in level_feats
-		uint32_t *own = nullptr;       // this rank's features (all levels) for the parameter exchange
+		vbi::DevBuf<uint32_t> own;     // this rank's features (all levels) for the parameter exchange
 		uint32_t own_n = 0;
-		double *base = nullptr;        // [2n] e, t at the start of a pass
-		double *buf = nullptr;         // [5n] summed changes / partial q-caches
-		double2 *pbuf = nullptr;       // [nf] parameter exchange
-		RowRec *rows0 = nullptr;       // in-process shards: the rows at the start of a pass
+		vbi::DevBuf<double> base;      // [2n] e, t at the start of a pass
+		vbi::DevBuf<double> buf;       // [5n] summed changes / partial q-caches
+		vbi::DevBuf<double2> pbuf;     // [nf] parameter exchange
+		vbi::DevBuf<RowRec> rows0;     // in-process shards: the rows at the start of a pass
 	} fs;
 	bool deferred() const { return store.lpay || store.lpay2; }
 	bool multi() const { return net.comm || net.xfn || net.failed; }
@@ -310,7 +382,11 @@ struct vbfm_ctx {
 	// warm-up), so that a learner can continue the reference's stream (UINT64_MAX: unknown)
 	uint32_t init_stream_seed = 0;
 	uint64_t init_stream_end = ~0ull;
+	~vbfm_ctx();   // vbfm_capi.hip: the learner states, the communicator, then the members
 };
+static_assert(!std::is_copy_constructible<vbfm_ctx::Store>::value && !std::is_copy_constructible<vbfm_ctx::FeatShards>::value &&
+                  !std::is_copy_constructible<vbfm_ctx::Net>::value,
+              "the owner groups do not copy");
 
 namespace vbi {
 
@@ -364,7 +440,6 @@ uint32_t ar_chunks(vbfm_ctx *c, uint32_t nfeat);
 void allreduce_chunk(vbfm_ctx *c, double2 *buf, size_t n, uint32_t i);
 // c->s waits for every chunk's all-reduce issued since the last join
 void allreduce_join(vbfm_ctx *c);
-void comm_free(vbfm_ctx *c);   // the communicator, its stream and events, the stall flag
 
 // chunk [c0, c1) of a level's features as a launch of its own (LevelArgs / McArgs): the
 // kernels index their columns, runs and statistics by the launch's feature index
@@ -431,7 +506,7 @@ template <class A> void store_args(vbfm_ctx *c, A &a, uint32_t l)
 }
 
 // ---- vbfm_capi.hip: the context's life and the VB sweep driver --------------------------------
-void free_data(DevData &d);
+void free_data(DataBuf &b, DevData &d);           // reset the owner, clear the view
 void alloc_rows(vbfm_ctx *c);                     // the records of a new train set
 uint32_t global_nf(vbfm_ctx *c, uint32_t nf);     // the train feature count every shard pads to
 double finish_sum(vbfm_ctx *c, uint32_t nblocks);
@@ -442,7 +517,6 @@ uint32_t nlevels(vbfm_ctx *c);
 constexpr size_t NO_SPAN = ~(size_t)0;   // prof_begin: this launch is not timed
 size_t prof_begin(vbfm_ctx *c, int kind, hipStream_t st = nullptr);
 void prof_end(vbfm_ctx *c, size_t a, hipStream_t st = nullptr);
-void prof_free(vbfm_ctx *c);
 int blocked_predict(const vbfm_ctx *c, const DevData &d);
 float ev_ms(vbfm_ctx *c, int a, int b);
 // steps of update_all shared with the online learner

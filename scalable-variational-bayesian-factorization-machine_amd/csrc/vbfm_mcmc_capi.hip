@@ -60,12 +60,7 @@ struct McState {
 	DevBuf<double> s_d;                                   // grows with the train set (class_train_step)
 	std::vector<double> s_h;
 	uint32_t hc[HC_N] = {};
-	hipEvent_t ev[MEV_N] = {};
-	~McState()
-	{
-		for (hipEvent_t e : ev)
-			if (e) (void)hipEventDestroy(e);
-	}
+	Event ev[MEV_N];
 };
 
 namespace vbi {
@@ -456,7 +451,7 @@ void scan_columns(vbfm_ctx *c)
 	m.col_nonempty.assign(nf, 0);
 	for (uint32_t j = 0; j < nf; j++) m.col_nonempty[j] = cp[j + 1] > cp[j];
 	if (c->multi() && nf) {
-		DevScratch<uint8_t> d(nf);
+		DevBuf<uint8_t> d(nf);
 		HIPCHK(hipMemcpyAsync(d, m.col_nonempty.data(), nf, hipMemcpyHostToDevice, c->s));
 		allreduce_dev(c, d, nf, ncclUint8, ncclMax);
 		HIPCHK(d2h(c, m.col_nonempty.data(), d, nf));
@@ -474,7 +469,7 @@ void class_row_offset(vbfm_ctx *c)
 	const int R = c->net.nranks, me = c->net.rank;
 	std::vector<uint32_t> cnt((size_t)R, 0u);
 	cnt[me] = c->tr.n;
-	DevScratch<uint32_t> d((size_t)R);
+	DevBuf<uint32_t> d((size_t)R);
 	HIPCHK(hipMemcpyAsync(d, cnt.data(), (size_t)R * 4, hipMemcpyHostToDevice, c->s));
 	allreduce_dev(c, d, (size_t)R, ncclUint32, ncclSum);
 	HIPCHK(d2h(c, cnt.data(), d, (size_t)R * 4));
@@ -536,7 +531,7 @@ int vbfm_mcmc_init(vbfm_ctx *c, const vbfm_mcmc_config *cfg)
 		mc_free(c);
 		c->mc = new McState();
 		McState &m = *c->mc;
-		for (int i = 0; i < MEV_N; i++) HIPCHK(hipEventCreate(&m.ev[i]));
+		for (Event &e : m.ev) e.create();
 		m.sample = cfg->do_sample != 0;
 		m.multilevel = cfg->do_multilevel != 0;
 		m.rng = cfg->rng;
@@ -560,7 +555,7 @@ int vbfm_mcmc_init(vbfm_ctx *c, const vbfm_mcmc_config *cfg)
 			std::vector<double> v(kd), w(c->D), zero(std::max(kd, (size_t)c->D), 0.0);
 			for (double &x : v) x = m.stream.gaussian(0.0, cfg->init_stdev);
 			for (double &x : w) x = m.stream.gaussian(0.0, cfg->init_stdev);
-			DevScratch<double> tmp(2 * std::max(kd, (size_t)c->D));
+			DevBuf<double> tmp(2 * std::max(kd, (size_t)c->D));
 			const size_t half = std::max(kd, (size_t)c->D);
 			HIPCHK(hipMemcpyAsync(tmp + half, zero.data(), half * 8, hipMemcpyHostToDevice, c->s));
 			if (kd) {
@@ -589,7 +584,7 @@ int vbfm_mcmc_set_params(vbfm_ctx *c, const vbfm_mcmc_params *p)
 		McState &m = mc(c);
 		const size_t kd = (size_t)c->k * c->D, half = std::max(kd, (size_t)c->D);
 		if (!p->w || (kd && !p->v)) throw std::string("vbfm_mcmc_set_params: parameter arrays missing");
-		DevScratch<double> tmp(2 * half);
+		DevBuf<double> tmp(2 * half);
 		HIPCHK(hipMemsetAsync(tmp + half, 0, half * 8, c->s));
 		HIPCHK(hipMemcpyAsync(tmp, p->w, (size_t)c->D * 8, hipMemcpyHostToDevice, c->s));
 		HIPCHK(vbk::pack_pairs(tmp, tmp + half, c->ms_w, 1, c->D, c->s));
@@ -617,7 +612,7 @@ int vbfm_mcmc_get_params(vbfm_ctx *c, vbfm_mcmc_params *p)
 	return guarded(c, [&] {
 		McState &m = mc(c);
 		const size_t kd = (size_t)c->k * c->D, half = std::max(kd, (size_t)c->D);
-		DevScratch<double> tmp(2 * half);
+		DevBuf<double> tmp(2 * half);
 		HIPCHK(vbk::unpack_pairs(c->ms_w, tmp, tmp + half, 1, c->D, c->s));
 		if (p->w) HIPCHK(d2h(c, p->w, tmp, (size_t)c->D * 8));
 		sync(c);

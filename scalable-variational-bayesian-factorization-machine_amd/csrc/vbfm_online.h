@@ -39,10 +39,6 @@ struct OvState {
 	~OvState()
 	{
 		pre_join();
-		for (hipEvent_t e : ev)
-			if (e) (void)hipEventDestroy(e);
-		for (hipEvent_t e : bev)
-			if (e) (void)hipEventDestroy(e);
 	}
 	DevBuf<double2> nat_w, nat_v;   // natural_{mu,sigma}_{w,v}_dash; nat_v factor-major [f][j] (the
 	                                // reference's layout): a level's columns are consecutive ids, so
@@ -69,8 +65,8 @@ struct OvState {
 	DevBuf<uint2> csr_b;
 	DevBuf<float> t_b;
 	DevBuf<RowRec> rows_b;
-	hipEvent_t ev[4] = {};
-	std::vector<hipEvent_t> bev;   // [num_batch * 6] phase marks of every batch
+	vbi::Event ev[4];
+	std::vector<vbi::Event> bev;   // [num_batch * 6] phase marks of every batch
 	uint32_t launches_v = 0;
 	// the per-batch level-ordered store (k_ov_lord)
 	DevBuf<uint32_t> level_ptr_d;      // [L+1] level bounds in level positions

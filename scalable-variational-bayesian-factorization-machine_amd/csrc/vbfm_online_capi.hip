@@ -102,10 +102,10 @@ static void ov_lord_launch(vbfm_ctx *c, LevelArgs &a, bool is_w)
 {
 	static long launch_no = 0;
 	static const long want = [] { const char *e = getenv("VBFM_OV_STAMP"); return e ? atol(e) : -1L; }();
-	unsigned long long *st = nullptr;
+	DevBuf<unsigned long long> st;
 	const unsigned nwg = (a.nfeat + 31) / 32 + 4096;
 	if (!is_w && want >= 0 && launch_no >= want && (launch_no - want) % 1000 == 0) {
-		HIPCHK(hipMalloc(&st, (size_t)nwg * 5 * 8 * 8));
+		st.alloc((size_t)nwg * 5 * 8);
 		HIPCHK(hipMemsetAsync(st, 0, (size_t)nwg * 5 * 8 * 8, c->s));
 	}
 	a.stamp = st;
@@ -115,7 +115,7 @@ static void ov_lord_launch(vbfm_ctx *c, LevelArgs &a, bool is_w)
 		std::vector<unsigned long long> h((size_t)nwg * 5 * 8);
 		HIPCHK(d2h(c, h.data(), st, h.size() * 8));
 		sync(c);
-		(void)hipFree(st);
+		st.reset();
 		fprintf(stderr, "OVSTAMP launch %ld nfeat %u avg %u\n", launch_no - 1, a.nfeat, a.avg_len);
 		for (size_t w = 0; w * 5 < h.size() && h[w * 5] != 0; w++)
 			fprintf(stderr, "OVSTAMP %zu %llu %llu %llu %llu %llu\n", w, h[w * 5], h[w * 5 + 1], h[w * 5 + 2],
@@ -343,7 +343,7 @@ bool ov_init_store(vbfm_ctx *c, const OvEnv &env)
 	o.level_ptr_d.alloc((size_t)L + 1);
 	HIPCHK(hipMemcpy(o.level_ptr_d, c->level_ptr.data(), ((size_t)L + 1) * 4, hipMemcpyHostToDevice));
 	o.lvl_d.alloc((size_t)o.num_batch * (L + 1));
-	DevScratch<uint32_t> cnt(1);
+	DevBuf<uint32_t> cnt(1);
 	uint32_t ne1 = 1;
 	HIPCHK(vbk::count_x_ne1(c->tr.csc, c->tr.nnz, cnt, c->s));
 	HIPCHK(d2h(c, &ne1, cnt, 4));
@@ -436,7 +436,7 @@ void ov_batch(vbfm_ctx *c, uint32_t b, uint64_t nnz, vbfm_online_stats &st)
 {
 	OvState &o = *c->ov;
 	Range r_b("batch");
-	hipEvent_t *bev = &o.bev[(size_t)b * 6];
+	Event *bev = &o.bev[(size_t)b * 6];
 	HIPCHK(hipEventRecord(bev[0], c->s));
 	const uint32_t n = (uint32_t)(o.rstart[b + 1] - o.rstart[b]);
 	OvBatchView view(c, ov_batch_gather(c, b, n, nnz));
@@ -524,9 +524,9 @@ int vbfm_online_init(vbfm_ctx *c, const vbfm_online_config *cfg)
 			lord_release(c, false);
 			c->sched_ready = false;
 			require_train(c);
-			for (hipEvent_t &e : o.ev) HIPCHK(hipEventCreate(&e));
+			for (Event &e : o.ev) e.create();
 			o.bev.resize((size_t)cfg->num_batch * 6);
-			for (hipEvent_t &e : o.bev) HIPCHK(hipEventCreate(&e));
+			for (Event &e : o.bev) e.create();
 			o.num_batch = cfg->num_batch;
 			o.n_total = c->tr.n;
 			o.size = size;
@@ -590,7 +590,7 @@ int vbfm_online_get_state(vbfm_ctx *c, double *nat_mu_w, double *nat_sigma_w, do
 		if (!c->ov) throw std::string("not an online VB context (vbfm_online_init)");
 		OvState &o = *c->ov;
 		const size_t kd = (size_t)c->k * c->D;
-		DevScratch<double> tmp(2 * std::max(kd, (size_t)c->D));
+		DevBuf<double> tmp(2 * std::max(kd, (size_t)c->D));
 		HIPCHK(vbk::unpack_pairs(o.nat_w, tmp, tmp + c->D, 1, c->D, c->s));
 		sync(c);
 		if (nat_mu_w) HIPCHK(hipMemcpy(nat_mu_w, tmp, (size_t)c->D * 8, hipMemcpyDeviceToHost));
@@ -601,7 +601,7 @@ int vbfm_online_get_state(vbfm_ctx *c, double *nat_mu_w, double *nat_sigma_w, do
 			if (nat_mu_v) HIPCHK(hipMemcpy(nat_mu_v, tmp, kd * 8, hipMemcpyDeviceToHost));
 			if (nat_sigma_v) HIPCHK(hipMemcpy(nat_sigma_v, tmp + kd, kd * 8, hipMemcpyDeviceToHost));
 		}
-		dfree(tmp.p);
+		tmp.reset();
 		if (new_wj) HIPCHK(hipMemcpy(new_wj, o.new_wj, (size_t)c->D * 8, hipMemcpyDeviceToHost));
 		if (new_vj) HIPCHK(hipMemcpy(new_vj, o.new_vj, (size_t)c->D * 8, hipMemcpyDeviceToHost));
 		if (scalars) {

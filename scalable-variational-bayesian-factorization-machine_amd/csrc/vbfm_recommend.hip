@@ -643,17 +643,11 @@ void check_exclusions(const std::string &who, uint32_t B, uint32_t M, const uint
 
 // event pairs around the phases of the chunk in a slot
 struct PhaseEvents {
-	hipEvent_t ev[2][4] = {};
+	Event ev[2][4];
 	PhaseEvents()
 	{
 		for (auto &s : ev)
-			for (hipEvent_t &e : s) HIPCHK(hipEventCreate(&e));
-	}
-	~PhaseEvents()
-	{
-		for (auto &s : ev)
-			for (hipEvent_t &e : s)
-				if (e) (void)hipEventDestroy(e);
+			for (Event &e : s) e.create();
 	}
 };
 
@@ -664,12 +658,12 @@ struct vbfm_candidates {
 	int dev = 0;
 	uint32_t M = 0, Mpad = 0;
 	int k = 0;
-	double *qt = nullptr;         // [k][Mpad], zero beyond M
-	double *base = nullptr;       // [Mpad]
+	DevBuf<double> qt;            // [k][Mpad], zero beyond M
+	DevBuf<double> base;          // [Mpad]
 	// vbfm_candidates_create_var only: Z and U = Z + P, the planes behind qt in its allocation
 	// ([3][k][Mpad]), and the rows' T_n
-	double *zt = nullptr, *ut = nullptr;
-	double *tb = nullptr;         // [Mpad]
+	double *zt = nullptr, *ut = nullptr;   // (views into qt)
+	DevBuf<double> tb;            // [Mpad]
 };
 
 namespace {
@@ -709,12 +703,12 @@ int candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows
 		c->M = rows->num_rows;
 		c->Mpad = Mpad;
 		c->k = k;
-		c->qt = dalloc<double>(nq);
-		c->base = dalloc<double>(c->Mpad);
+		c->qt.alloc(nq);
+		c->base.alloc(c->Mpad);
 		if (var) {
 			c->zt = c->qt + (size_t)k * Mpad;
 			c->ut = c->zt + (size_t)k * Mpad;
-			c->tb = dalloc<double>(c->Mpad);
+			c->tb.alloc(c->Mpad);
 			if (c->Mpad) HIPCHK(hipMemsetAsync(c->tb, 0, (size_t)c->Mpad * 8, m->s));
 		}
 		if (nq) HIPCHK(hipMemsetAsync(c->qt, 0, nq * 8, m->s));
@@ -830,11 +824,11 @@ void rank_call(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *context
 	const auto out_doubles = [&](size_t nr) { return d.nvals * nr * topn + (nr * topn * 4 + nr * 4 + 7) / 8; };
 	staging_reserve(m, need_in, out_doubles(need_rows));
 	const size_t rows_pad = round_up(need_rows, ctx);
-	DevScratch<double> base_c(rows_pad), tb_c;
-	if (d.tb) tb_c.p = dalloc<double>(rows_pad);
-	DevScratch<double> qc(d.planes * rows_pad * (size_t)k), part_key(need_part * topn);
-	DevScratch<uint32_t> part_idx(need_part * topn), part_cnt(need_part);
-	DevScratch<unsigned long long> counters(2);
+	DevBuf<double> base_c(rows_pad), tb_c;
+	if (d.tb) tb_c.alloc(rows_pad);
+	DevBuf<double> qc(d.planes * rows_pad * (size_t)k), part_key(need_part * topn);
+	DevBuf<uint32_t> part_idx(need_part * topn), part_cnt(need_part);
+	DevBuf<unsigned long long> counters(2);
 	HIPCHK(hipMemsetAsync(counters, 0, 16, m->s));
 	HIPCHK(hipMemsetAsync(base_c, 0, rows_pad * 8, m->s));
 	if (d.tb) HIPCHK(hipMemsetAsync(tb_c, 0, rows_pad * 8, m->s));
@@ -858,7 +852,7 @@ void rank_call(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *context
 	    [&](size_t i, vbfm_model::Slot &sl) {
 		    const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
 		    const size_t n = (size_t)nr * topn;
-		    hipEvent_t *ev = pe.ev[i & 1];
+		    Event *ev = pe.ev[i & 1];
 		    HIPCHK(hipEventRecord(ev[0], m->s));
 		    launch_prepare(m, sl.d_in, nr, contexts->row_ptr[r0], r0, base_c, tb_c, qc, ctx);
 		    HIPCHK(hipEventRecord(ev[1], m->s));
@@ -925,9 +919,6 @@ void vbfm_candidates_destroy(vbfm_candidates *c)
 {
 	if (!c) return;
 	(void)hipSetDevice(c->dev);
-	dfree(c->qt);
-	dfree(c->base);
-	dfree(c->tb);
 	delete c;
 }
 

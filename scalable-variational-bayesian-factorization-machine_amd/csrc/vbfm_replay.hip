@@ -203,12 +203,14 @@ extern "C" int vbfm_init_params_replay(vbfm_ctx *c, uint32_t seed, double init_s
 		const uint64_t nnorm = r.n_fmv + r.n_fmw + D + kD;
 		r.total = nnorm;
 		uint64_t end_h = 0;
-		r.end = dalloc<uint64_t>(1);
+		DevBuf<uint64_t> end_d(1);
+		r.end = end_d;
 		HIPCHK(hipMemsetAsync(r.end, 0, 8, c->s));
 		uint32_t st0[31];
 		vbrng::glibc_warm_state(seed, st0);
-		double *fmv_d = fm_v_out && r.n_fmv ? dalloc<double>(r.n_fmv) : nullptr;
-		double *fmw_d = fm_w_out && r.n_fmw ? dalloc<double>(r.n_fmw) : nullptr;
+		DevBuf<double> fmv_d, fmw_d;
+		if (fm_v_out && r.n_fmv) fmv_d.alloc(r.n_fmv);
+		if (fm_w_out && r.n_fmw) fmw_d.alloc(r.n_fmw);
 		// ~2.74 uniforms per Leva normal; grow the stream if it falls short
 		uint64_t nuni = (uint64_t)(2.8 * (double)nnorm) + 4 * CHUNK;
 		for (int attempt = 0;; attempt++) {
@@ -227,10 +229,10 @@ extern "C" int vbfm_init_params_replay(vbfm_ctx *c, uint32_t seed, double init_s
 					q[i] = a;
 				}
 			}
-			uint32_t *states_d = dalloc<uint32_t>(states.size());
-			int32_t *out = dalloc<int32_t>(nuni);
-			uint64_t *zpos = dalloc<uint64_t>(MAX_ZEROS);
-			uint32_t *cnt = dalloc<uint32_t>(2);
+			DevBuf<uint32_t> states_d(states.size());
+			DevBuf<int32_t> out(nuni);
+			DevBuf<uint64_t> zpos(MAX_ZEROS);
+			DevBuf<uint32_t> cnt(2);
 			HIPCHK(hipMemcpyAsync(states_d, states.data(), states.size() * 4, hipMemcpyHostToDevice, c->s));
 			HIPCHK(hipMemsetAsync(cnt, 0, 8, c->s));
 			k_glibc_chunks<<<grid_of(nchunks), 256, 0, c->s>>>(states_d, nchunks, out);
@@ -254,10 +256,10 @@ extern "C" int vbfm_init_params_replay(vbfm_ctx *c, uint32_t seed, double init_s
 			}
 			const Seg &last = seg.back();
 			const uint64_t nattempt = nuni >= last.pos + 2 ? last.first + (nuni - last.pos) / 2 : last.first;
-			Seg *seg_d = dalloc<Seg>(seg.size());
+			DevBuf<Seg> seg_d(seg.size());
 			HIPCHK(hipMemcpy(seg_d, seg.data(), seg.size() * sizeof(Seg), hipMemcpyHostToDevice));
-			uint32_t *flag = dalloc<uint32_t>(nattempt), *offs = dalloc<uint32_t>(nattempt);
-			uint64_t *unsure = dalloc<uint64_t>(MAX_UNSURE);
+			DevBuf<uint32_t> flag(nattempt), offs(nattempt);
+			DevBuf<uint64_t> unsure(MAX_UNSURE);
 			k_leva_flags<<<grid_of(nattempt), 256, 0, c->s>>>(out, seg_d, (uint32_t)seg.size(), nattempt, flag, unsure,
 			                                                  cnt + 1);
 			HIPCHK(hipGetLastError());
@@ -281,35 +283,36 @@ extern "C" int vbfm_init_params_replay(vbfm_ctx *c, uint32_t seed, double init_s
 				}
 			}
 			size_t tb = 0;
-			HIPCHK(rocprim::exclusive_scan(nullptr, tb, flag, offs, 0u, (size_t)nattempt, rocprim::plus<uint32_t>(), c->s));
-			void *tmp = dalloc<uint8_t>(tb);
-			HIPCHK(rocprim::exclusive_scan(tmp, tb, flag, offs, 0u, (size_t)nattempt, rocprim::plus<uint32_t>(), c->s));
+			HIPCHK(rocprim::exclusive_scan(nullptr, tb, flag.p, offs.p, 0u, (size_t)nattempt, rocprim::plus<uint32_t>(), c->s));
+			DevBuf<uint8_t> tmp(tb);
+			HIPCHK(rocprim::exclusive_scan(tmp.p, tb, flag.p, offs.p, 0u, (size_t)nattempt, rocprim::plus<uint32_t>(), c->s));
 			uint32_t tail[2] = {0, 0};
 			if (nattempt) {
 				HIPCHK(d2h(c, &tail[0], offs + nattempt - 1, 4));
 				HIPCHK(d2h(c, &tail[1], flag + nattempt - 1, 4));
 			}
 			sync(c);
+			if (attempt == 0 && fault_at("replay")) throw HipError{hipErrorOutOfMemory, "VBFM_FAULT=replay"};
 			const uint64_t accepted = (uint64_t)tail[0] + tail[1];
 			if (accepted >= nnorm)
 				k_leva_route<<<grid_of(nattempt), 256, 0, c->s>>>(out, seg_d, (uint32_t)seg.size(), nattempt, flag, offs,
 				                                                  r, fmv_d, fmw_d, c->ms_w, c->ms_v);
 			HIPCHK(hipGetLastError());
 			sync(c);
-			dfree(tmp); dfree(flag); dfree(offs); dfree(unsure); dfree(seg_d);
-			dfree(states_d); dfree(out); dfree(zpos); dfree(cnt);
+			tmp.reset(); flag.reset(); offs.reset(); unsure.reset(); seg_d.reset();
+			states_d.reset(); out.reset(); zpos.reset(); cnt.reset();
 			if (accepted >= nnorm) break;
 			if (attempt > 8) throw std::string("init replay: stream too short");
 			nuni = nuni + nuni / 4;
 		}
 		// attributes past the drawn ones keep their values; fm_learn_vb::init scalars (:693-712)
 		HIPCHK(hipMemcpy(&end_h, r.end, 8, hipMemcpyDeviceToHost));
-		dfree(r.end);
+		end_d.reset();
 		c->init_stream_seed = seed;
 		c->init_stream_end = end_h;   // outputs after the warm-up that the draws consumed
 		if (fmv_d) HIPCHK(hipMemcpy(fm_v_out, fmv_d, r.n_fmv * 8, hipMemcpyDeviceToHost));
 		if (fmw_d) HIPCHK(hipMemcpy(fm_w_out, fmw_d, r.n_fmw * 8, hipMemcpyDeviceToHost));
-		dfree(fmv_d); dfree(fmw_d);
+		fmv_d.reset(); fmw_d.reset();
 		std::fill(c->hyp_w.begin(), c->hyp_w.end(), 1.0);
 		std::fill(c->hyp_v.begin(), c->hyp_v.end(), 1.0);
 		upload_hyp(c);

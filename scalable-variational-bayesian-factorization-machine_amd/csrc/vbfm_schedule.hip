@@ -11,9 +11,7 @@ namespace vbi {
 // ---- the feature shards' chunks (vbfm_set_shard_mode) ------------------------------------
 void fs_free(vbfm_ctx *c)
 {
-	vbfm_ctx::FeatShards &fs = c->fs;
-	dfree(fs.own); dfree(fs.base); dfree(fs.buf); dfree(fs.pbuf); dfree(fs.rows0);
-	fs = {fs.mode, fs.req};   // what the caller asked for (vbfm_set_shard_mode) stays, the rest starts over
+	c->fs = {c->fs.mode, c->fs.req};   // what the caller asked for (vbfm_set_shard_mode) stays, the rest starts over
 }
 
 // chunk s of level l: level_feats[fs.lo[l*(P+1) + s], fs.lo[l*(P+1) + s + 1])
@@ -37,14 +35,14 @@ static void build_fshards(vbfm_ctx *c)
 		for (uint32_t l = 0; l < L; l++)
 			for (uint32_t i = c->fs.lo[(size_t)l * (P + 1) + c->net.rank]; i < c->fs.lo[(size_t)l * (P + 1) + c->net.rank + 1]; i++)
 				own.push_back(feats[i]);
-		c->fs.own = dalloc<uint32_t>(own.size());
+		c->fs.own.alloc(own.size());
 		c->fs.own_n = (uint32_t)own.size();
 		if (!own.empty()) HIPCHK(hipMemcpy(c->fs.own, own.data(), own.size() * 4, hipMemcpyHostToDevice));
-		c->fs.pbuf = dalloc<double2>(c->tr.nf);
+		c->fs.pbuf.alloc(c->tr.nf);
 	}
-	c->fs.base = dalloc<double>(2 * (size_t)n);
-	c->fs.buf = dalloc<double>(5 * (size_t)n);
-	if (!c->multi() && P > 1) c->fs.rows0 = dalloc<RowRec>(n);
+	c->fs.base.alloc(2 * (size_t)n);
+	c->fs.buf.alloc(5 * (size_t)n);
+	if (!c->multi() && P > 1) c->fs.rows0.alloc(n);
 }
 
 // VBFM_CHECK=1: verify on the device that no level lets two columns touch one row (the
@@ -52,7 +50,7 @@ static void build_fshards(vbfm_ctx *c)
 static void check_schedule(vbfm_ctx *c)
 {
 	const uint32_t n = c->tr.n;
-	DevScratch<uint32_t> owner(n), bad(1);
+	DevBuf<uint32_t> owner(n), bad(1);
 	HIPCHK(hipMemsetAsync(bad, 0, 4, c->s));
 	for (uint32_t l = 0; l < nlevels(c); l++) {
 		HIPCHK(hipMemsetAsync(owner, 0xFF, (size_t)n * 4, c->s));
@@ -62,7 +60,6 @@ static void check_schedule(vbfm_ctx *c)
 	uint32_t nb = 0;
 	HIPCHK(d2h(c, &nb, bad, 4));
 	sync(c);
-	dfree(owner.p); dfree(bad.p);
 	if (nb) throw std::string("VBFM_CHECK: dependency schedule violated (") + std::to_string(nb) + " row claims)";
 }
 
@@ -76,7 +73,7 @@ static void kahn_levels(vbfm_ctx *c, uint32_t *level)
 	if (nf == 0) return;
 	const int batch = 32;
 	const size_t nb = (size_t)nf + 2 * batch + 3;
-	DevScratch<uint32_t> indeg(nf), order(nf), tail(1), bounds(nb);
+	DevBuf<uint32_t> indeg(nf), order(nf), tail(1), bounds(nb);
 	HIPCHK(vbk::kahn_init(d.row_ptr, d.csr, d.n, nf, indeg, level, order, tail, bounds, c->s));
 	uint32_t prev = 0xFFFFFFFFu;
 	for (int t = 0;; t += batch) {
@@ -91,7 +88,7 @@ static void kahn_levels(vbfm_ctx *c, uint32_t *level)
 		if (tl == prev || tl > nf) throw std::string("level schedule did not converge (a feature cycle)");
 		prev = tl;
 	}
-	dfree(indeg.p); dfree(order.p); dfree(tail.p); dfree(bounds.p);   // (in the order they came)
+	indeg.reset(); order.reset(); tail.reset(); bounds.reset();   // (in the order they came)
 }
 
 // Dependency levels of the train features (see vbfm_kernels.hip header). With several
@@ -104,9 +101,8 @@ void build_schedule(vbfm_ctx *c)
 	c->place.bytes = 0;
 	DevData &d = c->tr;
 	const uint32_t nf = d.nf;
-	DevScratch<uint32_t> level(nf), changed(1);
-	dfree(c->dup);
-	c->dup = dalloc<uint8_t>(nf);
+	DevBuf<uint32_t> level(nf), changed(1);
+	c->dup.alloc(nf);
 	HIPCHK(hipMemsetAsync(c->dup, 0, nf, c->s));
 	HIPCHK(vbk::level_init(level, nf, c->s));
 	HIPCHK(vbk::mark_dups(d.row_ptr, d.csr, d.n, c->dup, c->s));
@@ -139,8 +135,8 @@ void build_schedule(vbfm_ctx *c)
 	if (mode == 2) kahn_levels(c, level);
 	c->level_h.assign(nf, 0);
 	if (nf) HIPCHK(hipMemcpy(c->level_h.data(), level, nf * 4, hipMemcpyDeviceToHost));
-	dfree(level.p);   // before level_feats and the store are allocated
-	dfree(changed.p);
+	level.reset();   // before level_feats and the store are allocated
+	changed.reset();
 	uint32_t L = 0;
 	for (uint32_t j = 0; j < nf; j++) L = std::max(L, c->level_h[j]);
 	c->level_ptr.assign((size_t)L + 1, 0);
@@ -148,8 +144,7 @@ void build_schedule(vbfm_ctx *c)
 	for (uint32_t l = 0; l < L; l++) c->level_ptr[l + 1] += c->level_ptr[l];
 	std::vector<uint32_t> feats(nf), pos(c->level_ptr.begin(), c->level_ptr.end() - 1);
 	for (uint32_t j = 0; j < nf; j++) feats[pos[c->level_h[j] - 1]++] = j;   // ascending j per level
-	dfree(c->level_feats);
-	c->level_feats = dalloc<uint32_t>(nf);
+	c->level_feats.alloc(nf);
 	if (nf) HIPCHK(hipMemcpy(c->level_feats, feats.data(), nf * 4, hipMemcpyHostToDevice));
 	std::vector<uint64_t> cp((size_t)nf + 1, 0);
 	HIPCHK(hipMemcpy(cp.data(), d.col_ptr, ((size_t)nf + 1) * 8, hipMemcpyDeviceToHost));
@@ -167,11 +162,7 @@ void build_schedule(vbfm_ctx *c)
 	}
 	uint32_t maxlev = 0;
 	for (uint32_t l = 0; l < L; l++) maxlev = std::max(maxlev, c->level_ptr[l + 1] - c->level_ptr[l]);
-	if (c->split() && maxlev > c->stats_cap) {
-		dfree(c->stats);
-		c->stats = dalloc<double2>(maxlev);
-		c->stats_cap = maxlev;
-	}
+	if (c->split()) c->stats.reserve(maxlev);
 	c->sched_ready = true;
 	// a failure from here on (the store's allocations, the placement search) leaves the schedule to
 	// be rebuilt by the next call instead of running on a half-built store

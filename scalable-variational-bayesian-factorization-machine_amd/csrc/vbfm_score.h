@@ -294,22 +294,24 @@ struct vbfm_model {
 	int dev = 0;
 	vbfm_model_info info = {};
 	int32_t task = VBFM_TASK_REGRESSION;          // task c: clip = 1 scores are Phi(yhat), clip = 0 the raw yhat
-	double *mw = nullptr, *mv = nullptr;          // means: w [D], v [j*k + f] (ALS / MCMC: the values)
-	double2 *ms_w = nullptr, *ms_v = nullptr;     // VB kinds: the {mu, sigma} pairs
+	vbi::Stream s, s_copy;                        // kernels and results; the chunks' copies to the device
+	vbi::DevBuf<double> mw, mv;                   // means: w [D], v [j*k + f] (ALS / MCMC: the values)
+	vbi::DevBuf<double2> ms_w, ms_v;              // VB kinds: the {mu, sigma} pairs
 	// VBFM_MODEL_MCMC_CHAIN: S draws, feature-major with the draws of a feature adjacent (mw / mv are
 	// not allocated): cw [j*S + s], cv [(j*S + s)*k + f], cw0 = w0 [s] then alpha [S + s]; the draws' scalars also on the host
 	uint32_t S = 1;
-	double *cw = nullptr, *cv = nullptr, *cw0 = nullptr;
+	vbi::DevBuf<double> cw, cv, cw0;
 	std::vector<double> draw_w0, draw_alpha;
-	hipStream_t s = nullptr, s_copy = nullptr;    // kernels and results; the chunks' copies to the device
-	vbs::ScoreFlags *flags = nullptr;
+	vbi::DevBuf<vbs::ScoreFlags> flags;
 	// the staging of caller rows, kept between calls: two pinned host and two device buffers for the
 	// chunks ([row_ptr slice | entries], vbfm_recommend: + the exclusion lists) and for their results
 	// (vbfm_score: [mean | var])
 	struct Slot {
-		uint8_t *h_in = nullptr, *d_in = nullptr;
-		double *h_out = nullptr, *d_out = nullptr;
-		hipEvent_t ev[vbs::SEV_N] = {};
+		vbi::HostBuf<uint8_t> h_in;
+		vbi::HostBuf<double> h_out;
+		vbi::DevBuf<uint8_t> d_in;
+		vbi::DevBuf<double> d_out;
+		vbi::Event ev[vbs::SEV_N];
 	} slot[2];
 	size_t cap_in = 0, cap_out = 0;               // bytes of every h_in / d_in; doubles of every h_out / d_out
 };
@@ -342,12 +344,8 @@ template <class F> int mguarded(vbfm_model *m, F &&fn)
 inline void staging_free(vbfm_model *m)
 {
 	for (auto &sl : m->slot) {
-		if (sl.h_in) (void)hipHostFree(sl.h_in);
-		if (sl.h_out) (void)hipHostFree(sl.h_out);
-		sl.h_in = nullptr;
-		sl.h_out = nullptr;
-		dfree(sl.d_in);
-		dfree(sl.d_out);
+		sl.h_in.reset(); sl.h_out.reset();
+		sl.d_in.reset(); sl.d_out.reset();
 	}
 	m->cap_in = m->cap_out = 0;
 }
@@ -360,10 +358,10 @@ inline void staging_reserve(vbfm_model *m, size_t need_in, size_t need_out)
 	need_out = std::max(need_out, m->cap_out);
 	staging_free(m);
 	for (auto &sl : m->slot) {
-		HIPCHK(hipHostMalloc((void **)&sl.h_in, need_in, hipHostMallocDefault));
-		HIPCHK(hipHostMalloc((void **)&sl.h_out, std::max<size_t>(need_out, 1) * 8, hipHostMallocDefault));
-		sl.d_in = dalloc<uint8_t>(need_in);
-		sl.d_out = dalloc<double>(need_out);
+		sl.h_in.alloc(need_in);
+		sl.h_out.alloc(need_out);
+		sl.d_in.alloc(need_in);
+		sl.d_out.alloc(need_out);
 	}
 	m->cap_in = need_in;
 	m->cap_out = need_out;

@@ -105,38 +105,30 @@ void model_free(vbfm_model *m)
 {
 	if (!m) return;
 	(void)hipSetDevice(m->dev);
-	staging_free(m);
-	for (auto &sl : m->slot)
-		for (hipEvent_t &e : sl.ev)
-			if (e) (void)hipEventDestroy(e);
-	dfree(m->mw); dfree(m->mv); dfree(m->ms_w); dfree(m->ms_v); dfree(m->flags);
-	dfree(m->cw); dfree(m->cv); dfree(m->cw0);
-	if (m->s) (void)hipStreamDestroy(m->s);
-	if (m->s_copy) (void)hipStreamDestroy(m->s_copy);
-	delete m;
+	delete m;   // the staging and its events, the tables, then the streams
 }
 
 // streams, events, the flag word and the tables of m->info's shape (their contents are the caller's)
 void model_alloc(vbfm_model *m)
 {
 	HIPCHK(hipSetDevice(m->dev));
-	HIPCHK(hipStreamCreateWithFlags(&m->s, hipStreamNonBlocking));
-	HIPCHK(hipStreamCreateWithFlags(&m->s_copy, hipStreamNonBlocking));
+	m->s.create();
+	m->s_copy.create();
 	for (auto &sl : m->slot)
-		for (hipEvent_t &e : sl.ev) HIPCHK(hipEventCreate(&e));
-	m->flags = dalloc<ScoreFlags>(1);
+		for (Event &e : sl.ev) e.create();
+	m->flags.alloc(1);
 	const size_t D = m->info.num_attribute, kd = D * (size_t)m->info.num_factor;
 	if (kind_chain(m->info.kind)) {
-		m->cw = dalloc<double>(D * m->S);
-		m->cv = dalloc<double>(kd * m->S);
-		m->cw0 = dalloc<double>(2 * (size_t)m->S);   // w0 [s], then alpha [S + s]
+		m->cw.alloc(D * m->S);
+		m->cv.alloc(kd * m->S);
+		m->cw0.alloc(2 * (size_t)m->S);   // w0 [s], then alpha [S + s]
 		return;
 	}
-	m->mw = dalloc<double>(D);
-	m->mv = dalloc<double>(kd);
+	m->mw.alloc(D);
+	m->mv.alloc(kd);
 	if (kind_vb(m->info.kind)) {
-		m->ms_w = dalloc<double2>(D);
-		m->ms_v = dalloc<double2>(kd);
+		m->ms_w.alloc(D);
+		m->ms_v.alloc(kd);
 	}
 }
 
@@ -378,7 +370,7 @@ int vbfm_score(vbfm_model *m, const vbfm_csr *rows, const vbfm_score_opts *opts,
 		    [&](size_t i, vbfm_model::Slot &sl) {
 			    const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
 			    ScoreArgs a = score_args(m, o.clip);
-			    a.row_ptr = (const uint64_t *)sl.d_in;
+			    a.row_ptr = (const uint64_t *)sl.d_in.p;
 			    a.ent = (const uint2 *)(sl.d_in + ((size_t)nr + 1) * 8);
 			    a.ent_base = rows->row_ptr[r0];
 			    a.mean = sl.d_out;
@@ -422,7 +414,7 @@ int vbfm_score_device(vbfm_model *m, vbfm_ctx *c, int32_t which, const vbfm_scor
 		if (!d.row_ptr) throw std::string(which ? "no test data set (vbfm_set_test)" : "no train data set (vbfm_set_train)");
 		sync(c);   // the set is complete in device memory
 		vbfm_score_stats out = {};
-		DevScratch<double> res((size_t)d.n * (var ? 2 : 1));
+		DevBuf<double> res((size_t)d.n * (var ? 2 : 1));
 		flags_reset(m);
 		ScoreArgs a = score_args(m, o.clip);
 		a.row_ptr = d.row_ptr;

@@ -12,9 +12,7 @@ namespace vbi {
 void store_release(vbfm_ctx *c)
 {
 	vbfm_ctx::Store &st = c->store;
-	dfree(st.rows_alt); dfree(st.lcp); dfree(st.lx); dfree(st.lnext); dfree(st.lrow0); dfree(st.lpos0);
-	dfree(st.lpidx); dfree(st.lpx); dfree(st.post_tab); dfree(st.lpay); dfree(st.lpay2);
-	dfree(st.long_segs); dfree(st.seg_part);
+	c->rec_release(st.rows_alt);
 	st = {st.layout_req};   // the request stays, every build product starts over
 }
 
@@ -81,9 +79,9 @@ static void build_long_segs(vbfm_ctx *c, const std::vector<uint64_t> &lcp, const
 	c->store.seg_ptr[L] = (uint32_t)segs.size();
 	if (segs.empty()) return;
 	c->store.long_min = 1;   // some level has segments (each level's threshold: long_min_l)
-	c->store.long_segs = dalloc<LongSeg>(segs.size());
+	c->store.long_segs.alloc(segs.size());
 	HIPCHK(hipMemcpyAsync(c->store.long_segs, segs.data(), segs.size() * sizeof(LongSeg), hipMemcpyHostToDevice, c->s));
-	c->store.seg_part = dalloc<double2>(2 * (size_t)maxs);
+	c->store.seg_part.alloc(2 * (size_t)maxs);
 	sync(c);
 }
 
@@ -92,14 +90,14 @@ static void build_long_segs(vbfm_ctx *c, const std::vector<uint64_t> &lcp, const
 static void alloc_lx(vbfm_ctx *c)
 {
 	DevData &d = c->tr;
-	DevScratch<uint32_t> cnt(1);
+	DevBuf<uint32_t> cnt(1);
 	uint32_t h = 1;
 	HIPCHK(vbk::count_x_ne1(d.csc, d.nnz, cnt, c->s));
 	HIPCHK(d2h(c, &h, cnt, 4));
 	sync(c);
-	dfree(cnt.p);
+	cnt.reset();
 	const char *kx = getenv("VBFM_LX");
-	if (h != 0 || (kx && kx[0] == '1')) c->store.lx = dalloc<float>(d.nnz);
+	if (h != 0 || (kx && kx[0] == '1')) c->store.lx.alloc(d.nnz);
 }
 
 // the deferred kernels' payload: one 16-B record per entry {x, next position, previous entry's
@@ -108,10 +106,10 @@ static void pack_payload(vbfm_ctx *c, const uint32_t *pidx, const float *px)
 {
 	const uint64_t nnz = c->tr.nnz;
 	if (c->store.lx) {
-		c->store.lpay = dalloc<uint4>(nnz);
+		c->store.lpay.alloc(nnz);
 		HIPCHK(vbk::lord_pack(c->store.lx, c->store.lnext, pidx, px, c->store.lpay, nnz, c->s));
 	} else {
-		c->store.lpay2 = dalloc<uint2>(nnz);
+		c->store.lpay2.alloc(nnz);
 		HIPCHK(vbk::lord_pack2(c->store.lnext, pidx, c->store.lpay2, nnz, c->s));
 	}
 }
@@ -150,15 +148,15 @@ static bool build_estore(vbfm_ctx *c, const std::vector<uint64_t> &lcp, const st
 	}
 	std::vector<uint32_t> lvpos(nf);
 	for (uint32_t i = 0; i < nf; i++) lvpos[feats[i]] = i;
-	c->store.lcp = dalloc<uint64_t>(lcp.size());
+	c->store.lcp.alloc(lcp.size());
 	HIPCHK(hipMemcpyAsync(c->store.lcp, lcp.data(), lcp.size() * 8, hipMemcpyHostToDevice, c->s));
-	DevScratch<uint32_t> lv(nf);
+	DevBuf<uint32_t> lv(nf);
 	HIPCHK(hipMemcpyAsync(lv, lvpos.data(), (size_t)nf * 4, hipMemcpyHostToDevice, c->s));
 	alloc_lx(c);
-	c->store.lnext = dalloc<uint32_t>(d.nnz);
-	c->store.lpos0 = dalloc<uint32_t>(n);
+	c->store.lnext.alloc(d.nnz);
+	c->store.lpos0.alloc(n);
 	// slots: the entries, then one parking slot per row (used by rows without entries)
-	c->store.rows_alt = dalloc<RowRec>(d.nnz + n);
+	c->store.rows_alt = c->rec_alloc(d.nnz + n);
 	HIPCHK(hipMemsetAsync(c->store.rows_alt, 0, (d.nnz + n) * sizeof(RowRec), c->s));
 	HIPCHK(vbk::estore_build(d.row_ptr, d.csr, d.col_ptr, d.csc, lv, c->store.lcp, n, d.nnz, c->store.lnext,
 	                         c->store.lx, c->store.lpos0, c->s));
@@ -168,15 +166,15 @@ static bool build_estore(vbfm_ctx *c, const std::vector<uint64_t> &lcp, const st
 	// communicator, profiles/r03_multihot_split/); VBFM_DEFER=1 takes the deferred form
 	const char *df = getenv("VBFM_DEFER");
 	if (c->split() && df && df[0] == '1') {
-		DevScratch<uint32_t> pidx(d.nnz);
-		DevScratch<float> px(d.nnz);
+		DevBuf<uint32_t> pidx(d.nnz);
+		DevBuf<float> px(d.nnz);
 		HIPCHK(vbk::estore_prev(d.row_ptr, d.csr, d.col_ptr, d.csc, lv, c->store.lcp, n, pidx, px, c->s));
 		pack_payload(c, pidx, px);
-		c->store.post_tab = dalloc<PostT>(std::max(nf, 1u));
+		c->store.post_tab.alloc(std::max(nf, 1u));
 		HIPCHK(hipMemsetAsync(c->store.post_tab, 0, (size_t)std::max(nf, 1u) * sizeof(PostT), c->s));
 		sync(c);
-		dfree(pidx.p);
-		dfree(px.p);
+		pidx.reset();
+		px.reset();
 	}
 	sync(c);
 	c->store.lord = true;
@@ -193,32 +191,22 @@ static bool place_search(vbfm_ctx *c, size_t bytes, int extra)
 	const uint32_t nfl = c->level_ptr[1] - c->level_ptr[0];
 	// what the search holds is let go on every way out, in the reverse of this order: the fresh
 	// candidates it still owns, the stash, the reference buffer, the two events
-	struct Events {
-		hipEvent_t e0 = nullptr, e1 = nullptr;
-		~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-	} ev;
-	DevScratch<RowRec> ref_buf, keep_buf;
-	// cand[0], cand[1]: the store's own pair; the rest fresh allocations this search owns until it
-	// commits. On any failure the records go back into c->rows from the stash and the error
-	// propagates (build_schedule then leaves the schedule to be rebuilt by the next call)
-	struct Cands {
-		std::vector<RowRec *> v;
-		~Cands() { for (size_t i = 2; i < v.size(); i++) dfree(v[i]); }
-	} cands{{c->rows, c->store.rows_alt}};
+	Event e0, e1;
+	DevBuf<RowRec> ref_buf, keep_buf;
+	// cand[0], cand[1]: the store's own pair (views); the rest views of the fresh allocations this
+	// search owns until it commits. On any failure the records go back into c->rows from the stash and
+	// the error propagates (build_schedule then leaves the schedule to be rebuilt by the next call)
+	std::vector<DevBuf<RowRec>> fresh;
+	std::vector<RowRec *> cand{c->rows, c->store.rows_alt};
 	// the records wait in a stash while every candidate is overwritten
-	if (hipMalloc((void **)&keep_buf.p, bytes) != hipSuccess || hipMalloc((void **)&ref_buf.p, bytes) != hipSuccess) {
-		(void)hipGetLastError();
-		return false;
-	}
-	RowRec *const keep = keep_buf.p, *const ref = ref_buf.p;
-	hipEvent_t &e0 = ev.e0, &e1 = ev.e1;
-	std::vector<RowRec *> &cand = cands.v;
+	if (!keep_buf.try_alloc(bytes / sizeof(RowRec)) || !ref_buf.try_alloc(bytes / sizeof(RowRec))) return false;
+	RowRec *const keep = keep_buf, *const ref = ref_buf;
 	bool stashed = false;
 	try {
 		HIPCHK(hipMemcpyAsync(keep, c->rows, bytes, hipMemcpyDeviceToDevice, c->s));
 		stashed = true;
-		HIPCHK(hipEventCreate(&e0));
-		HIPCHK(hipEventCreate(&e1));
+		e0.create();
+		e1.create();
 		// x -> y once to warm up, then both directions twice between the two events
 		auto score_pair = [&](RowRec *x, RowRec *y) {
 			HIPCHK(vbk::place_move(x, y, lp, c->store.lnext, nfl, c->s));   // warm-up
@@ -237,12 +225,10 @@ static bool place_search(vbfm_ctx *c, size_t bytes, int extra)
 		// 14.1 ms against 11.5-11.8 ms for plain ones at C4 and no better at C3: not tried)
 		// (an allocation the driver refuses ends the list: the tuning never fails the store)
 		for (int i = 0; i < extra; i++) {
-			void *q = nullptr;
-			if (hipMalloc(&q, bytes) != hipSuccess) {
-				(void)hipGetLastError();
-				break;
-			}
-			cand.push_back((RowRec *)q);
+			DevBuf<RowRec> q;
+			if (!q.try_alloc(bytes / sizeof(RowRec))) break;
+			cand.push_back(q);
+			fresh.push_back(std::move(q));
 		}
 		c->place.bytes = (uint64_t)bytes * cand.size();   // the fresh candidates + the stash + the reference
 		std::vector<float> ms(cand.size());
@@ -272,10 +258,14 @@ static bool place_search(vbfm_ctx *c, size_t bytes, int extra)
 			std::swap(order[1], order[bb]);   // bb > ba >= 0: untouched by the first swap
 		}
 		// commit (nothing below the frees can throw before c->rows names a live buffer again)
-		for (size_t j = 2; j < order.size(); j++) dfree(cand[order[j]]);
+		for (size_t j = 2; j < order.size(); j++) {
+			if (order[j] < 2) c->rec_release(cand[order[j]]);
+			else fresh[order[j] - 2].reset();
+		}
+		for (int j = 0; j < 2; j++)   // a fresh buffer kept goes to the owner that lost its own
+			if (order[j] >= 2) c->rec[c->rec[0] ? 1 : 0] = std::move(fresh[order[j] - 2]);
 		c->rows = cand[order[0]];
 		c->store.rows_alt = cand[order[1]];
-		cand.resize(2);   // every fresh buffer is now the store's or freed
 		HIPCHK(hipMemcpyAsync(c->rows, keep, bytes, hipMemcpyDeviceToDevice, c->s));
 		sync(c);
 		stashed = false;
@@ -390,16 +380,15 @@ void build_lorder(vbfm_ctx *c, const std::vector<uint64_t> &cp, const std::vecto
 		build_estore(c, lcp, dup, feats, true);
 		return;
 	}
-	c->store.lcp = dalloc<uint64_t>(lcp.size());
+	c->store.lcp.alloc(lcp.size());
 	HIPCHK(hipMemcpyAsync(c->store.lcp, lcp.data(), lcp.size() * 8, hipMemcpyHostToDevice, c->s));
 	build_long_segs(c, lcp, dup, feats);
 	alloc_lx(c);
-	c->store.lnext = dalloc<uint32_t>(d.nnz);
-	c->store.lrow0 = dalloc<uint32_t>(n);
-	c->store.lpos0 = dalloc<uint32_t>(n);
-	c->store.rows_alt = dalloc<RowRec>(n);
-	DevScratch<uint32_t> tmp_buf(n);   // freed on every path out, the placement search's failure included
-	uint32_t *&tmp = tmp_buf.p;
+	c->store.lnext.alloc(d.nnz);
+	c->store.lrow0.alloc(n);
+	c->store.lpos0.alloc(n);
+	c->store.rows_alt = c->rec_alloc(n);
+	DevBuf<uint32_t> tmp(n);
 	auto lev = [&](uint32_t l, uint32_t *&f, uint32_t &nfl, const uint64_t *&lp) {
 		f = c->level_feats + c->level_ptr[l];
 		nfl = c->level_ptr[l + 1] - c->level_ptr[l];
@@ -423,10 +412,9 @@ void build_lorder(vbfm_ctx *c, const std::vector<uint64_t> &cp, const std::vecto
 	// correction (VBFM_DEFER=0 keeps the two-pass split)
 	const char *df = getenv("VBFM_DEFER");
 	if (c->split() && !(df && df[0] == '0')) {
-		c->store.lpidx = dalloc<uint32_t>(d.nnz);
-		c->store.lpx = dalloc<float>(d.nnz);
-		DevScratch<float> tmpx_buf(n);
-		float *&tmpx = tmpx_buf.p;
+		c->store.lpidx.alloc(d.nnz);
+		c->store.lpx.alloc(d.nnz);
+		DevBuf<float> tmpx(n);
 		uint32_t maxlev = 0;
 		for (uint32_t l = 0; l < L; l++) {
 			const uint32_t pl = (l + L - 1) % L;
@@ -436,17 +424,16 @@ void build_lorder(vbfm_ctx *c, const std::vector<uint64_t> &cp, const std::vecto
 			lev(l, f, nfl, lp);
 			HIPCHK(vbk::lord_prev_fill(f, nfl, lp, d.col_ptr, d.csc, tmp, tmpx, c->store.lpidx, c->store.lpx, c->s));
 		}
-		c->store.post_tab = dalloc<PostT>(maxlev);
+		c->store.post_tab.alloc(maxlev);
 		sync(c);
-		dfree(tmpx);
-		// the separate arrays are not read in this mode any more
-		dfree(tmp);
+		tmpx.reset();
+		tmp.reset();   // (before the payload is allocated)
 		pack_payload(c, c->store.lpidx, c->store.lpx);
 		sync(c);
-		dfree(c->store.lx); dfree(c->store.lnext); dfree(c->store.lpidx); dfree(c->store.lpx);
+		// the separate arrays are not read in this mode any more
+		c->store.lx.reset(); c->store.lnext.reset(); c->store.lpidx.reset(); c->store.lpx.reset();
 	}
 	sync(c);
-	dfree(tmp);
 	c->store.lord = true;
 }
 
