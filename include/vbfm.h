@@ -416,7 +416,14 @@ int vbfm_online_get_state(vbfm_ctx *ctx, double *nat_mu_w, double *nat_sigma_w, 
 #define VBFM_RNG_DEVICE 1     /* hyper-prior draws from that stream; the per-attribute
                                  normals of draw_w / draw_v from a counter-based generator
                                  keyed (seed, iteration, factor, attribute), identical on
-                                 every shard; fm.w / fm.v initialised on the device */
+                                 every shard; fm.w / fm.v initialised on the device.
+                                 normal(seed, stream, j) is Box-Muller on the 53-bit uniforms
+                                 of splitmix64(seed * K1 + stream * K2 + 2j) and (+ 1). Stream
+                                 ids: a sweep's is iteration * (k + 1) + (0 for w, f + 1 for
+                                 v_f); bits 63 and 62 are reserved -- bit 63 | iteration keys
+                                 the row draws of task c, bit 62 | 21 initialises fm.v (v_f[j]
+                                 takes j * k + f) and bit 62 | 22 fm.w -- so no two share a
+                                 stream */
 
 typedef struct {
 	int32_t do_sample;        /* fm_learn_mcmc::do_sample: 1 mcmc, 0 als (libfm.cpp:131-135, 303) */

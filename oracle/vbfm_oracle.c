@@ -1247,8 +1247,18 @@ int or_als_attach(or_als *st, const or_data *train, const or_data *test)
 }
 
 /* draw_w (fm_learn_mcmc.h:671-718) */
+/* the normal of attribute j's draw in sweep f (-1: draw_w): ran_gaussian(mean, stdev) on the
+ * or_srand stream, or -- with a source attached (VBFM_RNG_DEVICE's contract, include/vbfm.h) --
+ * mean + stdev * fn(user, iteration, f, j), under random.h:166-172's guard either way */
+static double als_gaussian(or_als *st, double mean, double stdev, int f, uint32_t j)
+{
+	if (!st->normal_fn) return or_ran_gaussian_ms(mean, stdev);
+	if (stdev == 0.0 || isnan(stdev)) return mean;
+	return mean + stdev * st->normal_fn(st->normal_user, st->iter_done, f, j);
+}
+
 static void als_draw_w(or_als *st, double *w, double w_mu, double w_lambda,
-                       const uint32_t *rows, const float *vals, uint64_t n)
+                       const uint32_t *rows, const float *vals, uint64_t n, uint32_t j)
 {
 	double w_sigma_sqr = 0, w_mean = 0, w_old;
 	uint64_t p;
@@ -1261,7 +1271,7 @@ static void als_draw_w(or_als *st, double *w, double w_mu, double w_lambda,
 	w_mean = -w_sigma_sqr * (st->alpha * w_mean - w_mu * w_lambda);
 	w_old = *w;
 	if (isnan(w_sigma_sqr) || isinf(w_sigma_sqr)) *w = 0.0;
-	else *w = st->do_sample ? or_ran_gaussian_ms(w_mean, sqrt(w_sigma_sqr)) : w_mean;
+	else *w = st->do_sample ? als_gaussian(st, w_mean, sqrt(w_sigma_sqr), -1, j) : w_mean;
 	if (isnan(*w)) { st->nan_w++; *w = w_old; return; }
 	if (isinf(*w)) { st->inf_w++; *w = w_old; return; }
 	for (p = 0; p < n; p++) {
@@ -1272,7 +1282,7 @@ static void als_draw_w(or_als *st, double *w, double w_mu, double w_lambda,
 
 /* draw_v (fm_learn_mcmc.h:780-835) */
 static void als_draw_v(or_als *st, double *v, double v_mu, double v_lambda,
-                       const uint32_t *rows, const float *vals, uint64_t n)
+                       const uint32_t *rows, const float *vals, uint64_t n, int f, uint32_t j)
 {
 	double v_sigma_sqr = 0, v_mean = 0, v_old;
 	uint64_t p;
@@ -1288,7 +1298,7 @@ static void als_draw_v(or_als *st, double *v, double v_mu, double v_lambda,
 	v_mean = -v_sigma_sqr * (st->alpha * v_mean - v_mu * v_lambda);
 	v_old = *v;
 	if (isnan(v_sigma_sqr) || isinf(v_sigma_sqr)) *v = 0.0;
-	else *v = st->do_sample ? or_ran_gaussian_ms(v_mean, sqrt(v_sigma_sqr)) : v_mean;
+	else *v = st->do_sample ? als_gaussian(st, v_mean, sqrt(v_sigma_sqr), f, j) : v_mean;
 	if (isnan(*v)) { st->nan_v++; *v = v_old; return; }
 	if (isinf(*v)) { st->inf_v++; *v = v_old; return; }
 	for (p = 0; p < n; p++) {
@@ -1402,6 +1412,117 @@ static void mc_draw_v_mu(or_als *st)
 	}
 }
 
+/* ---- binary classification (-task c, probit link) ------------------------------------------ */
+
+/* the reference's own erf, which shadows libm's (random.h:47-61), and cdf_gaussian (:67-69) */
+static double or_erf(double x)
+{
+	double t, result;
+	if (x >= 0) t = 1.0 / (1.0 + 0.3275911 * x);
+	else t = 1.0 / (1.0 - 0.3275911 * x);
+	result = 1.0 - (t * (0.254829592 + t * (-0.284496736 + t * (1.421413741 + t * (-1.453152027 + t * 1.061405429))))) * exp(-x * x);
+	return x >= 0 ? result : -result;
+}
+
+double or_cdf_gaussian(double x) { return 0.5 + 0.5 * or_erf(0.707106781 * x); }
+
+/* ran_left_tgaussian(left) (random.h:72-102) on the or_srand stream: naive rejection of a Leva
+ * normal for left <= 0, Robert's translated exponential above; ran_exp is :178-180 */
+static double or_ran_left_tgaussian1(double left)
+{
+	if (left <= 0.0) {
+		double result;
+		do { result = or_ran_gaussian(); } while (result < left);
+		return result;
+	} else {
+		double alpha_star = 0.5 * (left + sqrt(left * left + 4.0)), z, d, u;
+		for (;;) {
+			z = -log(1 - or_uniform()) / alpha_star + left;
+			d = z - alpha_star;
+			d = exp(-(d * d) / 2);
+			u = or_uniform();
+			if (u < d) return z;
+		}
+	}
+}
+
+/* random.h:104-114 */
+double or_ran_left_tgaussian(double left, double mean, double stdev)
+{
+	return mean + stdev * or_ran_left_tgaussian1((left - mean) / stdev);
+}
+
+double or_ran_right_tgaussian(double right, double mean, double stdev)
+{
+	return mean + stdev * -or_ran_left_tgaussian1(-((right - mean) / stdev));
+}
+
+/* :193 / :333 / :389: a zero target is never counted */
+static int class_correct(double p, float y) { return ((p >= 0.5) && (y > 0.0)) || ((p < 0.5) && (y < 0.0)); }
+
+/* the sums of _evaluate_class (fm_learn_mcmc_simultaneous.h:383-401) */
+static void class_evaluate(const double *pred, const float *target, uint32_t n, double normalizer,
+                           uint32_t *correct, double *loglikelihood)
+{
+	double ll = 0.0;
+	uint32_t c, acc = 0;
+	for (c = 0; c < n; c++) {
+		double p = pred[c] * normalizer, m, pll;
+		if (class_correct(p, target[c])) acc++;
+		m = (target[c] + 1.0) * 0.5;
+		pll = p;
+		if (pll > 0.99) pll = 0.99;
+		if (pll < 0.01) pll = 0.01;
+		ll -= m * log10(pll) + (1 - m) * log10(1 - pll);
+	}
+	*correct = acc;
+	*loglikelihood = ll / n;
+}
+
+/* the row step of task c after the re-prediction (fm_learn_mcmc_simultaneous.h:176-221) and the
+ * test evaluation (:262-270). ll_all, which the reference leaves uninitialised, is
+ * _evaluate_class on the running mean. */
+static void als_class_rows(or_als *st, const or_data *train, const or_data *test)
+{
+	uint32_t c, acc = 0;
+	for (c = 0; c < test->num_rows; c++) {
+		double p = or_cdf_gaussian(st->e_test[c]);
+		st->pred_this[c] = p;
+		st->pred_sum_all[c] += p;
+	}
+	for (c = 0; c < train->num_rows; c++) {
+		double mu = st->e[c], p = or_cdf_gaussian(mu), sampled_target;
+		int positive = train->target[c] >= 0.0;
+		if (class_correct(p, train->target[c])) acc++;
+		if (st->do_sample && st->latent_fn) {
+			sampled_target = st->latent_fn(st->latent_user, st->iter_done, c, mu, positive);
+		} else if (st->do_sample) {
+			sampled_target = positive ? or_ran_left_tgaussian(0.0, mu, 1.0) : or_ran_right_tgaussian(0.0, mu, 1.0);
+		} else {   /* the expected value of the truncated normal, pi = 3.141 as written */
+			double phi_minus_mu = exp(-mu * mu / 2.0) / sqrt(3.141 * 2);
+			double Phi_minus_mu = or_cdf_gaussian(-mu);
+			sampled_target = positive ? mu + phi_minus_mu / (1 - Phi_minus_mu) : mu - phi_minus_mu / Phi_minus_mu;
+		}
+		st->e[c] = mu - sampled_target;
+	}
+	st->n_train_correct = acc;
+	class_evaluate(st->pred_this, test->target, test->num_rows, 1.0, &st->n_test_correct_this, &st->ll_this);
+	class_evaluate(st->pred_sum_all, test->target, test->num_rows, 1.0 / (st->iter_done + 1),
+	               &st->n_test_correct_all, &st->ll_all);
+}
+
+void or_als_set_task(or_als *st, int task) { st->task = task; }
+
+void or_als_set_normal_source(or_als *st, or_normal_fn fn, void *user)
+{
+	st->normal_fn = fn; st->normal_user = user;
+}
+
+void or_als_set_latent_source(or_als *st, or_latent_fn fn, void *user)
+{
+	st->latent_fn = fn; st->latent_user = user;
+}
+
 void or_als_iterate(or_als *st, const or_data *train, const or_data *test,
                     double *rmse_all, double *rmse_this, double *train_rmse)
 {
@@ -1428,11 +1549,11 @@ void or_als_iterate(or_als *st, const or_data *train, const or_data *test,
 			uint32_t g = st->attr_group[i];
 			uint64_t b = train->col_ptr[i];
 			als_draw_w(st, &st->w[i], st->w_mu[g], st->w_lambda[g], train->col_row + b,
-			           train->col_val + b, train->col_ptr[i + 1] - b);
+			           train->col_val + b, train->col_ptr[i + 1] - b, i);
 		}
 		for (i = train->num_feature; i < st->D; i++) {
 			uint32_t g = st->attr_group[i];
-			als_draw_w(st, &st->w[i], st->w_mu[g], st->w_lambda[g], NULL, NULL, 0);
+			als_draw_w(st, &st->w[i], st->w_mu[g], st->w_lambda[g], NULL, NULL, 0, i);
 		}
 	}
 	if (st->k > 0) {
@@ -1449,17 +1570,23 @@ void or_als_iterate(or_als *st, const or_data *train, const or_data *test,
 			uint32_t g = st->attr_group[i];
 			uint64_t b = train->col_ptr[i];
 			als_draw_v(st, &v[i], st->v_mu[(size_t)g * st->k + f], st->v_lambda[(size_t)g * st->k + f],
-			           train->col_row + b, train->col_val + b, train->col_ptr[i + 1] - b);
+			           train->col_row + b, train->col_val + b, train->col_ptr[i + 1] - b, f, i);
 		}
 		for (i = train->num_feature; i < st->D; i++) {
 			uint32_t g = st->attr_group[i];
 			als_draw_v(st, &v[i], st->v_mu[(size_t)g * st->k + f], st->v_lambda[(size_t)g * st->k + f],
-			           NULL, NULL, 0);
+			           NULL, NULL, 0, f, i);
 		}
 	}
 	/* fm_learn_mcmc_simultaneous.h:134-175 */
 	als_predict(st, train, st->e, st->q);
 	als_predict(st, test, st->e_test, st->q_test);
+	if (st->task == OR_TASK_CLASSIFICATION) {
+		als_class_rows(st, train, test);
+		*rmse_all = *rmse_this = *train_rmse = 0.0;
+		st->iter_done++;
+		return;
+	}
 	for (c = 0; c < test->num_rows; c++) {
 		double pp = st->e_test[c];
 		st->pred_this[c] = pp;

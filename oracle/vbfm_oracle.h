@@ -130,6 +130,16 @@ void or_ovb_init(or_ovb *st, uint32_t seed, double init_stdev, const or_data *tr
 /* one epoch: shuffle, batches, update_all per batch, test RMSE / MAE */
 void or_ovb_epoch(or_ovb *st, const or_data *train, const or_data *test, double *rmse, double *mae);
 
+/* Optional sources of two kinds of draws, for holding libvbfm's VBFM_RNG_DEVICE chains to this
+ * oracle (include/vbfm.h): the standard normal of attribute j's draw in iteration iter (0-based),
+ * sweep f (-1: draw_w), and the latent target of train row `row` in task c given its prediction.
+ * With a source attached those draws take nothing from the or_srand stream; alpha, w0 and the
+ * hyper-prior draws always do. */
+typedef double (*or_normal_fn)(void *user, uint32_t iter, int f /* -1: draw_w */, uint32_t j);
+typedef double (*or_latent_fn)(void *user, uint32_t iter, uint32_t row, double yhat, int positive);
+#define OR_TASK_REGRESSION 0
+#define OR_TASK_CLASSIFICATION 1
+
 /* MCMC / ALS learner state (fm_learn_mcmc.h); ALS = mcmc without sampling / multilevel
  * (libfm.cpp:131-135). Draws come from the or_srand stream, as the reference's rand(). */
 typedef struct {
@@ -148,6 +158,13 @@ typedef struct {
 	double reg0;                    /* fm.reg0 (libfm.cpp:367-411) */
 	uint32_t nan_w, inf_w, nan_v, inf_v;
 	double *tmp_g;                  /* cache_for_group_values */
+	or_normal_fn normal_fn; void *normal_user;   /* NULL: or_ran_gaussian_ms */
+	int task;                       /* OR_TASK_*: fm_learn::task */
+	or_latent_fn latent_fn; void *latent_user;   /* NULL: ran_left / ran_right_tgaussian */
+	/* task c, the last iteration (fm_learn_mcmc_simultaneous.h:189-195, 262-270, 383-401);
+	 * pred_this / pred_sum_all then hold probabilities */
+	uint32_t n_train_correct, n_test_correct_this, n_test_correct_all;
+	double ll_this, ll_all;
 } or_als;
 
 int or_als_create(or_als *st, int k0, int k1, int k, uint32_t D, const uint32_t *attr_group);
@@ -157,8 +174,15 @@ double or_ran_gamma(double a);                 /* random.h:118-144 */
 double or_ran_gamma_ab(double a, double b);    /* random.h:146-148 */
 void or_als_init_params(or_als *st, uint32_t seed, double init_stdev); /* libfm.cpp:123,273,298 */
 int or_als_attach(or_als *st, const or_data *train, const or_data *test);
+/* task c writes 0 to the three values and its figures into the state */
 void or_als_iterate(or_als *st, const or_data *train, const or_data *test,
                     double *rmse_all, double *rmse_this, double *train_rmse);
+void or_als_set_task(or_als *st, int task);
+void or_als_set_normal_source(or_als *st, or_normal_fn fn, void *user);
+void or_als_set_latent_source(or_als *st, or_latent_fn fn, void *user);
+double or_cdf_gaussian(double x);                                       /* random.h:47-69 */
+double or_ran_left_tgaussian(double left, double mean, double stdev);   /* random.h:72-106 */
+double or_ran_right_tgaussian(double right, double mean, double stdev); /* random.h:108-114 */
 
 #ifdef __cplusplus
 }

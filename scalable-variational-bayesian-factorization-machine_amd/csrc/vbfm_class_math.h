@@ -78,11 +78,16 @@ VBFM_CM_FN uint64_t cm_splitmix64(uint64_t z)   // splitmix64 of vbfm_mc_math.h
 }
 
 // The device-mode draws of one row. Keying: (seed, stream, global row, attempt), where the stream
-// is CLASS_STREAM | iteration -- bit 63 is set in no stream of the attribute draws (those are
-// iteration * (k + 1) + factor) -- and the row is the index in the one-rank data set (a shard
-// adds its row offset), so the chain does not depend on the sharding. Attempt t of a row takes
-// the two 53-bit uniforms at counters 2t and 2t + 1 of the row's key.
+// is CLASS_STREAM | iteration, and the row is the index in the one-rank data set (a shard adds its
+// row offset), so the chain does not depend on the sharding. Attempt t of a row takes the two
+// 53-bit uniforms at counters 2t and 2t + 1 of the row's key.
+// Bits 63 and 62 of a stream id are reserved: the attribute draws of a sweep take stream
+// iteration * (k + 1) + factor (0 for w, f + 1 for v_f), which sets neither; bit 63 marks the row
+// draws, bit 62 the device-mode initialisation of fm.v (INIT_STREAM | 21) and fm.w (| 22). So no
+// two draws of one seed share a stream.
 constexpr uint64_t CLASS_STREAM = 1ull << 63;
+constexpr uint64_t INIT_STREAM = 1ull << 62;
+constexpr uint64_t INIT_STREAM_V = INIT_STREAM | 21, INIT_STREAM_W = INIT_STREAM | 22;
 
 struct RowKey {
 	uint64_t h;

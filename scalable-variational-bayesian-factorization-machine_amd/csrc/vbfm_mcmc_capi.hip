@@ -569,8 +569,9 @@ int vbfm_mcmc_init(vbfm_ctx *c, const vbfm_mcmc_config *cfg)
 			}
 			sync(c);
 		} else {
-			HIPCHK(vbk::init_normal_pairs(c->ms_v, kd, cfg->seed, 21, cfg->init_stdev, 0.0, c->s));
-			HIPCHK(vbk::init_normal_pairs(c->ms_w, c->D, cfg->seed, 22, cfg->init_stdev, 0.0, c->s));
+			// streams no sweep reaches: a sweep's id is iteration * (k + 1) + factor, below 2^62
+			HIPCHK(vbk::init_normal_pairs(c->ms_v, kd, cfg->seed, vbcm::INIT_STREAM_V, cfg->init_stdev, 0.0, c->s));
+			HIPCHK(vbk::init_normal_pairs(c->ms_w, c->D, cfg->seed, vbcm::INIT_STREAM_W, cfg->init_stdev, 0.0, c->s));
 			sync(c);
 		}
 		c->q_ready[0] = c->q_ready[1] = -1;

@@ -5,6 +5,9 @@
 //   sampler SEED                moments of the keyed (device-mode) sampler at five means, both sides
 //   edge                        non-finite yhat, and the fallback with the attempt cap forced to 0
 //   glibc SEED MU               1000 left_tgaussian(0, MU, 1) draws, the uniforms they came from
+//   streams                     the reserved stream ids: CLASS_STREAM, INIT_STREAM_V, INIT_STREAM_W
+//   draws SEED STREAM ROW0 N    stdin: N "yhat side" pairs, then "stream j" pairs to the end; prints
+//                               "s attempts flag" of row ROW0 + i per pair, then a normal per pair
 #include "../scalable-variational-bayesian-factorization-machine_amd/csrc/vbfm_class_math.h"
 #include "../scalable-variational-bayesian-factorization-machine_amd/csrc/vbfm_rng.h"
 
@@ -85,12 +88,45 @@ static int glibc(uint32_t seed, double mu)
 	return 0;
 }
 
+// device_normal of csrc/vbfm_mc_math.h:21-27 (a HIP-only header: DEVI, McArgs), its three lines copied
+static double device_normal(uint64_t seed, uint64_t stream, uint64_t j)
+{
+	const uint64_t base = seed * 0x9E3779B97F4A7C15ull + stream * 0xD1B54A32D192ED03ull + 2 * j;
+	const double u1 = ((double)(vbcm::cm_splitmix64(base) >> 11) + 1.0) * 0x1p-53;
+	const double u2 = (double)(vbcm::cm_splitmix64(base + 1) >> 11) * 0x1p-53;
+	return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
+static int draws(uint64_t seed, uint64_t stream, uint64_t row0, long n)
+{
+	for (long i = 0; i < n; i++) {
+		double yhat;
+		int side;
+		if (scanf("%lf %d", &yhat, &side) != 2) return 3;
+		const vbcm::RowKey key(seed, stream, row0 + (uint64_t)i);
+		int a = 0, flag = -1;
+		const double s = vbcm::class_sample_target(yhat, side > 0, key, vbcm::CLASS_MAX_ATTEMPTS, &a, &flag);
+		printf("%.17g %d %d\n", s, a, flag);
+	}
+	unsigned long long st, j;
+	while (scanf("%llu %llu", &st, &j) == 2) printf("%.17g\n", device_normal(seed, st, j));
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	if (argc >= 2 && !strcmp(argv[1], "grid")) return grid();
 	if (argc >= 3 && !strcmp(argv[1], "sampler")) return sampler(strtoull(argv[2], nullptr, 10));
 	if (argc >= 2 && !strcmp(argv[1], "edge")) return edge();
 	if (argc >= 4 && !strcmp(argv[1], "glibc")) return glibc((uint32_t)strtoul(argv[2], nullptr, 10), atof(argv[3]));
-	fprintf(stderr, "usage: class_math_check grid | sampler SEED | edge | glibc SEED MU\n");
+	if (argc >= 2 && !strcmp(argv[1], "streams")) {
+		printf("%llu %llu %llu\n", (unsigned long long)vbcm::CLASS_STREAM, (unsigned long long)vbcm::INIT_STREAM_V,
+		       (unsigned long long)vbcm::INIT_STREAM_W);
+		return 0;
+	}
+	if (argc >= 6 && !strcmp(argv[1], "draws"))
+		return draws(strtoull(argv[2], nullptr, 10), strtoull(argv[3], nullptr, 10), strtoull(argv[4], nullptr, 10),
+		             atol(argv[5]));
+	fprintf(stderr, "usage: class_math_check grid | sampler SEED | edge | glibc SEED MU | streams | draws SEED STREAM ROW0 N\n");
 	return 2;
 }

@@ -47,7 +47,11 @@ class OrALS(C.Structure):
                 ("min_target", C.c_float), ("max_target", C.c_float), ("iter_done", C.c_uint32),
                 ("do_sample", C.c_int), ("do_multilevel", C.c_int), ("reg0", C.c_double),
                 ("nan_w", C.c_uint32), ("inf_w", C.c_uint32), ("nan_v", C.c_uint32), ("inf_v", C.c_uint32),
-                ("tmp_g", P_f64)]
+                ("tmp_g", P_f64),
+                ("normal_fn", C.c_void_p), ("normal_user", C.c_void_p), ("task", C.c_int),
+                ("latent_fn", C.c_void_p), ("latent_user", C.c_void_p),
+                ("n_train_correct", C.c_uint32), ("n_test_correct_this", C.c_uint32),
+                ("n_test_correct_all", C.c_uint32), ("ll_this", C.c_double), ("ll_all", C.c_double)]
 
 
 class OrOVB(C.Structure):
@@ -62,6 +66,8 @@ class OrOVB(C.Structure):
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(None, P_f64, C.c_int, C.c_void_p)
+NORMAL_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32)
+LATENT_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_int)
 
 _lib = None
 
@@ -103,6 +109,11 @@ def lib():
                                      P_f64, P_f64, P_f64]
         L.or_als_destroy.argtypes = [C.POINTER(OrALS)]
         L.or_als_configure.argtypes = [C.POINTER(OrALS), C.c_int, C.c_int, C.c_double]
+        L.or_als_set_task.argtypes = [C.POINTER(OrALS), C.c_int]
+        L.or_als_set_normal_source.argtypes = [C.POINTER(OrALS), NORMAL_FN, C.c_void_p]
+        L.or_als_set_latent_source.argtypes = [C.POINTER(OrALS), LATENT_FN, C.c_void_p]
+        L.or_cdf_gaussian.argtypes = [C.c_double]
+        L.or_cdf_gaussian.restype = C.c_double
         L.or_ovb_create.argtypes = [C.POINTER(OrOVB), C.c_int, C.c_int, C.c_int, C.c_uint32, P_u32, C.c_uint32]
         L.or_ovb_destroy.argtypes = [C.POINTER(OrOVB)]
         L.or_ovb_init.argtypes = [C.POINTER(OrOVB), C.c_uint32, C.c_double, C.POINTER(OrData), C.POINTER(OrData)]
@@ -220,13 +231,15 @@ class VB:
 class ALS:
     """fm_learn_mcmc: method "als" (no sampling, no hyper-prior inference) or "mcmc"."""
 
-    def __init__(self, k0, k1, k, D, attr_group=None, method="als", reg0=0.0):
+    def __init__(self, k0, k1, k, D, attr_group=None, method="als", reg0=0.0, task="r"):
         self.s = OrALS()
         self._groups = None if attr_group is None else np.ascontiguousarray(attr_group, dtype=np.uint32)
         gp = None if self._groups is None else self._groups.ctypes.data_as(P_u32)
         lib().or_als_create(C.byref(self.s), int(k0), int(k1), int(k), int(D), gp)
         mc = method == "mcmc"
         lib().or_als_configure(C.byref(self.s), int(mc), int(mc), float(reg0))
+        lib().or_als_set_task(C.byref(self.s), 1 if task == "c" else 0)
+        self._normal_cb = self._latent_cb = None
 
     def set_lambda(self, w_lambda, v_lambda):
         """-regular (libfm.cpp:367-411): w_lambda[G], v_lambda[G*k] at [g*k + f]"""
@@ -248,6 +261,66 @@ class ALS:
         lib().or_als_iterate(C.byref(self.s), C.byref(self.train.d), C.byref(self.test.d),
                              C.byref(a), C.byref(t), C.byref(tr))
         return a.value, t.value, tr.value
+
+    def seed(self, seed):
+        """srand(seed) alone: VBFM_RNG_DEVICE takes no initialisation draw from the stream."""
+        lib().or_srand(seed)
+
+    def set_params(self, p):
+        """w [D], v [k*D] ([f][j]), the hyper-priors, w0 and alpha, where given."""
+        s = self.s
+        for key in ("w", "v", "w_mu", "w_lambda", "v_mu", "v_lambda"):
+            if key in p:
+                a = np.ascontiguousarray(p[key], dtype=np.float64).ravel()
+                C.memmove(getattr(s, key), a.ctypes.data, a.nbytes)
+        if "w0" in p:
+            s.w0 = float(p["w0"])
+        if "alpha" in p:
+            s.alpha = float(p["alpha"])
+
+    def set_normal_source(self, fn):
+        """fn(iter, f, D) -> the D standard normals of sweep f (-1: draw_w) of iteration iter, in
+        place of the or_srand stream's (or_normal_fn); asked once per sweep."""
+        cache = {}
+
+        def cb(_user, it, f, j):
+            if cache.get("key") != (it, f):
+                cache["key"], cache["z"] = (it, f), np.asarray(fn(it, f, self.s.D), dtype=np.float64)
+            return float(cache["z"][j])
+        self._normal_cb = NORMAL_FN(cb)
+        lib().or_als_set_normal_source(C.byref(self.s), self._normal_cb, None)
+
+    def set_latent_source(self, fn):
+        """fn(iter, yhat[n_train], positive[n_train]) -> the latent targets of task c's row step
+        (or_latent_fn). Asked once per iteration, at row 0, when e still holds every row's yhat."""
+        cache = {}
+
+        def cb(_user, it, row, yhat, positive):
+            if row == 0:
+                yh = arr(self.s.e, self.s.n_train)
+                pos = arr(self.train.d.target, self.s.n_train, np.float32) >= 0
+                cache["s"] = np.asarray(fn(it, yh, pos), dtype=np.float64)
+                cache["yhat"], cache["pos"] = yh, pos
+            assert cache["yhat"][row] == yhat and bool(cache["pos"][row]) == bool(positive)
+            return float(cache["s"][row])
+        self._latent_cb = LATENT_FN(cb)
+        lib().or_als_set_latent_source(C.byref(self.s), self._latent_cb, None)
+
+    def rows(self):
+        return {"e": arr(self.s.e, self.s.n_train)}
+
+    def class_info(self):
+        s = self.s
+        return {"n_train_correct": s.n_train_correct, "n_test_correct_this": s.n_test_correct_this,
+                "n_test_correct_all": s.n_test_correct_all, "ll_this": s.ll_this, "ll_all": s.ll_all}
+
+    def predict(self):
+        """fm_learn_mcmc::predict (fm_learn_mcmc.h:355-381): the mean over the iterations when
+        sampling, else the last iteration's; clipped to the target range ([0, 1] in task c)."""
+        s = self.s
+        p = arr(s.pred_sum_all, s.n_test) / s.iter_done if s.do_sample else arr(s.pred_this, s.n_test)
+        lo, hi = (0.0, 1.0) if s.task == 1 else (s.min_target, s.max_target)
+        return np.maximum(lo, np.minimum(hi, p))
 
     def params(self):
         s = self.s
