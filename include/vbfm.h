@@ -676,7 +676,8 @@ int vbfm_score_device(vbfm_model *m, vbfm_ctx *ctx, int32_t which, const vbfm_sc
  * the launch geometry. var is 0 for S = 1. With every iteration of a run kept, scoring the attached
  * test rows reproduces vbfm_mcmc_get_test_pred bit for bit. The predictive variance of y in regression
  * is var + mean_s(1 / alpha_s); the addition is the caller's (vbfm_model_draw_scalars has the alphas).
- * vbfm_candidates_create / vbfm_recommend refuse a chain model.
+ * vbfm_candidates_create / vbfm_recommend refuse a chain model ("ranking a chain of draws" below has the
+ * entry points that take one).
  *
  * vbfm_chain_create: capacity draws of ctx's shape on ctx's device; only a sampling MCMC context
  * (vbfm_mcmc_config::do_sample = 1) is accepted -- ALS is deterministic, a chain of it is one point.
@@ -796,6 +797,63 @@ typedef struct {
 int vbfm_recommend_ucb(vbfm_model *m, const vbfm_candidates *c, const vbfm_csr *contexts, const uint64_t *excl_ptr,
                        const uint32_t *excl_idx, const vbfm_recommend_ucb_opts *o, int32_t *idx, double *key,
                        double *score, double *var, uint32_t *count, vbfm_recommend_stats *st);
+
+/* ---- ranking a chain of draws (additive to ABI 4: new functions and structs only) -------------------
+ * Top-N from a VBFM_MODEL_MCMC_CHAIN model: the pairs ranked on the mean over the S draws of the pair's
+ * raw value -- what the MCMC learner reports, before the link -- plus beta times its spread across the
+ * draws. Every other entry point above goes on refusing a chain model; these two refuse every other
+ * kind (the message names it and points to vbfm_candidates_create / vbfm_recommend). For context row c,
+ * candidate row j and draw s = 0 .. S - 1, in the order the draws were added:
+ *     dot_s = 0;  for f = 0 .. k - 1:  dot_s = fma(Q_{c,s}[f], Q_{j,s}[f], dot_s)
+ *     raw_s = ((base_{c,s} + base_{j,s}) - (k0 ? w0_s : 0)) + dot_s
+ * base_{r,s} is the unclipped yhat_s of row r alone as the chain scorer forms it in group order (bit for
+ * bit vbfm_score(clip = 0, VBFM_ORDER_GROUP) of a MCMC_DRAW model holding draw s), Q_{r,s}[f] that
+ * scorer's per-factor sum (entries in ascending id); so raw_s is bit for bit what vbfm_recommend returns
+ * with clip = 0 for the one-draw model of draw s. The moments are shifted by raw_0 and formed in draw
+ * order, every operation rounded on its own; invS = 1.0 / S is rounded once on the host:
+ *     a = 0;  b = 0;  for s = 1 .. S - 1:  d = raw_s - raw_0;  a = a + d;  b = fma(d, d, b)
+ *     am   = a * invS
+ *     mean = raw_0 + am
+ *     var  = max((b - a * am) * invS, 0)
+ *     sd   = sqrt(var + (noise ? na : 0))
+ *     key  = fma(beta, sd, mean)
+ * na is the mean over the draws of 1 / alpha_s: summed in draw order, then divided by S, once on the
+ * host. Every pair is formed by exactly these expressions, whatever tile, slice or chunk it falls in,
+ * and the ranking is the total order on key (larger first, equal keys by smaller candidate index), so
+ * idx, key, score, var and count are bit-identical whatever the chunk size and the launch geometry. A
+ * pair whose mean, var or key is not finite is never returned and is counted in nonfinite_pairs (a
+ * non-finite raw_s of any draw makes a, and so mean, non-finite). S = 1, or S identical draws: a = 0,
+ * mean = raw_0, var = 0, and with noise = 0 key is raw_0: vbfm_recommend's results of that draw, bit
+ * for bit. Returned for each survivor, best first: idx; key; var (the spread of the raw values,
+ * without the noise term); score = mean with clip = 0, and with clip = 1 what vbfm_score returns for
+ * the chain on the pair's row ("chains of draws" above): sum = sum + p_s in draw order with
+ * p_s = clip(raw_s, min_target, max_target), task c Phi(raw_s); then sum / S; then the min / max to the
+ * target range, task c [0, 1]. The ranking is always on the raw mean (ranking on clipped values would
+ * tie every saturated pair). beta is any finite double; beta = 0 with noise = 0 ranks on the chain
+ * mean; noise = 1 is refused for a model of task c. Limits as vbfm_recommend.
+ *
+ * vbfm_candidates_create_chain makes the set vbfm_recommend_chain takes (it refuses any other, and
+ * vbfm_recommend / vbfm_recommend_ucb refuse this one): every draw's sums and bases, S * (k + 1) *
+ * Mpad * 8 bytes with Mpad the candidate count rounded up to 128, checked against the free memory
+ * before anything is allocated; the refusal names both figures. vbfm_candidates_count and
+ * vbfm_candidates_destroy serve it too. A chunk of context rows also holds its prepared sums,
+ * S * (k + 1) * 8 bytes a row, so vbfm_recommend_chain cuts the contexts so that staged rows plus those
+ * fit chunk_bytes (at least 8 rows a chunk while there are that many; a larger row is a chunk by
+ * itself). */
+int vbfm_candidates_create_chain(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids);
+typedef struct {
+	int32_t topn;          /* the four fields of vbfm_recommend_opts */
+	int32_t clip;
+	int32_t unknown_ids;
+	uint64_t chunk_bytes;
+	double beta;           /* finite */
+	int32_t noise;         /* 1: sd is of y (var + the draws' mean of 1 / alpha), 0: of the raw value across the draws */
+} vbfm_recommend_chain_opts;
+/* contexts, exclusions, idx, count and the stats as vbfm_recommend; key, score, var [B * topn] (NaN
+ * beyond count), each may be NULL. */
+int vbfm_recommend_chain(vbfm_model *m, const vbfm_candidates *c, const vbfm_csr *contexts, const uint64_t *excl_ptr,
+                         const uint32_t *excl_idx, const vbfm_recommend_chain_opts *o, int32_t *idx, double *key,
+                         double *score, double *var, uint32_t *count, vbfm_recommend_stats *st);
 
 #ifdef __cplusplus
 }

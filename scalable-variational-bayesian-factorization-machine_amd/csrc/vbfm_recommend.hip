@@ -13,7 +13,10 @@
 // row's per-factor sums), k_rec_pairs (the hot path) and k_rec_merge (the slices' lists into one).
 // Ranking by mean + beta * sd (vbfm_recommend_ucb) adds the variance term of the merged
 // row by the same algebra: k_score<.., VAR, QOUT>, k_ucb_pairs, the same merge, k_ucb_finish. Both
-// calls are one host pipeline (rank_call) under two descriptions (Ranking).
+// calls are one host pipeline (rank_call) under two descriptions (Ranking). Ranking a chain of draws
+// (vbfm_recommend_chain) is a third: k_chain_prepare stores every draw's base and sums,
+// k_chain_pairs loops over the draws with the moments of a pair's raw values in registers, the same
+// merge, k_chain_finish.
 #include "vbfm_score.h"
 #include "vbfm_class_math.h"
 
@@ -40,6 +43,7 @@ namespace {
 
 struct PairArgs {
 	uint32_t nB;              // contexts of the launch
+	uint32_t rows_pad;        // rows the context-side arrays were allocated for (a chain's base_c is [s][rows_pad])
 	uint32_t M, Mpad;         // candidates; rounded up to REC_STEP
 	int k;
 	double w0;                // k0 ? w0 : 0
@@ -557,6 +561,325 @@ hipError_t launch_ucb_pairs(uint32_t ctx, const PairPtrs &p, const PairArgs &a, 
 	return hipGetLastError();
 }
 
+// ---- ranking a chain of draws (include/vbfm.h "ranking a chain of draws") -------------
+// A pair has one raw per draw; the kernel keeps raw_0 and the moments of raw_s - raw_0 in registers
+// and ranks on mean + beta * sd of the S values. A wave owns CHAIN_CTX contexts: a pair's persistent
+// state is three doubles (raw_0, a, b) beside the dot of the draw at hand, so the block of
+// CHAIN_CTX x REC_CJ pairs is 128 VGPRs; the 16-context form would need 256 for the block alone, all
+// the architectural VGPRs a wave has, and is not compiled.
+#define CHAIN_CTX 8
+#define CHAIN_WAVES 4
+#define CHAIN_TILE_B (CHAIN_CTX * CHAIN_WAVES)
+
+struct ChainRank {
+	uint32_t S;
+	double invS;    // 1.0 / S, rounded once on the host
+	double na;      // noise ? mean over the draws of 1 / alpha_s : 0
+	double beta;
+	int link;       // the finish kernel's p_s: 0 raw_s, 1 its clip to [mn, mx], 2 Phi(raw_s)
+	int fin;        // the returned score is the mean of p_s clamped to [lo, hi] (else the raw mean)
+	double mn, mx, lo, hi;
+};
+
+struct ChainVal {
+	double mean, var, key;
+	bool ok;        // mean, var and key are finite
+};
+
+// THE expressions of a pair's moments (include/vbfm.h): over the draws in order, from raw_0 and
+// d = raw_s - raw_0. The pair kernel ranks on them and k_chain_finish forms the survivors' values
+// with them.
+DEVI void chain_add(double &raw0, double &sa, double &sb, double raw, bool first)
+{
+	if (first) {
+		raw0 = raw; sa = 0.0; sb = 0.0;
+	} else {
+		const double d = raw - raw0;
+		sa = sa + d;
+		sb = __builtin_fma(d, d, sb);
+	}
+}
+
+DEVI ChainVal chain_val(double raw0, double sa, double sb, const ChainRank &u)
+{
+	ChainVal v;
+	const double am = sa * u.invS;
+	v.mean = raw0 + am;
+	v.var = __builtin_fmax((sb - sa * am) * u.invS, 0.0);
+	const double sd = __builtin_sqrt(v.var + u.na);
+	v.key = __builtin_fma(u.beta, sd, v.mean);
+	v.ok = __builtin_isfinite(v.mean) && __builtin_isfinite(v.var) && __builtin_isfinite(v.key);
+	return v;
+}
+
+struct ChainPrepArgs {
+	ScoreArgs a;                  // the rows, the model's shape, the flags; q / q_tile as QOUT (a tile is [S][k][q_tile])
+	const double *cw, *cv, *w0;   // the chain model's interleaved tables (vbfm_chain.hip)
+	uint32_t S;
+	double *base;                 // yhat_s of row r to base[s * base_stride + r]
+	uint32_t base_stride;
+};
+
+// The preparation: k_score<G, KP, false, QOUT>'s body -- a group of G lanes, factor f on lane f % G,
+// the same expressions, entry order and butterfly -- on draw s's slice of the interleaved tables, one
+// group per (row, draw), the draws of a row on adjacent groups (their gathers of one entry are
+// adjacent in cv). That is k_score_chain's yhat_s before link and reduction, and the bits a
+// MCMC_DRAW model of draw s gives vbfm_recommend. Unknown ids are flagged by draw 0's group only.
+template <int G, int KP>
+__global__ __launch_bounds__(256) void k_chain_prepare(const ChainPrepArgs c)
+{
+	static_assert(KP == 1 || G == 64, "several passes only with whole waves");
+	const ScoreArgs &a = c.a;
+	const uint32_t lane = threadIdx.x & 63, gl = lane & (G - 1), gbase = lane & ~(uint32_t)(G - 1);
+	const uint64_t ngroups = (uint64_t)gridDim.x * (256u / G), items = (uint64_t)a.n * c.S;
+	const int k = a.k;
+	const uint32_t D = a.D;
+	const size_t S = c.S;
+	for (uint64_t it = ((uint64_t)blockIdx.x * 256u + threadIdx.x) / G; it < items; it += ngroups) {
+		const uint32_t r = (uint32_t)(it / S), s = (uint32_t)(it % S);
+		const uint64_t b = a.row_ptr[r] - a.ent_base, en = a.row_ptr[r + 1] - a.ent_base;
+		double qe[KP];
+#pragma unroll
+		for (int cc = 0; cc < KP; ++cc) qe[cc] = 0.0;
+		double qqe = 0.0;
+		constexpr int PU = score_pu(KP);
+		for (uint64_t p0 = b; p0 < en; p0 += G) {
+			const uint32_t cnt = (uint32_t)min<uint64_t>(G, en - p0);
+			const uint2 mine = gl < cnt ? a.ent[p0 + gl] : make_uint2(0u, 0u);
+			const bool unknown = gl < cnt && mine.x >= D;
+			if (unknown && s == 0) flag_unknown(a, r, mine.x);
+			const uint64_t okm = __ballot(!unknown) >> gbase;   // bit i: entry i of this step is in the model
+			if (k <= 0) continue;
+			for (uint32_t i0 = 0; i0 < cnt; i0 += PU) {
+				double vm[PU][KP];
+				float xs[PU];
+				bool ok[PU];
+#pragma unroll
+				for (int u = 0; u < PU; ++u) {
+					const int i = (int)min(i0 + u, cnt - 1);
+					const uint32_t j = __shfl(mine.x, i, G);
+					xs[u] = __uint_as_float(__shfl(mine.y, i, G));
+					ok[u] = i0 + u < cnt && ((okm >> i) & 1);
+#pragma unroll
+					for (int cc = 0; cc < KP; ++cc) {
+						const int f = (int)gl + 64 * cc;
+						vm[u][cc] = 0.0;
+						if (f < k && ok[u]) vm[u][cc] = c.cv[((size_t)j * S + s) * k + f];
+					}
+				}
+#pragma unroll
+				for (int u = 0; u < PU; ++u) {
+					if (i0 + u >= cnt) break;
+					if (!ok[u]) continue;
+					const float x = xs[u];
+#pragma unroll
+					for (int cc = 0; cc < KP; ++cc)
+						if ((int)gl + 64 * cc < k) {
+							const double m = vm[u][cc];
+							qe[cc] += m * x;                           // fm_learn_vb.h:93-133
+							qqe -= 0.5 * m * m * x * x;                // :136-163
+						}
+				}
+			}
+		}
+		const size_t qbase = ((size_t)(r / a.q_tile) * S + s) * k * a.q_tile + r % a.q_tile;
+#pragma unroll
+		for (int cc = 0; cc < KP; ++cc)
+			if ((int)gl + 64 * cc < k) a.q[qbase + (size_t)((int)gl + 64 * cc) * a.q_tile] = qe[cc];
+		double e = 0.0;
+#pragma unroll
+		for (int cc = 0; cc < KP; ++cc)
+			if ((int)gl + 64 * cc < k) e += 0.5 * qe[cc] * qe[cc];
+		e = group_sum<G>(e);
+		qqe = group_sum<G>(qqe);
+		if (a.k1) {                                             // :166-188
+			for (uint64_t p0 = b; p0 < en; p0 += G) {
+				const uint32_t cnt = (uint32_t)min<uint64_t>(G, en - p0);
+				double pe = 0.0;
+				bool known = false;
+				if (gl < cnt) {
+					const uint2 ent = a.ent[p0 + gl];
+					known = ent.x < D;
+					if (known) pe = c.cw[(size_t)ent.x * S + s] * ent_x(ent);
+				}
+				const uint64_t okm = __ballot(known) >> gbase;
+				for (uint32_t i = 0; i < cnt; ++i) {
+					const double ve = __shfl(pe, (int)i, G);
+					if ((okm >> i) & 1) qqe += ve;
+				}
+			}
+		}
+		e = e + qqe;
+		if (a.k0) e += c.w0[s];
+		if (gl == 0) c.base[(size_t)s * c.base_stride + r] = e;
+	}
+}
+
+template <int G, int KP> hipError_t launch_chain_prepare_g(const ChainPrepArgs &c, hipStream_t s)
+{
+	const uint64_t per = 256u / G, items = (uint64_t)c.a.n * c.S;
+	k_chain_prepare<G, KP><<<(unsigned)std::min<uint64_t>((items + per - 1) / per, 16384), 256, 0, s>>>(c);
+	return hipGetLastError();
+}
+
+// k_rec_pairs with the draws as an outer loop. Grid (context tiles of CTX * WAVES, candidate slices); a
+// wave's lists (ordered by key) are its own, no barrier, no atomics in the loops. The context side is
+// wave-uniform: ctx_all is the preparation's [tile of CTX][s][f][CTX], base_c [s][rows_pad] and w0s
+// [S] (zeros without k0), read by scalar loads through plain restrict parameters; a lane loads its
+// REC_CJ candidates' sums of (s, f) (coalesced, [s][f][Mpad]). The f loop is k_rec_pairs' FMA block;
+// after it every pair takes raw_s into raw_0 / a / b (chain_add). Nothing reaches memory unless it survives.
+template <int CAP, int WAVES, int CTX>
+__global__ __launch_bounds__(64 * WAVES) void k_chain_pairs(const double *__restrict__ ctx_all, const double *__restrict__ qt,
+                                                            const double *__restrict__ base_c, const double *__restrict__ base_j,
+                                                            const double *__restrict__ w0s, const PairArgs a, const ChainRank u)
+{
+	__shared__ double s_key[WAVES][CTX][CAP];
+	__shared__ uint32_t s_idx[WAVES][CTX][CAP];
+	__shared__ uint32_t s_cnt[WAVES][CTX];
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+	const uint32_t tile = blockIdx.x * WAVES + wave;
+	const uint32_t c0 = tile * CTX;
+	if (c0 >= a.nB) return;
+	const int nctx = (int)min((uint32_t)CTX, a.nB - c0);
+	const int k = a.k, topn = a.topn;
+	const uint32_t S = u.S;
+	const uint32_t slice = blockIdx.y;
+	const uint32_t jb = (uint32_t)min((uint64_t)a.M, (uint64_t)slice * a.slice_len);
+	const uint32_t je = (uint32_t)min((uint64_t)a.M, (uint64_t)jb + a.slice_len);
+	if (lane < CTX) {
+		s_cnt[wave][lane] = 0;
+		s_key[wave][lane][topn - 1] = -INFINITY;
+		s_idx[wave][lane][topn - 1] = 0xffffffffu;
+	}
+	wave_sync();
+	const double *__restrict__ qc = ctx_all + (size_t)tile * S * k * CTX;
+	uint32_t nonfinite = 0, exhits = 0;
+	for (uint32_t j0 = jb; j0 < je; j0 += REC_STEP) {   // at most slice_len / REC_STEP steps
+		double raw0[REC_CJ][CTX], sa[REC_CJ][CTX], sb[REC_CJ][CTX];
+		const size_t at = (size_t)j0 + lane;   // j0 + 127 < Mpad: Mpad % REC_STEP == 0
+#pragma unroll 1
+		for (uint32_t s = 0; s < S; ++s) {
+			double dot[REC_CJ][CTX];
+#pragma unroll
+			for (int v = 0; v < REC_CJ; ++v)
+#pragma unroll
+				for (int i = 0; i < CTX; ++i) dot[v][i] = 0.0;
+			const double *__restrict__ qj = qt + (size_t)s * k * a.Mpad + at;
+			const double *__restrict__ cs = qc + (size_t)s * k * CTX;
+#pragma unroll 2
+			for (int f = 0; f < k; ++f) {
+				const double v0 = qj[(size_t)f * a.Mpad], v1 = qj[(size_t)f * a.Mpad + 64];
+				const double *__restrict__ c = cs + (size_t)f * CTX;
+#pragma unroll
+				for (int i = 0; i < CTX; ++i) {
+					const double ci = c[i];
+					dot[0][i] = __builtin_fma(ci, v0, dot[0][i]);
+					dot[1][i] = __builtin_fma(ci, v1, dot[1][i]);
+				}
+			}
+			const double bj0 = base_j[(size_t)s * a.Mpad + at], bj1 = base_j[(size_t)s * a.Mpad + at + 64];
+			const double w0 = w0s[s];
+			const double *__restrict__ bcs = base_c + (size_t)s * a.rows_pad + c0;   // c0 + CTX <= rows_pad
+			const bool first = s == 0;
+#pragma unroll
+			for (int i = 0; i < CTX; ++i) {
+				const double bc = bcs[i];
+				chain_add(raw0[0][i], sa[0][i], sb[0][i], rec_raw(bc, bj0, w0, dot[0][i]), first);
+				chain_add(raw0[1][i], sa[1][i], sb[1][i], rec_raw(bc, bj1, w0, dot[1][i]), first);
+			}
+		}
+		const bool in0 = j0 + lane < je, in1 = j0 + 64 + lane < je;
+#pragma unroll
+		for (int i = 0; i < CTX; ++i) {
+			if (i < nctx) {
+				const double tr = s_key[wave][i][topn - 1];
+				const uint32_t ti = s_idx[wave][i][topn - 1];
+				const ChainVal v0 = chain_val(raw0[0][i], sa[0][i], sb[0][i], u);
+				const ChainVal v1 = chain_val(raw0[1][i], sa[1][i], sb[1][i], u);
+				// a pair that is not ok carries a NaN key: rec_insert drops what is not finite
+				const double r[REC_CJ] = {v0.ok ? v0.key : __builtin_nan(""), v1.ok ? v1.key : __builtin_nan("")};
+				nonfinite += (uint32_t)__popcll(__ballot(in0 && !v0.ok)) + (uint32_t)__popcll(__ballot(in1 && !v1.ok));
+				const bool s0 = in0 && v0.ok && rec_better(r[0], j0 + lane, tr, ti);
+				const bool s1 = in1 && v1.ok && rec_better(r[1], j0 + 64 + lane, tr, ti);
+				if (__ballot(s0 || s1))
+					rec_insert<CAP>(a, s_key[wave][i], s_idx[wave][i], &s_cnt[wave][i], c0 + i, r, j0, je, lane, exhits);
+			}
+		}
+	}
+	wave_sync();
+	for (int i = 0; i < nctx; ++i) {
+		const uint32_t n = s_cnt[wave][i];
+		const size_t list = (size_t)(c0 + i) * a.slices + slice;
+		for (uint32_t e = lane; e < n; e += 64) {
+			a.part_raw[list * topn + e] = s_key[wave][i][e];
+			a.part_idx[list * topn + e] = s_idx[wave][i][e];
+		}
+		if (lane == 0) a.part_cnt[list] = n;
+	}
+	if (lane == 0) {
+		if (nonfinite) atomicAdd(&a.counters[0], (unsigned long long)nonfinite);
+		if (exhits) atomicAdd(&a.counters[1], (unsigned long long)exhits);
+	}
+}
+
+struct ChainFinishArgs {
+	const double *ctx_all;        // [tile of CHAIN_CTX][s][f][CHAIN_CTX]
+	const double *qt, *base_c, *base_j, *w0s;
+	uint32_t nB, rows_pad, Mpad;
+	int k, topn;
+	ChainRank u;
+	const int32_t *idx;           // [nB][topn] and [nB]: the merge's results
+	const uint32_t *count;
+	double *key, *score, *var;    // [nB][topn], NaN beyond count
+};
+
+// After the merge: one thread per returned entry forms the survivor's S raw_s again -- the same sums
+// in the same order through rec_raw, chain_add and chain_val, so the bits the pair kernel ranked on --
+// and beside them the returned score: the mean, or with clip = 1 vbfm_score's mean over the draws of
+// the linked per-draw values (the only place that needs Phi).
+__global__ __launch_bounds__(256) void k_chain_finish(const ChainFinishArgs a)
+{
+	const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (p >= (uint64_t)a.nB * a.topn) return;
+	const uint32_t c = (uint32_t)(p / a.topn), e = (uint32_t)(p % a.topn);
+	if (e >= a.count[c]) {
+		a.key[p] = a.score[p] = a.var[p] = __builtin_nan("");
+		return;
+	}
+	const uint32_t j = (uint32_t)a.idx[p], S = a.u.S;
+	const int k = a.k;
+	const double *qc = a.ctx_all + (size_t)(c / CHAIN_CTX) * S * k * CHAIN_CTX + c % CHAIN_CTX;
+	double raw0 = 0.0, sa = 0.0, sb = 0.0, sum = 0.0;
+	for (uint32_t s = 0; s < S; ++s) {
+		const double *qs = qc + (size_t)s * k * CHAIN_CTX, *qj = a.qt + (size_t)s * k * a.Mpad + j;
+		double dot = 0.0;
+		for (int f = 0; f < k; ++f) dot = __builtin_fma(qs[(size_t)f * CHAIN_CTX], qj[(size_t)f * a.Mpad], dot);
+		const double raw = rec_raw(a.base_c[(size_t)s * a.rows_pad + c], a.base_j[(size_t)s * a.Mpad + j], a.w0s[s], dot);
+		chain_add(raw0, sa, sb, raw, s == 0);
+		sum = sum + (a.u.link == 1 ? clip(raw, a.u.mn, a.u.mx) : (a.u.link == 2 ? vbcm::Phi(raw) : raw));
+	}
+	const ChainVal v = chain_val(raw0, sa, sb, a.u);
+	const double avg = sum / (double)S;
+	a.key[p] = v.key;
+	a.score[p] = a.u.fin ? clip(avg, a.u.lo, a.u.hi) : v.mean;
+	a.var[p] = v.var;
+}
+
+// capacities as launch_pairs; the lists of CHAIN_CTX contexts fit four waves at every capacity
+hipError_t launch_chain_pairs(const PairPtrs &p, const double *w0s, const PairArgs &a, const ChainRank &u, hipStream_t s)
+{
+	if (a.nB == 0) return hipSuccess;
+	const uint32_t waves = (a.nB + CHAIN_CTX - 1) / CHAIN_CTX;
+	const dim3 grid((waves + CHAIN_WAVES - 1) / CHAIN_WAVES, a.slices);
+#define CHAIN_LAUNCH(CAP) \
+	k_chain_pairs<CAP, CHAIN_WAVES, CHAIN_CTX><<<grid, 64 * CHAIN_WAVES, 0, s>>>(p.ctx_all, p.qt, p.base_c, p.base_j, w0s, a, u)
+	if (a.topn <= 16) CHAIN_LAUNCH(16);
+	else if (a.topn <= 64) CHAIN_LAUNCH(64);
+	else CHAIN_LAUNCH(VBFM_REC_MAX_TOPN);
+#undef CHAIN_LAUNCH
+	return hipGetLastError();
+}
+
 uint32_t round_up(uint64_t v, uint32_t to) { return (uint32_t)((v + to - 1) / to * to); }
 
 // Candidate slices of a launch over nB contexts: enough waves to fill the chip when contexts are few
@@ -593,6 +916,34 @@ void launch_prepare(vbfm_model *m, const uint8_t *d_in, uint32_t nr, uint64_t e0
 	a.q_tile = q_tile;
 	if (!nr) return;
 	HIPCHK(tb ? (launch_group<true, true>(a, 0, m->s)) : (launch_group<false, true>(a, 0, m->s)));
+}
+
+// The same for a chain model: every draw's base (base[s * base_stride + r]) and per-factor sums (q in
+// tiles of [S][k][q_tile]) by k_chain_prepare, with the group width launch_group picks.
+void launch_prepare_chain(vbfm_model *m, const uint8_t *d_in, uint32_t nr, uint64_t e0, uint32_t r0, double *base,
+                          uint32_t base_stride, double *q, uint32_t q_tile)
+{
+	if (!nr) return;
+	ChainPrepArgs c = {};
+	c.a = score_args(m, 0);
+	c.a.row_ptr = (const uint64_t *)d_in;
+	c.a.ent = (const uint2 *)(d_in + ((size_t)nr + 1) * 8);
+	c.a.ent_base = e0;
+	c.a.n = nr;
+	c.a.row0 = r0;
+	c.a.q = q;
+	c.a.q_tile = q_tile;
+	c.cw = m->cw; c.cv = m->cv; c.w0 = m->cw0;
+	c.S = m->S;
+	c.base = base;
+	c.base_stride = base_stride;
+	const int k = c.a.k;
+	HIPCHK(k <= 8    ? (launch_chain_prepare_g<8, 1>(c, m->s))
+	       : k <= 16 ? (launch_chain_prepare_g<16, 1>(c, m->s))
+	       : k <= 32 ? (launch_chain_prepare_g<32, 1>(c, m->s))
+	       : k <= 64 ? (launch_chain_prepare_g<64, 1>(c, m->s))
+	       : k <= 128 ? (launch_chain_prepare_g<64, 2>(c, m->s))
+	                  : (launch_chain_prepare_g<64, 4>(c, m->s)));
 }
 
 const char *kind_name(int32_t kind)
@@ -664,17 +1015,31 @@ struct vbfm_candidates {
 	// ([3][k][Mpad]), and the rows' T_n
 	double *zt = nullptr, *ut = nullptr;   // (views into qt)
 	DevBuf<double> tb;            // [Mpad]
+	// vbfm_candidates_create_chain only: the draws of the chain model; qt is then [S][k][Mpad] and base
+	// [S][Mpad]. 0: a set of one set of parameters
+	uint32_t S = 0;
 };
 
 namespace {
 
-// vbfm_candidates_create (var = false: what it always allocated and launched) and _create_var
-int candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids, bool var, const std::string &who)
+enum SetKind { SET_PLAIN, SET_VAR, SET_CHAIN };
+
+// what the chain entry points say to a model of one set of parameters
+std::string not_a_chain(const std::string &who, const vbfm_model *m)
 {
+	return who + ": a model of kind " + kind_name(m->info.kind) + " holds one set of parameters, not a chain of draws "
+	             "(VBFM_MODEL_MCMC_CHAIN): rank it with vbfm_candidates_create / vbfm_recommend";
+}
+
+// vbfm_candidates_create (SET_PLAIN: what it always allocated and launched), _create_var and _create_chain
+int candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids, SetKind set, const std::string &who)
+{
+	const bool var = set == SET_VAR, chain = set == SET_CHAIN;
 	if (!m) return mfail(nullptr, who + ": null model");
 	if (!out || !rows) return mfail(m, who + ": null argument");
 	*out = nullptr;
-	if (m->info.kind == VBFM_MODEL_MCMC_CHAIN)
+	if (chain && m->info.kind != VBFM_MODEL_MCMC_CHAIN) return mfail(m, not_a_chain(who, m));
+	if (!chain && m->info.kind == VBFM_MODEL_MCMC_CHAIN)
 		return mfail(m, who + ": a chain of draws (VBFM_MODEL_MCMC_CHAIN) is scored, not ranked: "
 		                "recommendation takes a model of one set of parameters");
 	vbfm_candidates *c = nullptr;
@@ -687,14 +1052,16 @@ int candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows
 		const std::vector<ChunkPlan> plan = plan_chunks(rows, VBFM_SCORE_CHUNK_DEFAULT, who, &need_in, &need_rows);
 		const uint32_t Mpad = round_up(rows->num_rows, REC_STEP);
 		const int k = m->info.num_factor;
-		const size_t planes = var ? 3 : 1, nq = planes * (size_t)k * Mpad;
-		if (var) {   // three times a plain set: its bytes against the free memory before anything is allocated
-			const uint64_t bytes = ((uint64_t)nq + 2 * (uint64_t)Mpad) * 8;
+		const size_t planes = var ? 3 : (chain ? m->S : 1), nbase = (chain ? m->S : 1) * (size_t)Mpad;
+		const size_t nq = planes * (size_t)k * Mpad;
+		if (var || chain) {   // 3 or S times a plain set: its bytes against the free memory before anything is allocated
+			const uint64_t bytes = ((uint64_t)nq + (uint64_t)nbase + (var ? (uint64_t)Mpad : 0)) * 8;
 			size_t free_b = 0, total_b = 0;
 			HIPCHK(hipMemGetInfo(&free_b, &total_b));
 			if (bytes > (uint64_t)free_b)
-				throw who + ": " + std::to_string(rows->num_rows) + " candidates of num_factor = " + std::to_string(k) + " need " +
-				    std::to_string(bytes) + " bytes of device memory, " + std::to_string((uint64_t)free_b) + " are free";
+				throw who + ": " + std::to_string(rows->num_rows) + " candidates of num_factor = " + std::to_string(k) +
+				    (chain ? " and " + std::to_string(m->S) + " draws" : std::string()) + " need " + std::to_string(bytes) +
+				    " bytes of device memory, " + std::to_string((uint64_t)free_b) + " are free";
 		}
 		staging_reserve(m, need_in, 0);
 		c = new vbfm_candidates();
@@ -703,8 +1070,9 @@ int candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows
 		c->M = rows->num_rows;
 		c->Mpad = Mpad;
 		c->k = k;
+		c->S = chain ? m->S : 0;
 		c->qt.alloc(nq);
-		c->base.alloc(c->Mpad);
+		c->base.alloc(nbase);
 		if (var) {
 			c->zt = c->qt + (size_t)k * Mpad;
 			c->ut = c->zt + (size_t)k * Mpad;
@@ -712,7 +1080,7 @@ int candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows
 			if (c->Mpad) HIPCHK(hipMemsetAsync(c->tb, 0, (size_t)c->Mpad * 8, m->s));
 		}
 		if (nq) HIPCHK(hipMemsetAsync(c->qt, 0, nq * 8, m->s));
-		if (c->Mpad) HIPCHK(hipMemsetAsync(c->base, 0, (size_t)c->Mpad * 8, m->s));
+		if (nbase) HIPCHK(hipMemsetAsync(c->base, 0, nbase * 8, m->s));
 		flags_reset(m);
 		// one chunk at a time through slot 0: a candidate set is prepared once
 		for (const ChunkPlan &p : plan) {
@@ -720,8 +1088,11 @@ int candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows
 			const uint32_t nr = p.r1 - p.r0;
 			const size_t bytes = stage_rows(sl.h_in, rows, p.r0, nr);
 			HIPCHK(hipMemcpyAsync(sl.d_in, sl.h_in, bytes, hipMemcpyHostToDevice, m->s));
-			launch_prepare(m, sl.d_in, nr, rows->row_ptr[p.r0], p.r0, c->base + p.r0, var ? c->tb + p.r0 : nullptr, c->qt + p.r0,
-			               c->Mpad);
+			if (chain)
+				launch_prepare_chain(m, sl.d_in, nr, rows->row_ptr[p.r0], p.r0, c->base + p.r0, c->Mpad, c->qt + p.r0, c->Mpad);
+			else
+				launch_prepare(m, sl.d_in, nr, rows->row_ptr[p.r0], p.r0, c->base + p.r0, var ? c->tb + p.r0 : nullptr,
+				               c->qt + p.r0, c->Mpad);
 			HIPCHK(hipStreamSynchronize(m->s));
 		}
 		if (var && (size_t)k * Mpad) {   // the P plane becomes U = Z + P, rounded once
@@ -744,8 +1115,15 @@ int candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows
 // What a ranking adds to rank_call below (vbfm_recommend, vbfm_recommend_ucb).
 struct Ranking {
 	const char *who = "";         // the call, in messages
-	int planes = 1;               // prepared per context: 1 (Q) or 3 (Q, Z, P)
+	int planes = 1;               // prepared per context: 1 (Q), 3 (Q, Z, P) or a chain's S (Q of every draw)
+	int bases = 1;                // bases per context: 1, or a chain's S ([s][rows_pad])
 	bool tb = false;              // the contexts' T_n beside their bases (and the candidate set's tb)
+	// a chunk's prepared sums count against chunk_bytes where they outweigh its staged rows (a chain:
+	// planes * (k + 1) * 8 bytes a row); such a chunk holds at least min_rows rows (plan_chunks)
+	uint64_t row_extra = 0;
+	uint32_t min_rows = 1;
+	// the contexts' preparation where it is not launch_prepare: (staged rows, nr, e0, r0, base, q, q_tile, rows_pad)
+	std::function<void(const uint8_t *, uint32_t, uint64_t, uint32_t, double *, double *, uint32_t, uint32_t)> prepare;
 	// the pair kernel's context tile for a call whose largest chunk has nB rows
 	std::function<uint32_t(size_t nB, int k, int topn)> tile;
 	std::function<hipError_t(uint32_t ctx, const PairPtrs &, const PairArgs &, hipStream_t)> pairs;
@@ -759,13 +1137,16 @@ struct Ranking {
 	std::function<void(uint32_t ctx, const PairPtrs &, const PairArgs &, const MergeArgs &, hipStream_t)> finish;
 };
 
-// what both ranking calls refuse before anything else; then fn under the model's guard
+// what the ranking calls refuse before anything else (chain: the call that takes a chain model, and
+// nothing else); then fn under the model's guard
 template <class F>
-int ranking_guarded(const std::string &who, vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *contexts, const void *opts, F &&fn)
+int ranking_guarded(const std::string &who, vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *contexts, const void *opts, F &&fn,
+                    bool chain = false)
 {
 	if (!m) return mfail(nullptr, who + ": null model");
 	if (!cs || !contexts || !opts) return mfail(m, who + ": null argument");
-	if (m->info.kind == VBFM_MODEL_MCMC_CHAIN)
+	if (chain && m->info.kind != VBFM_MODEL_MCMC_CHAIN) return mfail(m, not_a_chain(who, m));
+	if (!chain && m->info.kind == VBFM_MODEL_MCMC_CHAIN)
 		return mfail(m, who + ": a chain of draws (VBFM_MODEL_MCMC_CHAIN) is scored, not ranked: "
 		                "recommendation takes a model of one set of parameters");
 	return mguarded(m, fn);
@@ -776,6 +1157,14 @@ int ranking_guarded(const std::string &who, vbfm_model *m, const vbfm_candidates
 void require_own_set(const std::string &who, const vbfm_model *m, const vbfm_candidates *cs)
 {
 	if (cs->m != m) throw who + ": the candidate set was made from another model";
+}
+
+// a set of vbfm_candidates_create_chain holds S draws' sums in another layout
+void refuse_chain_set(const std::string &who, const vbfm_candidates *cs)
+{
+	if (cs->S)
+		throw who + ": the candidate set holds the sums of a chain's " + std::to_string(cs->S) +
+		    " draws (it was made by vbfm_candidates_create_chain); vbfm_recommend_chain ranks it";
 }
 
 void require_topn(const std::string &who, int32_t topn)
@@ -808,7 +1197,7 @@ void rank_call(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *context
 	check_exclusions(who, B, M, excl_ptr, excl_idx);
 	size_t need_in = 0, need_rows = 0;
 	const std::vector<ChunkPlan> plan = plan_chunks(contexts, o.chunk_bytes ? o.chunk_bytes : VBFM_SCORE_CHUNK_DEFAULT, who,
-	                                                &need_in, &need_rows);
+	                                                &need_in, &need_rows, d.row_extra, d.min_rows);
 	const uint32_t ctx = d.tile(need_rows, k, o.topn);
 	// a chunk's rows as stage_rows writes them; its exclusion lists follow
 	const auto rows_bytes = [&](uint32_t r0, uint32_t nr) {
@@ -824,13 +1213,13 @@ void rank_call(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *context
 	const auto out_doubles = [&](size_t nr) { return d.nvals * nr * topn + (nr * topn * 4 + nr * 4 + 7) / 8; };
 	staging_reserve(m, need_in, out_doubles(need_rows));
 	const size_t rows_pad = round_up(need_rows, ctx);
-	DevBuf<double> base_c(rows_pad), tb_c;
+	DevBuf<double> base_c(d.bases * rows_pad), tb_c;
 	if (d.tb) tb_c.alloc(rows_pad);
 	DevBuf<double> qc(d.planes * rows_pad * (size_t)k), part_key(need_part * topn);
 	DevBuf<uint32_t> part_idx(need_part * topn), part_cnt(need_part);
 	DevBuf<unsigned long long> counters(2);
 	HIPCHK(hipMemsetAsync(counters, 0, 16, m->s));
-	HIPCHK(hipMemsetAsync(base_c, 0, rows_pad * 8, m->s));
+	HIPCHK(hipMemsetAsync(base_c, 0, d.bases * rows_pad * 8, m->s));
 	if (d.tb) HIPCHK(hipMemsetAsync(tb_c, 0, rows_pad * 8, m->s));
 	flags_reset(m);
 	PhaseEvents pe;
@@ -854,10 +1243,11 @@ void rank_call(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *context
 		    const size_t n = (size_t)nr * topn;
 		    Event *ev = pe.ev[i & 1];
 		    HIPCHK(hipEventRecord(ev[0], m->s));
-		    launch_prepare(m, sl.d_in, nr, contexts->row_ptr[r0], r0, base_c, tb_c, qc, ctx);
+		    if (d.prepare) d.prepare(sl.d_in, nr, contexts->row_ptr[r0], r0, base_c, qc, ctx, (uint32_t)rows_pad);
+		    else launch_prepare(m, sl.d_in, nr, contexts->row_ptr[r0], r0, base_c, tb_c, qc, ctx);
 		    HIPCHK(hipEventRecord(ev[1], m->s));
 		    PairArgs a = {};
-		    a.nB = nr; a.M = M; a.Mpad = cs->Mpad;
+		    a.nB = nr; a.rows_pad = (uint32_t)rows_pad; a.M = M; a.Mpad = cs->Mpad;
 		    a.k = k;
 		    a.w0 = m->info.k0 ? m->info.w0_or_mu0 : 0.0;
 		    a.topn = o.topn;
@@ -924,12 +1314,17 @@ void vbfm_candidates_destroy(vbfm_candidates *c)
 
 int vbfm_candidates_create(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids)
 {
-	return candidates_create(out, m, rows, unknown_ids, false, "vbfm_candidates_create");
+	return candidates_create(out, m, rows, unknown_ids, SET_PLAIN, "vbfm_candidates_create");
 }
 
 int vbfm_candidates_create_var(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids)
 {
-	return candidates_create(out, m, rows, unknown_ids, true, "vbfm_candidates_create_var");
+	return candidates_create(out, m, rows, unknown_ids, SET_VAR, "vbfm_candidates_create_var");
+}
+
+int vbfm_candidates_create_chain(vbfm_candidates **out, vbfm_model *m, const vbfm_csr *rows, int32_t unknown_ids)
+{
+	return candidates_create(out, m, rows, unknown_ids, SET_CHAIN, "vbfm_candidates_create_chain");
 }
 
 int vbfm_recommend(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *contexts, const uint64_t *excl_ptr,
@@ -938,6 +1333,7 @@ int vbfm_recommend(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *con
 {
 	const std::string who = "vbfm_recommend";
 	return ranking_guarded(who, m, cs, contexts, opts, [&] {
+		refuse_chain_set(who, cs);
 		require_own_set(who, m, cs);
 		require_topn(who, opts->topn);
 		require_rest(who, m, opts->unknown_ids, contexts, idx && score && count);
@@ -964,6 +1360,7 @@ int vbfm_recommend_ucb(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr 
 	const std::string who = "vbfm_recommend_ucb";
 	return ranking_guarded(who, m, cs, contexts, opts, [&] {
 		const vbfm_recommend_ucb_opts o = *opts;
+		refuse_chain_set(who, cs);
 		require_variance(m, who.c_str());
 		require_own_set(who, m, cs);
 		if (!cs->tb)
@@ -1006,6 +1403,83 @@ int vbfm_recommend_ucb(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr 
 		rank_call(m, cs, contexts, excl_ptr, excl_idx, vbfm_recommend_opts{o.topn, o.clip, o.unknown_ids, o.chunk_bytes}, d, idx,
 		          count, st);
 	});
+}
+
+// vbfm_recommend's pipeline with a draw axis: k_chain_prepare for the contexts' S bases and sums,
+// k_chain_pairs, the merge on key and k_chain_finish for the returned values
+int vbfm_recommend_chain(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *contexts, const uint64_t *excl_ptr,
+                         const uint32_t *excl_idx, const vbfm_recommend_chain_opts *opts, int32_t *idx, double *key,
+                         double *score, double *var, uint32_t *count, vbfm_recommend_stats *st)
+{
+	const std::string who = "vbfm_recommend_chain";
+	return ranking_guarded(
+	    who, m, cs, contexts, opts,
+	    [&] {
+		    const vbfm_recommend_chain_opts o = *opts;
+		    if (!cs->S)   // such a set is never this model's: vbfm_candidates_create refuses a chain
+			    throw who + ": the candidate set holds one set of sums (it was made by vbfm_candidates_create" +
+			        (cs->tb ? "_var" : "") + "; use vbfm_candidates_create_chain)";
+		    require_own_set(who, m, cs);
+		    require_topn(who, o.topn);
+		    if (!std::isfinite(o.beta)) throw who + ": beta = " + std::to_string(o.beta) + " is not a finite number";
+		    if (o.noise != 0 && o.noise != 1) throw who + ": noise is 0 or 1";
+		    const bool cls = m->task == VBFM_TASK_CLASSIFICATION;
+		    if (o.noise && cls)
+			    throw who + ": noise = 1 adds the mean of 1 / alpha to the spread, and a model of task c has no noise precision";
+		    require_rest(who, m, o.unknown_ids, contexts, idx && count);
+		    const uint32_t S = m->S;
+		    const int k = cs->k;
+		    ChainRank u = {};
+		    u.S = S;
+		    u.invS = 1.0 / (double)S;
+		    if (o.noise) {   // the mean over the draws of 1 / alpha_s, in draw order
+			    double sum = 0.0;
+			    for (uint32_t s = 0; s < S; s++) sum = sum + 1.0 / m->draw_alpha[s];
+			    u.na = sum / (double)S;
+		    }
+		    u.beta = o.beta;
+		    u.link = !o.clip ? 0 : (cls ? 2 : 1);
+		    u.fin = o.clip != 0;
+		    u.mn = m->info.min_target; u.mx = m->info.max_target;
+		    u.lo = cls ? 0.0 : (double)m->info.min_target;
+		    u.hi = cls ? 1.0 : (double)m->info.max_target;
+		    // what rec_raw subtracts for draw s: its w0, or nothing without k0
+		    std::vector<double> h_w0(S, 0.0);
+		    if (m->info.k0) h_w0 = m->draw_w0;
+		    DevBuf<double> w0s(S);
+		    HIPCHK(hipMemcpy(w0s, h_w0.data(), (size_t)S * 8, hipMemcpyHostToDevice));
+		    const double *d_w0s = w0s;
+		    Ranking d;
+		    d.who = who.c_str();
+		    d.planes = (int)S;
+		    d.bases = (int)S;
+		    d.row_extra = (uint64_t)S * ((uint64_t)k + 1) * 8;
+		    d.min_rows = CHAIN_CTX;
+		    d.tile = [](size_t, int, int) { return (uint32_t)CHAIN_CTX; };
+		    d.prepare = [m](const uint8_t *d_in, uint32_t nr, uint64_t e0, uint32_t r0, double *base, double *q, uint32_t q_tile,
+		                    uint32_t rows_pad) { launch_prepare_chain(m, d_in, nr, e0, r0, base, rows_pad, q, q_tile); };
+		    d.pairs = [u, d_w0s](uint32_t, const PairPtrs &p, const PairArgs &a, hipStream_t s) {
+			    return launch_chain_pairs(p, d_w0s, a, u, s);
+		    };
+		    d.link = 0;   // the lists' keys as they are; k_chain_finish forms what is returned
+		    d.nvals = 3;
+		    d.vals[0] = key; d.vals[1] = score; d.vals[2] = var;
+		    d.finish = [u, d_w0s](uint32_t, const PairPtrs &p, const PairArgs &a, const MergeArgs &g, hipStream_t s) {
+			    const size_t n = (size_t)a.nB * a.topn;
+			    if (!n) return;
+			    ChainFinishArgs fa = {};
+			    fa.ctx_all = p.ctx_all; fa.qt = p.qt; fa.base_c = p.base_c; fa.base_j = p.base_j; fa.w0s = d_w0s;
+			    fa.nB = a.nB; fa.rows_pad = a.rows_pad; fa.Mpad = a.Mpad; fa.k = a.k; fa.topn = a.topn;
+			    fa.u = u;
+			    fa.idx = g.idx; fa.count = g.count;
+			    fa.key = g.score; fa.score = g.score + n; fa.var = g.score + 2 * n;
+			    k_chain_finish<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(fa);
+			    HIPCHK(hipGetLastError());
+		    };
+		    rank_call(m, cs, contexts, excl_ptr, excl_idx, vbfm_recommend_opts{o.topn, o.clip, o.unknown_ids, o.chunk_bytes}, d, idx,
+		              count, st);
+	    },
+	    true);
 }
 
 }  // extern "C"

@@ -430,9 +430,12 @@ struct ChunkPlan { uint32_t r0, r1; };
 
 // the rows of a call ("who" names it in messages) checked and cut into chunks of whole rows of at
 // most `budget` bytes of [row_ptr slice | entries]; a larger row is a chunk by itself. need_in /
-// need_rows: the largest chunk's bytes and rows
+// need_rows: the largest chunk's bytes and rows. row_extra: bytes that every row of a chunk takes
+// beside its staged form (vbfm_recommend_chain: the prepared sums of its draws); they count against
+// the budget, not in need_in, and a chunk then holds at least min_rows rows (a context tile) while
+// the call has them. With the defaults the plan is the one of the staged bytes alone.
 inline std::vector<ChunkPlan> plan_chunks(const vbfm_csr *rows, uint64_t budget, const std::string &who, size_t *need_in,
-                                          size_t *need_rows)
+                                          size_t *need_rows, uint64_t row_extra = 0, uint32_t min_rows = 1)
 {
 	const uint32_t n = rows->num_rows;
 	if (n && !rows->row_ptr) throw who + ": rows without row_ptr";
@@ -442,12 +445,13 @@ inline std::vector<ChunkPlan> plan_chunks(const vbfm_csr *rows, uint64_t budget,
 	*need_in = *need_rows = 0;
 	for (uint32_t r0 = 0; r0 < n;) {
 		uint32_t r1 = r0;
-		uint64_t bytes = 8;
+		uint64_t bytes = 8, extra = 0;
 		while (r1 < n) {
 			if (rows->row_ptr[r1 + 1] < rows->row_ptr[r1]) throw who + ": row_ptr is not monotone";
 			const uint64_t add = 8 + (rows->row_ptr[r1 + 1] - rows->row_ptr[r1]) * 8;
-			if (r1 > r0 && bytes + add > budget) break;
+			if (r1 - r0 >= min_rows && bytes + extra + add + row_extra > budget) break;
 			bytes += add;
+			extra += row_extra;
 			r1++;
 		}
 		plan.push_back(ChunkPlan{r0, r1});

@@ -20,6 +20,7 @@
 //     counterpart: the reference predicts only the test set attached while training); with
 //     -candidates ITEMS -topn N [-exclude X] that mode ranks the rows of ITEMS for every row of T,
 //     with -ucb BETA [-ucb_noise 1] [-out_rank_var V] on mean + BETA * sd (a model with variances);
+//     a chain file is ranked on the mean over its draws, with -ucb plus BETA times their spread;
 //   * -method mcmc -save_model FILE -chain B,T keeps the draws of iterations B, B + T, ... and writes
 //     them as one model whose -load_model scores are the chain average (what -out reports), -out_var
 //     the spread across the draws.
@@ -83,6 +84,8 @@
 #pragma weak vbfm_recommend
 #pragma weak vbfm_candidates_create_var
 #pragma weak vbfm_recommend_ucb
+#pragma weak vbfm_candidates_create_chain
+#pragma weak vbfm_recommend_chain
 #pragma weak vbfm_chain_create
 #pragma weak vbfm_chain_add
 #pragma weak vbfm_chain_count
@@ -1036,7 +1039,8 @@ static void run_score(const ScoreRun &r)
 // returned. Line r of X: candidate indices (0-based rows of ITEMS) never to return, in any order.
 // With -ucb BETA [-ucb_noise 1] [-out_rank_var V] the ranking is on mean + BETA * sd
 // (vbfm_recommend_ucb; a model with variances); P is as before and V holds, in P's layout, the
-// survivors' variance terms T.
+// survivors' variance terms T. A chain file (-chain B,T) takes vbfm_recommend_chain: the ranking is on
+// the mean over its draws (+ BETA * their spread with -ucb), P holds the chain's scores and V the spread.
 struct RecommendRun {
 	std::string model_file, context_file, item_file, out_file, exclude_file;
 	int32_t device, topn;
@@ -1085,16 +1089,17 @@ static void run_recommend(const RecommendRun &r)
 	}
 	const Owned<vbfm_model> model = load_model(r.model_file, r.device);
 	vbfm_model *m = model.get();
-	if (r.ucb) {
-		vbfm_model_info info;
-		if (vbfm_model_info_get(m, &info) != 0) throw std::string(vbfm_model_last_error(m));
-		if (!info.has_variance)
-			throw std::string("-ucb needs a model with variances (-method vb or vb_online): " + r.model_file + " holds none");
-	}
+	vbfm_model_info info;
+	if (vbfm_model_info_get(m, &info) != 0) throw std::string(vbfm_model_last_error(m));
+	const bool chain = info.kind == VBFM_MODEL_MCMC_CHAIN;
+	if (chain && !(vbfm_candidates_create_chain && vbfm_recommend_chain)) throw std::string("this build has no scorer");
+	if (r.ucb && !chain && !info.has_variance)
+		throw std::string("-ucb needs a model with variances (-method vb or vb_online): " + r.model_file +
+		                  " holds none (a chain file, -chain B,T, can be ranked with -ucb on the spread of its draws)");
 	const vbfm_csr item_rows{items.h.num_rows, items.h.nnz, items.h.row_ptr, items.h.row_ent};
 	vbfm_candidates *cs = nullptr;
-	if ((r.ucb ? vbfm_candidates_create_var : vbfm_candidates_create)(&cs, m, &item_rows, r.skip_unknown ? 1 : 0) != 0)
-		throw std::string(vbfm_model_last_error(m));
+	const auto create = chain ? vbfm_candidates_create_chain : (r.ucb ? vbfm_candidates_create_var : vbfm_candidates_create);
+	if (create(&cs, m, &item_rows, r.skip_unknown ? 1 : 0) != 0) throw std::string(vbfm_model_last_error(m));
 	const Owned<vbfm_candidates> candidates(cs);   // declared after the model: destroyed before it
 	const vbfm_csr rows{B, ctx.h.nnz, ctx.h.row_ptr, ctx.h.row_ent};
 	const vbfm_recommend_opts o{r.topn, 1, r.skip_unknown ? 1 : 0, 0};
@@ -1105,7 +1110,12 @@ static void run_recommend(const RecommendRun &r)
 	vbfm_recommend_stats st;
 	const uint64_t *xp = xptr.empty() ? nullptr : xptr.data();
 	const uint32_t *xi = xptr.empty() ? nullptr : xidx.data();
-	if (r.ucb) {
+	if (chain) {   // without -ucb: beta = 0, the chain mean
+		const vbfm_recommend_chain_opts co{o.topn, o.clip, o.unknown_ids, o.chunk_bytes, r.beta, r.ucb_noise ? 1 : 0};
+		if (vbfm_recommend_chain(m, cs, &rows, xp, xi, &co, idx.data(), nullptr, score.data(), r.ucb ? var.data() : nullptr,
+		                         count.data(), &st) != 0)
+			throw std::string(vbfm_model_last_error(m));
+	} else if (r.ucb) {
 		const vbfm_recommend_ucb_opts uo{o.topn, o.clip, o.unknown_ids, o.chunk_bytes, r.beta, r.ucb_noise ? 1 : 0};
 		if (vbfm_recommend_ucb(m, cs, &rows, xp, xi, &uo, idx.data(), nullptr, score.data(), var.data(), count.data(), &st) != 0)
 			throw std::string(vbfm_model_last_error(m));
@@ -1424,7 +1434,7 @@ int main(int argc, char **argv)
 		const std::string p_cand = cmd.reg("candidates", "with -load_model: rank the rows of this file for every row of -test and write the best -topn per row to -out as index:score pairs (targets are ignored)");
 		const std::string p_topn = cmd.reg("topn", "with -candidates: entries to return per row of -test (1..128)");
 		const std::string p_excl = cmd.reg("exclude", "with -candidates: line r lists the candidate indices (0-based rows of -candidates) never to return for row r of -test");
-		const std::string p_ucb = cmd.reg("ucb", "with -candidates: rank on mean + BETA * sd of the pair's row (vb and vb_online models; a negative BETA ranks on a lower bound); -out still holds the scores");
+		const std::string p_ucb = cmd.reg("ucb", "with -candidates: rank on mean + BETA * sd of the pair's row (vb and vb_online models, and chain files: sd is then the spread across the draws; a negative BETA ranks on a lower bound); -out still holds the scores");
 		const std::string p_ucbn = cmd.reg("ucb_noise", "with -ucb: 1 = sd is of y (T + 1/alpha), 0 (default) = of the model's mean (T)");
 		const std::string p_orv = cmd.reg("out_rank_var", "with -ucb: the returned entries' variance terms T as index:T pairs, in the layout of -out");
 		if (cmd.has(p_help) || argc == 1) { cmd.print_help(); return 0; }

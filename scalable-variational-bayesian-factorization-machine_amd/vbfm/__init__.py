@@ -219,6 +219,10 @@ class RecommendUcbOpts(C.Structure):
     _fields_ = RecommendOpts._fields_ + [("beta", C.c_double), ("noise", C.c_int32)]
 
 
+# vbfm_recommend_chain_opts: the same fields
+RecommendChainOpts = RecommendUcbOpts
+
+
 class RecommendStats(C.Structure):
     _fields_ = [("n_chunks", C.c_uint32), ("pairs", C.c_uint64), ("nonfinite_pairs", C.c_uint64),
                 ("excluded_hits", C.c_uint64), ("ms_prepare", C.c_double), ("ms_pairs", C.c_double),
@@ -246,6 +250,7 @@ EXPORTS = ["vbfm_abi_version", "vbfm_last_error", "vbfm_create", "vbfm_destroy",
            "vbfm_synth_binarize", "vbfm_mcmc_class_info", "vbfm_model_file_task", "vbfm_model_write_host_task",
            "vbfm_model_task", "vbfm_candidates_create", "vbfm_candidates_count", "vbfm_candidates_destroy",
            "vbfm_recommend", "vbfm_candidates_create_var", "vbfm_recommend_ucb",
+           "vbfm_candidates_create_chain", "vbfm_recommend_chain",
            "vbfm_model_file_draws", "vbfm_model_write_host_chain", "vbfm_model_read_host_draw", "vbfm_model_num_draws",
            "vbfm_model_draw_scalars", "vbfm_chain_create", "vbfm_chain_add", "vbfm_chain_count", "vbfm_chain_save",
            "vbfm_model_from_chain", "vbfm_chain_destroy", "vbfm_chain_last_error"]
@@ -359,6 +364,9 @@ def lib():
         L.vbfm_candidates_create_var.argtypes = [C.POINTER(V), V, C.POINTER(Csr), C.c_int32]
         L.vbfm_recommend_ucb.argtypes = [V, V, C.POINTER(Csr), P_u64, P_u32, C.POINTER(RecommendUcbOpts),
                                          C.POINTER(C.c_int32), P_f64, P_f64, P_f64, P_u32, C.POINTER(RecommendStats)]
+        L.vbfm_candidates_create_chain.argtypes = [C.POINTER(V), V, C.POINTER(Csr), C.c_int32]
+        L.vbfm_recommend_chain.argtypes = [V, V, C.POINTER(Csr), P_u64, P_u32, C.POINTER(RecommendChainOpts),
+                                           C.POINTER(C.c_int32), P_f64, P_f64, P_f64, P_u32, C.POINTER(RecommendStats)]
         L.vbfm_model_file_draws.argtypes = [C.c_char_p, P_u32]
         L.vbfm_model_write_host_chain.argtypes = [C.c_char_p, C.POINTER(ModelInfo), C.c_int32, C.c_uint32,
                                                   C.POINTER(McmcParams)]
@@ -1242,6 +1250,27 @@ class Model:
         bound. exclude as recommend takes it."""
         o = RecommendUcbOpts(int(topn), int(bool(clip)), UNKNOWN_IDS[unknown_ids], int(chunk_bytes), float(beta), int(bool(noise)))
         idx, (key, score, var), count = self._rank(lib().vbfm_recommend_ucb, o, 3, contexts, candidates, topn, exclude)
+        return idx, key, score, var, count
+
+    def candidates_chain(self, data, unknown_ids="refuse"):
+        """The rows of `data` prepared once for recommend_chain (a chain model only): every draw's sums,
+        num_draws times the device memory of a set of one model. Close it before the model."""
+        rows, _keep = self._rows(data)
+        h = C.c_void_p()
+        self._mcheck(lib().vbfm_candidates_create_chain(C.byref(h), self._m, C.byref(rows), UNKNOWN_IDS[unknown_ids]))
+        return Candidates(h, self)
+
+    def recommend_chain(self, contexts, candidates, topn, beta=0.0, noise=False, exclude=None, clip=True,
+                        unknown_ids="refuse", chunk_bytes=0):
+        """recommend for a chain model (include/vbfm.h "ranking a chain of draws"; a candidate set from
+        candidates_chain): the pairs ranked on the mean over the draws of their raw value plus beta
+        times its spread across the draws. Returns (idx, key, score, var, count): key the value ranked
+        on, score the chain mean (clip=True: as score returns it for the pair's row), var the spread
+        without the noise term; sd is sqrt(var), with noise=True sqrt(var + mean of 1 / alpha).
+        exclude as recommend takes it."""
+        o = RecommendChainOpts(int(topn), int(bool(clip)), UNKNOWN_IDS[unknown_ids], int(chunk_bytes), float(beta),
+                               int(bool(noise)))
+        idx, (key, score, var), count = self._rank(lib().vbfm_recommend_chain, o, 3, contexts, candidates, topn, exclude)
         return idx, key, score, var, count
 
     def close(self):
