@@ -855,6 +855,99 @@ int vbfm_recommend_chain(vbfm_model *m, const vbfm_candidates *c, const vbfm_csr
                          const uint32_t *excl_idx, const vbfm_recommend_chain_opts *o, int32_t *idx, double *key,
                          double *score, double *var, uint32_t *count, vbfm_recommend_stats *st);
 
+/* ---- fold-in: new attributes into a VB model (additive to ABI 4: new functions and structs only) ------
+ * No reference counterpart. A model m of a VB kind (VBFM_MODEL_VB, VBFM_MODEL_VB_ONLINE) with D attributes
+ * and k factors is extended by attributes it has never seen -- a user who signed up after training --
+ * from support rows that mention them, everything the model knows held fixed. With all other parameters
+ * frozen the prediction of a row holding ONE new attribute j (value x) is linear in j's (w, v_1..v_k):
+ *     yhat_r = base_r + x w + x sum_f A_r[f] v[f]
+ * so the VB update of those k + 1 parameters is the reference's own update_w / update_v
+ * (fm_learn_vb.h:527-644) restricted to attribute j, different new attributes do not interact, and each
+ * is a small independent problem over the rows that mention it.
+ *
+ * Input: support rows (vbfm_csr) with float target[num_rows]. An entry with id < D is frozen, one with
+ * id >= D is new; a valid row holds EXACTLY ONE new entry (id j, value x_r) and j < D_out, where D_out is
+ * num_attribute_out or, if that is 0, the largest new id + 1 (D for no rows). A row with no new entry, with
+ * two, or with j >= D_out fails the call; the message names the first such row and the id.
+ *
+ * Frozen sums of row r: exactly what the lane-group scorer produces for the row with its new entry left
+ * out (vbfm_score with unknown_ids = skip, VBFM_ORDER_GROUP, the row preparation of vbfm_recommend_ucb):
+ * base_r the unclipped mean, A_r[f] = sum mu_v x, B_r[f] = sum sigma_v x^2 over the frozen entries in
+ * ascending id.
+ *
+ * Priors (precisions): the model file holds no hyper-parameters, so lambda_w and lambda_v[f] are given
+ * (prior_w > 0, prior_v[k]) or derived as the reference's hyper step does (fm_learn_vb.h:474-498) over the
+ * ids [prior_lo, prior_hi) of the model as its one group (0, 0: [0, D)), n = prior_hi - prior_lo:
+ *     lambda_w = n / sum_i (mu_w_i^2 + sigma_w_i)      lambda_v[f] = n / sum_i (mu_v_if^2 + sigma_v_if)
+ * so that new users can take the user block's prior. The sums are formed on the device in a fixed order
+ * (256 strided partial sums, each in ascending id, then a fixed tree): the same model gives the same
+ * bits every time. With k1 = 0 lambda_w is neither read nor derived (prior_used[0] = 0).
+ *
+ * The sweep for one new attribute j over its rows R_j in the caller's order; alpha, mu_0_dash and every
+ * frozen parameter stay fixed:
+ *     w = 0; v[f] = 0; s_w = 1 / lambda_w; s_v[f] = 1 / lambda_v[f];  e_r = target_r - base_r
+ *     for pass = 1 .. passes:
+ *       if k1:  S = sum x_r^2;  M = sum x_r (e_r + x_r w)
+ *               s' = 1 / (lambda_w + alpha S);  w' = s' alpha M;  guards (update_w, :545-565)
+ *               e_r += x_r (w - w');  w = w';  s_w = s'
+ *       for f = 0 .. k - 1:
+ *               h = A_r[f];  h1 = B_r[f]
+ *               S = sum x_r^2 (h^2 + h1);  M = sum x_r h (e_r + x_r v[f] h)
+ *               s' = 1 / (lambda_v[f] + alpha S);  v' = s' alpha M;  guards (update_v, :600-619)
+ *               e_r += x_r h (v[f] - v');  v[f] = v';  s_v[f] = s'
+ *       if tol > 0 and the largest |new - old| mean of this pass <= tol: stop this column
+ * The guards are the reference's: a non-finite s' keeps the old sigma; a non-finite mean keeps the old
+ * one, skips its e update and is counted in nonfinite_updates (its |new - old| is 0). h is the frozen sum
+ * itself: the reference's q - x mu is the same number without the rounding of adding and subtracting the
+ * attribute's own term. t, tq and tz are not kept: only alpha's update reads them, and alpha is fixed.
+ * An id in [D, D_out) without a row gets {0, 1 / lambda}. With k1 = 0 the new w entries are {0, 0} (the
+ * scorer never reads them). The sums S and M are formed by a group of lanes (the rows across the lanes,
+ * a fixed butterfly): a column's result depends on its rows, the lane width and nothing else -- not the
+ * chunk size, the grid or its neighbours -- and differs from a row-order fp64 sum by the rounding of a
+ * reordered sum.
+ *
+ * The extended model *out is a new handle, independent of m: same kind, task, scalars, alpha and iter,
+ * num_attribute = D_out, entries [0, D) byte-identical to m's. Every consumer takes it unchanged:
+ * vbfm_score, vbfm_candidates_create[_var], vbfm_recommend[_ucb], vbfm_model_write. m is not changed.
+ * Rows with several new attributes (new user x new item), refitting ids the model has, ALS / MCMC models
+ * and updating alpha or the hyper-parameters are out of scope.
+ *
+ * Refused, with a message that names the offender and *out = NULL: a null argument; a model that is not
+ * of a VB kind (the message names the kind); passes < 1; num_factor > 256; a given prior that is not
+ * finite or not positive (prior_w < 0 included; prior_w = 0 derives); a prior id range that is empty or
+ * not inside [0, D); a derived prior that is not finite. Failures are in vbfm_model_last_error(m). */
+typedef struct {
+	int32_t passes;               /* >= 1 */
+	double tol;                   /* 0: run every pass */
+	double prior_w;               /* 0: derive; else finite and > 0 */
+	const double *prior_v;        /* [k] or NULL: derive */
+	uint32_t prior_lo, prior_hi;  /* 0, 0: [0, D) */
+	uint32_t num_attribute_out;   /* 0: largest new id + 1 */
+	int32_t lanes;                /* 0: auto; else a width of the table in csrc/vbfm_fold.hip: 4, 8, 16, 32, 64 or
+	                                 256 (one workgroup per column) (tests, tuning) */
+	uint64_t chunk_bytes;         /* 0: VBFM_SCORE_CHUNK_DEFAULT; staged rows plus their prepared planes */
+} vbfm_fold_opts;
+typedef struct {
+	uint32_t new_attributes;      /* D_out - D */
+	uint32_t with_rows;           /* of those, the ones some row mentions */
+	uint32_t longest_column;      /* rows */
+	uint32_t passes_max;          /* the largest pass count a column ran */
+	uint32_t not_converged;       /* tol > 0: columns with rows that ran every pass without meeting tol */
+	uint64_t rows, nonfinite_updates;
+	uint32_t n_chunks;
+	int32_t lanes;                /* the width used */
+	double ms_prepare, ms_fold;   /* device time of the chunks' row preparation / fold kernels, summed */
+	double ms_total;              /* host wall time of the call */
+} vbfm_fold_stats;
+/* resid: NULL or [rows], e_r after the last pass (= target_r - the extended model's unclipped mean of row
+ * r, up to rounding); prior_used: NULL or [1 + k], lambda_w then lambda_v[f]; st may be NULL. */
+int vbfm_fold_in(vbfm_model **out, vbfm_model *m, const vbfm_csr *rows, const float *target,
+                 const vbfm_fold_opts *o, double *resid, double *prior_used, vbfm_fold_stats *st);
+/* any model handle but a chain (that is refused, the message names vbfm_chain_save) to a model file,
+ * through the host writer of vbfm_model_save: load -> write reproduces a file byte for byte when iter is
+ * the file's */
+int vbfm_model_write(vbfm_model *m, const char *path, uint32_t iter);
+
 #ifdef __cplusplus
 }
 #endif

@@ -897,6 +897,11 @@ uint32_t pick_slices(uint32_t nB, uint32_t M, uint32_t ctx = REC_CTX)
 	return std::max<uint32_t>(1, std::min(want, most));
 }
 
+}  // namespace
+
+namespace vbs {
+
+// (declared in vbfm_score.h: vbfm_fold.hip prepares its support rows with it too)
 // The sums and bases of rows [r0, r0 + nr) (already staged at d_in) by the lane-group scorer. With tb
 // also the variance sums: q takes the three planes of a tile (ScoreArgs::q), tb the rows' T_n; base and
 // the Q plane are the same bits either way (the VAR instantiations form the mean by the same
@@ -917,6 +922,10 @@ void launch_prepare(vbfm_model *m, const uint8_t *d_in, uint32_t nr, uint64_t e0
 	if (!nr) return;
 	HIPCHK(tb ? (launch_group<true, true>(a, 0, m->s)) : (launch_group<false, true>(a, 0, m->s)));
 }
+
+}  // namespace vbs
+
+namespace {
 
 // The same for a chain model: every draw's base (base[s * base_stride + r]) and per-factor sums (q in
 // tiles of [S][k][q_tile]) by k_chain_prepare, with the group width launch_group picks.

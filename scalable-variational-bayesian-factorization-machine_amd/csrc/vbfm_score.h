@@ -412,6 +412,13 @@ inline double elapsed(hipEvent_t a, hipEvent_t b)
 void model_alloc(vbfm_model *m);   // streams, events, the flag word and the tables of m->info's shape (and m->S)
 void model_free(vbfm_model *m);
 
+// ---- vbfm_recommend.hip -----------------------------------------------------------------------
+// the row preparation of the rankings and of vbfm_fold_in: base and the per-factor sums of nr rows
+// staged at d_in ([row_ptr slice | entries], entry positions from e0) by the lane-group scorer on m->s;
+// with tb also the variance planes and the rows' T_n (ScoreArgs::q)
+void launch_prepare(vbfm_model *m, const uint8_t *d_in, uint32_t nr, uint64_t e0, uint32_t r0, double *base, double *tb,
+                    double *q, uint32_t q_tile);
+
 // ---- vbfm_chain.hip ---------------------------------------------------------------------------
 // a chain model's scores of a.n rows (a.mean, a.var or NULL) on its interleaved tables: the mean over
 // the draws of link(yhat_s) and its spread (include/vbfm.h "chains of draws"). link: 0 none, 1 the

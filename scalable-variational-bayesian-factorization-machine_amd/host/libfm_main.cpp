@@ -43,6 +43,7 @@
 #include "../../include/vbfm.h"
 
 #include <cctype>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -93,6 +94,9 @@
 #pragma weak vbfm_chain_destroy
 #pragma weak vbfm_chain_last_error
 #pragma weak vbfm_model_num_draws
+// ... and those of -fold_in
+#pragma weak vbfm_fold_in
+#pragma weak vbfm_model_write
 
 namespace {
 
@@ -955,6 +959,17 @@ static void run_train(const std::string &method, const TrainOpts &r, Data &train
 }
 
 
+// -fold_in SUPPORT (predict-only mode): the loaded model is extended by the ids it has never seen, fitted
+// from SUPPORT's rows (vbfm_fold_in: every row holds exactly one id >= the model's num_attribute), before
+// anything is scored or ranked; -save_model then writes the extended model.
+struct FoldSpec {
+	std::string support_file, save_file;   // support_file empty: no fold-in
+	int32_t passes = 20;
+	double tol = 0.0;
+	uint32_t prior_lo = 0, prior_hi = 0;
+	double prior_w = 0.0, prior_v = 0.0;   // 0: derived
+};
+
 // -load_model FILE -test T -out P [-out_var V]: score T's rows with a saved model, no training. P
 // has the format and clipping of a training run's -out, V one T_n per line at 17 digits (VB kinds; a
 // chain of draws: the spread of the per-draw predictions).
@@ -963,6 +978,7 @@ struct ScoreRun {
 	int32_t device;
 	bool skip_unknown;
 	int32_t task;   // the file's
+	FoldSpec fold;
 };
 
 static Owned<vbfm_model> load_model(const std::string &file, int32_t device)
@@ -970,6 +986,31 @@ static Owned<vbfm_model> load_model(const std::string &file, int32_t device)
 	vbfm_model *m = nullptr;
 	if (vbfm_model_load(&m, file.c_str(), device) != 0) throw std::string(vbfm_last_error(nullptr));
 	return Owned<vbfm_model>(m);
+}
+
+static Owned<vbfm_model> load_model(const std::string &file, int32_t device, const FoldSpec &fold)
+{
+	Owned<vbfm_model> model = load_model(file, device);
+	if (fold.support_file.empty()) return model;
+	if (!(vbfm_fold_in && vbfm_model_write)) throw std::string("this build has no fold-in");
+	Data support;
+	load(fold.support_file, support, "support");
+	vbfm_model_info info;
+	if (vbfm_model_info_get(model.get(), &info) != 0) throw std::string(vbfm_model_last_error(model.get()));
+	const std::vector<double> pv((size_t)std::max(info.num_factor, 1), fold.prior_v);
+	const vbfm_fold_opts o{fold.passes, fold.tol, fold.prior_w, fold.prior_v > 0.0 ? pv.data() : nullptr,
+	                       fold.prior_lo, fold.prior_hi, 0, 0, 0};
+	const vbfm_csr rows{support.h.num_rows, support.h.nnz, support.h.row_ptr, support.h.row_ent};
+	vbfm_fold_stats st;
+	vbfm_model *ext = nullptr;
+	if (vbfm_fold_in(&ext, model.get(), &rows, support.h.target, &o, nullptr, nullptr, &st) != 0)
+		throw std::string(vbfm_model_last_error(model.get()));
+	Owned<vbfm_model> extended(ext);
+	std::cout << "folded in " << st.new_attributes << " new attributes from " << st.rows << " rows: at most " << st.passes_max
+	          << " passes, " << st.not_converged << " columns not converged" << std::endl;
+	if (!fold.save_file.empty() && vbfm_model_write(ext, fold.save_file.c_str(), info.iter) != 0)
+		throw std::string(vbfm_model_last_error(ext));
+	return extended;
 }
 
 static Owned<FILE> open_for_writing(const std::string &file)
@@ -984,7 +1025,7 @@ static void run_score(const ScoreRun &r)
 	if (!have_scorer()) throw std::string("this build has no scorer");
 	Data test;
 	load(r.test_file, test, "test");
-	const Owned<vbfm_model> model = load_model(r.model_file, r.device);
+	const Owned<vbfm_model> model = load_model(r.model_file, r.device, r.fold);
 	vbfm_model *m = model.get();
 	vbfm_model_info info;
 	if (vbfm_model_info_get(m, &info) != 0) throw std::string(vbfm_last_error(nullptr));
@@ -1048,6 +1089,7 @@ struct RecommendRun {
 	bool ucb = false, ucb_noise = false;
 	double beta = 0.0;
 	std::string rank_var_file;
+	FoldSpec fold;
 };
 
 static bool have_recommender()
@@ -1087,7 +1129,7 @@ static void run_recommend(const RecommendRun &r)
 		}
 		if (xidx.empty()) xidx.push_back(0);
 	}
-	const Owned<vbfm_model> model = load_model(r.model_file, r.device);
+	const Owned<vbfm_model> model = load_model(r.model_file, r.device, r.fold);
 	vbfm_model *m = model.get();
 	vbfm_model_info info;
 	if (vbfm_model_info_get(m, &info) != 0) throw std::string(vbfm_model_last_error(m));
@@ -1283,12 +1325,76 @@ static int launch(const Job &job, Data &train, Data &test, Rank proto, const std
 	return 0;
 }
 
+// a whole number / a finite number of a flag's value, or the flag's refusal
+static long long flag_integer(const std::string &flag, const std::string &v, const std::string &what)
+{
+	char *end = nullptr;
+	errno = 0;
+	const long long x = strtoll(v.c_str(), &end, 10);
+	if (v.empty() || *end || errno) throw std::string("-" + flag + " needs " + what + ", not '" + v + "'");
+	return x;
+}
+
+static double flag_number(const std::string &flag, const std::string &v, const std::string &what)
+{
+	char *end = nullptr;
+	const double x = strtod(v.c_str(), &end);
+	if (v.empty() || *end || !std::isfinite(x)) throw std::string("-" + flag + " needs " + what + ", not '" + v + "'");
+	return x;
+}
+
+// -fold_in and its flags (checked before any file is read and before any GPU call)
+static FoldSpec parse_fold(const CmdLine &cmd)
+{
+	FoldSpec f;
+	if (!cmd.has("fold_in")) {
+		for (const std::string p : {"fold_passes", "fold_tol", "fold_prior_ids", "fold_prior"})
+			if (cmd.has(p)) throw std::string("-" + p + " needs -fold_in");
+		if (cmd.has("save_model")) throw std::string("-save_model with -load_model writes the model -fold_in extends: give -fold_in");
+		return f;
+	}
+	if (!cmd.has("save_model") && !cmd.has("test")) throw std::string("-fold_in needs -save_model or -test (or both)");
+	f.support_file = cmd.get("fold_in");
+	f.save_file = cmd.get("save_model");
+	if (cmd.has("fold_passes")) {
+		const long long t = flag_integer("fold_passes", cmd.get("fold_passes"), "a whole number >= 1");
+		if (t < 1 || t > 0x7fffffff) throw std::string("-fold_passes needs a whole number >= 1, not '" + cmd.get("fold_passes") + "'");
+		f.passes = (int32_t)t;
+	}
+	if (cmd.has("fold_tol")) {
+		f.tol = flag_number("fold_tol", cmd.get("fold_tol"), "a finite number >= 0");
+		if (f.tol < 0.0) throw std::string("-fold_tol needs a finite number >= 0, not '" + cmd.get("fold_tol") + "'");
+	}
+	if (cmd.has("fold_prior_ids")) {
+		const std::vector<std::string> lh = cmd.list("fold_prior_ids");
+		const std::string what = "LO,HI: two whole numbers with 0 <= LO < HI";
+		if (lh.size() != 2) throw std::string("-fold_prior_ids needs " + what + ", not '" + cmd.get("fold_prior_ids") + "'");
+		const long long lo = flag_integer("fold_prior_ids", lh[0], what), hi = flag_integer("fold_prior_ids", lh[1], what);
+		if (lo < 0 || lo >= hi || hi > 0xffffffffll)
+			throw std::string("-fold_prior_ids needs " + what + ", not '" + cmd.get("fold_prior_ids") + "'");
+		f.prior_lo = (uint32_t)lo;
+		f.prior_hi = (uint32_t)hi;
+	}
+	if (cmd.has("fold_prior")) {
+		const std::vector<std::string> wv = cmd.list("fold_prior");
+		const std::string what = "W,V: two finite precisions > 0";
+		if (wv.size() != 2) throw std::string("-fold_prior needs " + what + ", not '" + cmd.get("fold_prior") + "'");
+		f.prior_w = flag_number("fold_prior", wv[0], what);
+		f.prior_v = flag_number("fold_prior", wv[1], what);
+		if (!(f.prior_w > 0.0 && f.prior_v > 0.0)) throw std::string("-fold_prior needs " + what + ", not '" + cmd.get("fold_prior") + "'");
+	}
+	return f;
+}
+
 // -load_model: predict only; the model decides method and dimensions
 static void run_load_model(const CmdLine &cmd)
 {
 	for (const std::string p : {"method", "dim", "iter", "chain"})
 		if (cmd.has(p)) throw std::string("-load_model scores with a trained model: -" + p + " does not apply");
-	if (!cmd.has("test") || !cmd.has("out")) throw std::string("-load_model needs -test and -out");
+	const FoldSpec fold = parse_fold(cmd);
+	const bool fold_only = !fold.support_file.empty() && !cmd.has("test");   // fold in and write the extended model, nothing scored
+	if (fold_only && cmd.has("out")) throw std::string("-out needs -test");
+	if (!fold_only && (!cmd.has("test") || !cmd.has("out"))) throw std::string("-load_model needs -test and -out");
 	if (cmd.has("topn") && !cmd.has("candidates")) throw std::string("-topn needs -candidates");
 	if (cmd.has("exclude") && !cmd.has("candidates")) throw std::string("-exclude needs -candidates");
 	if (cmd.has("candidates") && !cmd.has("topn")) throw std::string("-candidates needs -topn");
@@ -1305,6 +1411,7 @@ static void run_load_model(const CmdLine &cmd)
 	}
 	// the task is the file's; a -task that contradicts it is refused
 	int32_t ftask = VBFM_TASK_REGRESSION;
+	if (!fold.support_file.empty() && !(vbfm_fold_in && vbfm_model_write)) throw std::string("this build has no fold-in");
 	if (!have_scorer()) throw std::string("this build has no scorer");
 	if (vbfm_model_file_task) {
 		if (vbfm_model_file_task(cmd.get("load_model").c_str(), &ftask) != 0) throw std::string(vbfm_last_error(nullptr));
@@ -1318,9 +1425,14 @@ static void run_load_model(const CmdLine &cmd)
 	}
 	const std::string unk = cmd.get("unknown_ids", "refuse");
 	if (unk != "refuse" && unk != "skip") throw std::string("-unknown_ids: refuse or skip");
+	if (fold_only) {
+		(void)load_model(cmd.get("load_model"), (int32_t)cmd.geti("device", 0), fold);
+		return;
+	}
 	if (cmd.has("candidates")) {
 		RecommendRun run{cmd.get("load_model"), cmd.get("test"), cmd.get("candidates"), cmd.get("out"), cmd.get("exclude"),
 		                 (int32_t)cmd.geti("device", 0), (int32_t)cmd.geti("topn", 0), unk == "skip"};
+		run.fold = fold;
 		if (cmd.has("ucb")) {
 			run.beta = beta;
 			run.ucb = true;
@@ -1331,7 +1443,7 @@ static void run_load_model(const CmdLine &cmd)
 		return;
 	}
 	run_score(ScoreRun{cmd.get("load_model"), cmd.get("test"), cmd.get("out"), cmd.get("out_var"),
-	                   (int32_t)cmd.geti("device", 0), unk == "skip", ftask});
+	                   (int32_t)cmd.geti("device", 0), unk == "skip", ftask, fold});
 }
 
 // -chain B,T (checked before the data load): the draws to keep follow from -iter
@@ -1437,6 +1549,11 @@ int main(int argc, char **argv)
 		const std::string p_ucb = cmd.reg("ucb", "with -candidates: rank on mean + BETA * sd of the pair's row (vb and vb_online models, and chain files: sd is then the spread across the draws; a negative BETA ranks on a lower bound); -out still holds the scores");
 		const std::string p_ucbn = cmd.reg("ucb_noise", "with -ucb: 1 = sd is of y (T + 1/alpha), 0 (default) = of the model's mean (T)");
 		const std::string p_orv = cmd.reg("out_rank_var", "with -ucb: the returned entries' variance terms T as index:T pairs, in the layout of -out");
+		const std::string p_fold = cmd.reg("fold_in", "with -load_model (vb and vb_online models): extend the model by the feature ids it has never seen, fitted from the rows of this file (each holds exactly one such id) with everything else fixed, before -test is scored or ranked; -save_model writes the extended model");
+		const std::string p_foldp = cmd.reg("fold_passes", "with -fold_in: sweeps over a new id's parameters; default=20");
+		const std::string p_foldt = cmd.reg("fold_tol", "with -fold_in: stop a new id once no mean moved by more than this in a sweep; default=0 (run every sweep)");
+		const std::string p_foldi = cmd.reg("fold_prior_ids", "with -fold_in: LO,HI derives the new ids' prior precisions from the model's ids LO..HI-1 (e.g. the user block); default: all");
+		const std::string p_foldw = cmd.reg("fold_prior", "with -fold_in: W,V gives the prior precisions of the new w and v instead of deriving them");
 		if (cmd.has(p_help) || argc == 1) { cmd.print_help(); return 0; }
 		cmd.check();
 
@@ -1449,6 +1566,8 @@ int main(int argc, char **argv)
 			throw std::string("-candidates, -topn and -exclude belong to -load_model");
 		if (cmd.has(p_ucb) || cmd.has(p_ucbn) || cmd.has(p_orv))
 			throw std::string("-ucb, -ucb_noise and -out_rank_var belong to -load_model");
+		if (cmd.has(p_fold) || cmd.has(p_foldp) || cmd.has(p_foldt) || cmd.has(p_foldi) || cmd.has(p_foldw))
+			throw std::string("-fold_in and its -fold_* flags belong to -load_model");
 
 		const uint32_t seed = cmd.has(p_seed) ? (uint32_t)cmd.geti(p_seed, 0) : (uint32_t)time(NULL);
 		const std::string method = cmd.get(p_method, "mcmc");

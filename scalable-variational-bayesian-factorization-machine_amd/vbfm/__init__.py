@@ -232,6 +232,24 @@ class RecommendStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FoldOpts(C.Structure):
+    """vbfm_fold_opts"""
+    _fields_ = [("passes", C.c_int32), ("tol", C.c_double), ("prior_w", C.c_double), ("prior_v", P_f64),
+                ("prior_lo", C.c_uint32), ("prior_hi", C.c_uint32), ("num_attribute_out", C.c_uint32),
+                ("lanes", C.c_int32), ("chunk_bytes", C.c_uint64)]
+
+
+class FoldStats(C.Structure):
+    """vbfm_fold_stats"""
+    _fields_ = [("new_attributes", C.c_uint32), ("with_rows", C.c_uint32), ("longest_column", C.c_uint32),
+                ("passes_max", C.c_uint32), ("not_converged", C.c_uint32), ("rows", C.c_uint64),
+                ("nonfinite_updates", C.c_uint64), ("n_chunks", C.c_uint32), ("lanes", C.c_int32),
+                ("ms_prepare", C.c_double), ("ms_fold", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/vbfm.h declares (checked by tests/test_capi_cpu.py)
 EXPORTS = ["vbfm_abi_version", "vbfm_last_error", "vbfm_create", "vbfm_destroy", "vbfm_set_train",
            "vbfm_set_test", "vbfm_synth_generate", "vbfm_synth_multihot", "vbfm_get_csc", "vbfm_get_shape", "vbfm_get_levels",
@@ -253,7 +271,8 @@ EXPORTS = ["vbfm_abi_version", "vbfm_last_error", "vbfm_create", "vbfm_destroy",
            "vbfm_candidates_create_chain", "vbfm_recommend_chain",
            "vbfm_model_file_draws", "vbfm_model_write_host_chain", "vbfm_model_read_host_draw", "vbfm_model_num_draws",
            "vbfm_model_draw_scalars", "vbfm_chain_create", "vbfm_chain_add", "vbfm_chain_count", "vbfm_chain_save",
-           "vbfm_model_from_chain", "vbfm_chain_destroy", "vbfm_chain_last_error"]
+           "vbfm_model_from_chain", "vbfm_chain_destroy", "vbfm_chain_last_error",
+           "vbfm_fold_in", "vbfm_model_write"]
 
 # vbfm_exchange_fn: int fn(void *user, void *buf, uint64_t count, int32_t dtype, int32_t op)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32)
@@ -382,6 +401,9 @@ def lib():
         L.vbfm_chain_destroy.restype = None
         L.vbfm_chain_last_error.argtypes = [V]
         L.vbfm_chain_last_error.restype = C.c_char_p
+        L.vbfm_fold_in.argtypes = [C.POINTER(V), V, C.POINTER(Csr), P_f32, C.POINTER(FoldOpts), P_f64, P_f64,
+                                   C.POINTER(FoldStats)]
+        L.vbfm_model_write.argtypes = [V, C.c_char_p, C.c_uint32]
         _lib = L
     return _lib
 
@@ -1272,6 +1294,52 @@ class Model:
                                int(bool(noise)))
         idx, (key, score, var), count = self._rank(lib().vbfm_recommend_chain, o, 3, contexts, candidates, topn, exclude)
         return idx, key, score, var, count
+
+    def fold_in(self, data, passes=20, tol=0.0, prior_w=None, prior_v=None, prior_ids=None, num_attribute=None, lanes=0,
+                chunk_bytes=0, residuals=False):
+        """Attributes this VB model has never seen, fitted from support rows (include/vbfm.h "fold-in"):
+        `data` is a DataSubset that holds its rows and targets or a (row_ptr, feat, val, target) tuple;
+        every row holds exactly one id >= num_attribute. Everything the model knows stays fixed. Returns
+        (Model, stats) -- the extended model, a new handle, and the call's stats with the precisions
+        used as stats["prior_used"] (lambda_w, then lambda_v[f]) -- and with residuals=True also e_r
+        after the last pass. prior_w / prior_v: given precisions (None: derived from the model's ids
+        prior_ids = (lo, hi), default all); num_attribute: of the result (None: the largest new id + 1);
+        lanes: 0 or a lane width to force (tests, tuning)."""
+        if isinstance(data, DataSubset):
+            rows, _keep = self._rows(data)
+            target = np.ascontiguousarray(data.target, dtype=np.float32)
+        else:
+            rows, _keep = self._rows(data[:3])
+            target = np.ascontiguousarray(data[3], dtype=np.float32)
+        n, k = rows.num_rows, self.info["num_factor"]
+        if len(target) != n:
+            raise VbfmError("fold_in: %d targets for %d rows" % (len(target), n))
+        pv = None
+        if prior_v is not None:
+            pv = np.ascontiguousarray(prior_v, dtype=np.float64)
+            if len(pv) != k:
+                raise VbfmError("fold_in: prior_v holds %d values for %d factors" % (len(pv), k))
+            if k == 0:
+                pv = np.zeros(1)
+        lo, hi = (0, 0) if prior_ids is None else (int(prior_ids[0]), int(prior_ids[1]))
+        o = FoldOpts(int(passes), float(tol), 0.0 if prior_w is None else float(prior_w), _ptr(pv, P_f64), lo, hi,
+                     0 if num_attribute is None else int(num_attribute), int(lanes), int(chunk_bytes))
+        resid = np.zeros(n) if residuals else None
+        used = np.zeros(1 + k)
+        st = FoldStats()
+        h = C.c_void_p()
+        self._mcheck(lib().vbfm_fold_in(C.byref(h), self._m, C.byref(rows), _ptr(target, P_f32) if n else None,
+                                        C.byref(o), _ptr(resid, P_f64), _ptr(used, P_f64), C.byref(st)))
+        stats = st.as_dict()
+        stats["prior_used"] = used
+        out = Model(h)
+        return (out, stats, resid) if residuals else (out, stats)
+
+    def save(self, path, num_iter=None):
+        """Write this model (any kind but a chain: Chain.save writes that) to a model file; num_iter:
+        the iteration count of the header (None: the one the model came with)."""
+        it = self.info["iter"] if num_iter is None else int(num_iter)
+        self._mcheck(lib().vbfm_model_write(self._m, os.fsencode(path), it))
 
     def close(self):
         if self._m:
