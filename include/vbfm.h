@@ -855,6 +855,70 @@ int vbfm_recommend_chain(vbfm_model *m, const vbfm_candidates *c, const vbfm_csr
                          const uint32_t *excl_idx, const vbfm_recommend_chain_opts *o, int32_t *idx, double *key,
                          double *score, double *var, uint32_t *count, vbfm_recommend_stats *st);
 
+/* ---- ranking held-out candidates (additive to ABI 4: new functions and structs only) ----------------
+ * No reference counterpart. The three calls above return at most VBFM_REC_MAX_TOPN entries; held-out
+ * evaluation (HR@N, NDCG@N, MRR, AUC) needs the exact position of given candidates -- the positives of
+ * a context -- among ALL candidates. vbfm_rank_positives returns it, under the total order of the call
+ * that `ranking` names: VBFM_RANKING_MEAN vbfm_recommend, VBFM_RANKING_UCB vbfm_recommend_ucb (beta,
+ * noise), VBFM_RANKING_CHAIN vbfm_recommend_chain (beta, noise).
+ *
+ * For context c a candidate j is RANKABLE when it is not on c's exclusion list and its pair is ok for
+ * the ranking: MEAN raw(c, j) finite; UCB raw, T and key finite; CHAIN mean, var and key finite --
+ * the conditions under which that call would return the pair. key(c, j) is formed by that call's very
+ * expressions (raw; or key of "ranking by mean + beta * sd"; or key of "ranking a chain of draws"),
+ * the sums in the same order, and the order is the same: larger key first, equal keys by smaller index.
+ *
+ * Input: contexts, excl_ptr / excl_idx exactly as vbfm_recommend takes them (non-decreasing lists,
+ * repeats allowed, a repeated index counts once); pos_ptr [B + 1] / pos_idx [P]: context r's positives
+ * are the candidate indices pos_idx[pos_ptr[r] .. pos_ptr[r + 1]), strictly ascending, < M, none of
+ * them on r's exclusion list. Output:
+ *     key [P]     key(c, p) of positive p of context c, in pos_idx order; NaN when the pair is not ok
+ *     rank [P]    the rankable candidates j of c that are before p in the order (key(c, j) larger, or
+ *                 equal with j < p); -1 when p's own pair is not ok. The other positives of c count
+ *                 like any candidate (their keys are returned: the caller can take them out)
+ *     ranked [B]  the rankable candidates of c (also for a context without positives)
+ * The defining property: rank[p] is the position of p in the list the ranking's call would return were
+ * topn unbounded. If 0 <= rank[p] < topn <= VBFM_REC_MAX_TOPN, that call (same exclusions, clip = 0)
+ * returns idx[c][rank[p]] == pos_idx[p], with the bits of key[p] as its score (vbfm_recommend) or key
+ * (the other two), and its count[c] is min(topn, ranked[c]). Every output is an integer or the bits of
+ * the one pair expression, so all of them are identical whatever the chunk size, the slice count, the
+ * context tile and the number of passes (a wave holds 8 positives of a context; a context with more is
+ * passed over again, stats passes).
+ *
+ * Refused before any device work, the message naming the offender: a null argument; ranking outside
+ * the three; pos_ptr not starting at 0 or not monotone; a positive >= M (row and index named); a
+ * positive list that is not strictly ascending; a positive that is on its context's exclusion list
+ * (row and index named); unknown_ids outside 0 / 1; the model and candidate-set refusals of the
+ * ranking's own call (a chain model or set with MEAN / UCB, any other with CHAIN, a model without
+ * variances or a set of vbfm_candidates_create with UCB, a set of another model, noise = 1 on a chain
+ * of task c); beta not finite; noise outside 0 / 1; beta != 0 or noise != 0 with VBFM_RANKING_MEAN;
+ * num_factor > 256. The exclusion lists are checked as vbfm_recommend checks them. */
+#define VBFM_RANKING_MEAN 0
+#define VBFM_RANKING_UCB 1
+#define VBFM_RANKING_CHAIN 2
+typedef struct {
+	int32_t ranking;       /* VBFM_RANKING_* */
+	int32_t unknown_ids;   /* of the context rows: 0 refuse, 1 skip the entry */
+	uint64_t chunk_bytes;  /* as vbfm_recommend_opts */
+	double beta;           /* UCB, CHAIN: finite; MEAN: 0 */
+	int32_t noise;         /* UCB, CHAIN: as those calls' opts; MEAN: 0 */
+} vbfm_rank_positives_opts;
+typedef struct {
+	uint32_t n_chunks;
+	uint64_t pairs;                /* B * M */
+	uint64_t nonfinite_pairs;      /* pairs that are not ok, excluded ones included */
+	uint64_t positives;            /* P */
+	uint64_t nonfinite_positives;  /* positives of rank -1 */
+	uint32_t passes;               /* the most passes a chunk took: ceil(its longest positive list / 8), at least 1 */
+	double ms_prepare, ms_keys, ms_count, ms_finish;   /* device time of the chunks' row preparation, listed-pair, counting and finish kernels, summed */
+	double ms_total;               /* host wall time of the call */
+} vbfm_rank_positives_stats;
+/* key, rank: [P], required when P > 0; ranked: [B]; st may be NULL. Failures are in vbfm_model_last_error(m). */
+int vbfm_rank_positives(vbfm_model *m, const vbfm_candidates *c, const vbfm_csr *contexts, const uint64_t *excl_ptr,
+                        const uint32_t *excl_idx, const uint64_t *pos_ptr, const uint32_t *pos_idx,
+                        const vbfm_rank_positives_opts *o, double *key, int64_t *rank, uint32_t *ranked,
+                        vbfm_rank_positives_stats *st);
+
 /* ---- fold-in: new attributes into a VB model (additive to ABI 4: new functions and structs only) ------
  * No reference counterpart. A model m of a VB kind (VBFM_MODEL_VB, VBFM_MODEL_VB_ONLINE) with D attributes
  * and k factors is extended by attributes it has never seen -- a user who signed up after training --

@@ -16,7 +16,9 @@
 // calls are one host pipeline (rank_call) under two descriptions (Ranking). Ranking a chain of draws
 // (vbfm_recommend_chain) is a third: k_chain_prepare stores every draw's base and sums,
 // k_chain_pairs loops over the draws with the moments of a pair's raw values in registers, the same
-// merge, k_chain_finish.
+// merge, k_chain_finish. The exact rank of listed candidates under any of the three orders
+// (vbfm_rank_positives) is the same pipeline with counters in place of lists (eval_call):
+// k_eval_keys, k_eval_count_mean / _ucb / _chain, k_eval_finish.
 #include "vbfm_score.h"
 #include "vbfm_class_math.h"
 
@@ -495,19 +497,11 @@ struct FinishArgs {
 	double *key, *score, *var;    // [nB][topn], NaN beyond count
 };
 
-// After the merge (which ordered the slices' lists by key): one thread per returned entry forms the
-// survivor's raw, T and key again -- the same sums in the same order through ucb_pair, so the bits
-// the pair kernel ranked on -- and the returned score from raw.
-__global__ __launch_bounds__(256) void k_ucb_finish(const FinishArgs a)
+// A pair's value from its rows' prepared sums, outside the pair kernel: the same sums in the same order
+// (f ascending from 0) through ucb_pair, so the bits the pair kernel ranked on. k_ucb_finish forms the
+// returned entries with it, k_eval_keys the listed pairs of vbfm_rank_positives.
+DEVI UcbVal ucb_entry(const FinishArgs &a, uint32_t c, uint32_t j)
 {
-	const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-	if (p >= (uint64_t)a.nB * a.topn) return;
-	const uint32_t c = (uint32_t)(p / a.topn), e = (uint32_t)(p % a.topn);
-	if (e >= a.count[c]) {
-		a.key[p] = a.score[p] = a.var[p] = __builtin_nan("");
-		return;
-	}
-	const uint32_t j = (uint32_t)a.idx[p];
 	const int k = a.k;
 	const double *qc = a.ctx_all + (size_t)(c / a.ctx) * 3 * k * a.ctx + c % a.ctx;
 	const double *zc = qc + (size_t)k * a.ctx, *pc = zc + (size_t)k * a.ctx;
@@ -518,7 +512,21 @@ __global__ __launch_bounds__(256) void k_ucb_finish(const FinishArgs a)
 		t = __builtin_fma(zc[(size_t)f * a.ctx], a.ut[o], t);
 		t = __builtin_fma(pc[(size_t)f * a.ctx], a.zt[o], t);
 	}
-	const UcbVal v = ucb_pair(a.base_c[c], a.base_j[j], a.w0, dot, a.tb_c[c], a.tb_j[j], t, a.u);
+	return ucb_pair(a.base_c[c], a.base_j[j], a.w0, dot, a.tb_c[c], a.tb_j[j], t, a.u);
+}
+
+// After the merge (which ordered the slices' lists by key): one thread per returned entry forms the
+// survivor's raw, T and key again (ucb_entry) and the returned score from raw.
+__global__ __launch_bounds__(256) void k_ucb_finish(const FinishArgs a)
+{
+	const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (p >= (uint64_t)a.nB * a.topn) return;
+	const uint32_t c = (uint32_t)(p / a.topn), e = (uint32_t)(p % a.topn);
+	if (e >= a.count[c]) {
+		a.key[p] = a.score[p] = a.var[p] = __builtin_nan("");
+		return;
+	}
+	const UcbVal v = ucb_entry(a, c, (uint32_t)a.idx[p]);
 	a.key[p] = v.key;
 	a.score[p] = a.clip ? clip(v.raw, a.mn, a.mx) : v.raw;
 	a.var[p] = v.T;
@@ -833,10 +841,32 @@ struct ChainFinishArgs {
 	double *key, *score, *var;    // [nB][topn], NaN beyond count
 };
 
-// After the merge: one thread per returned entry forms the survivor's S raw_s again -- the same sums
-// in the same order through rec_raw, chain_add and chain_val, so the bits the pair kernel ranked on --
-// and beside them the returned score: the mean, or with clip = 1 vbfm_score's mean over the draws of
-// the linked per-draw values (the only place that needs Phi).
+// A pair's moments from its rows' prepared sums, outside the pair kernel: the S raw_s again -- the same
+// sums in the same order through rec_raw, chain_add and chain_val, so the bits the pair kernel ranked
+// on. With LINK also the sum over the draws of the linked per-draw values (the only place that needs
+// Phi). k_chain_finish forms the returned entries with it, k_eval_keys the listed pairs of
+// vbfm_rank_positives.
+template <bool LINK> DEVI ChainVal chain_entry(const ChainFinishArgs &a, uint32_t c, uint32_t j, double &sum)
+{
+	const uint32_t S = a.u.S;
+	const int k = a.k;
+	const double *qc = a.ctx_all + (size_t)(c / CHAIN_CTX) * S * k * CHAIN_CTX + c % CHAIN_CTX;
+	double raw0 = 0.0, sa = 0.0, sb = 0.0;
+	sum = 0.0;
+	for (uint32_t s = 0; s < S; ++s) {
+		const double *qs = qc + (size_t)s * k * CHAIN_CTX, *qj = a.qt + (size_t)s * k * a.Mpad + j;
+		double dot = 0.0;
+		for (int f = 0; f < k; ++f) dot = __builtin_fma(qs[(size_t)f * CHAIN_CTX], qj[(size_t)f * a.Mpad], dot);
+		const double raw = rec_raw(a.base_c[(size_t)s * a.rows_pad + c], a.base_j[(size_t)s * a.Mpad + j], a.w0s[s], dot);
+		chain_add(raw0, sa, sb, raw, s == 0);
+		if (LINK) sum = sum + (a.u.link == 1 ? clip(raw, a.u.mn, a.u.mx) : (a.u.link == 2 ? vbcm::Phi(raw) : raw));
+	}
+	return chain_val(raw0, sa, sb, a.u);
+}
+
+// After the merge: one thread per returned entry forms the survivor's values again (chain_entry) and
+// beside them the returned score: the mean, or with clip = 1 vbfm_score's mean over the draws of the
+// linked per-draw values.
 __global__ __launch_bounds__(256) void k_chain_finish(const ChainFinishArgs a)
 {
 	const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -846,20 +876,9 @@ __global__ __launch_bounds__(256) void k_chain_finish(const ChainFinishArgs a)
 		a.key[p] = a.score[p] = a.var[p] = __builtin_nan("");
 		return;
 	}
-	const uint32_t j = (uint32_t)a.idx[p], S = a.u.S;
-	const int k = a.k;
-	const double *qc = a.ctx_all + (size_t)(c / CHAIN_CTX) * S * k * CHAIN_CTX + c % CHAIN_CTX;
-	double raw0 = 0.0, sa = 0.0, sb = 0.0, sum = 0.0;
-	for (uint32_t s = 0; s < S; ++s) {
-		const double *qs = qc + (size_t)s * k * CHAIN_CTX, *qj = a.qt + (size_t)s * k * a.Mpad + j;
-		double dot = 0.0;
-		for (int f = 0; f < k; ++f) dot = __builtin_fma(qs[(size_t)f * CHAIN_CTX], qj[(size_t)f * a.Mpad], dot);
-		const double raw = rec_raw(a.base_c[(size_t)s * a.rows_pad + c], a.base_j[(size_t)s * a.Mpad + j], a.w0s[s], dot);
-		chain_add(raw0, sa, sb, raw, s == 0);
-		sum = sum + (a.u.link == 1 ? clip(raw, a.u.mn, a.u.mx) : (a.u.link == 2 ? vbcm::Phi(raw) : raw));
-	}
-	const ChainVal v = chain_val(raw0, sa, sb, a.u);
-	const double avg = sum / (double)S;
+	double sum;
+	const ChainVal v = chain_entry<true>(a, c, (uint32_t)a.idx[p], sum);
+	const double avg = sum / (double)a.u.S;
 	a.key[p] = v.key;
 	a.score[p] = a.u.fin ? clip(avg, a.u.lo, a.u.hi) : v.mean;
 	a.var[p] = v.var;
@@ -878,6 +897,389 @@ hipError_t launch_chain_pairs(const PairPtrs &p, const double *w0s, const PairAr
 	else CHAIN_LAUNCH(VBFM_REC_MAX_TOPN);
 #undef CHAIN_LAUNCH
 	return hipGetLastError();
+}
+
+// ---- exact ranks of listed candidates (include/vbfm.h "ranking held-out candidates") ----
+// vbfm_rank_positives counts, for every positive of a context, the candidates that the ranking's total
+// order puts before it. Three steps per chunk: k_eval_keys forms the value of every LISTED pair (the
+// positives and the exclusion entries), k_eval_count_* stream all candidates past the positives' keys
+// and only count, k_eval_finish takes the excluded candidates out again. A wave holds EVAL_POS
+// thresholds per context and pass; a context with more is covered by further passes (grid z), which
+// the waves whose tile has nothing left for them leave at once.
+#define EVAL_POS 8
+
+enum { EVAL_MEAN = 0, EVAL_UCB = 1, EVAL_CHAIN = 2 };
+
+// a chunk's two lists: positions ptr[r] .. ptr[r + 1] of the CALL for context r of the chunk, position
+// p at idx[p - base]
+struct EvalList {
+	const uint64_t *ptr;
+	const uint32_t *idx;
+	uint64_t base;
+	uint64_t n;               // entries of the chunk
+};
+
+// the context of position q of a list: the last r with ptr[r] <= q (33 steps at the most)
+DEVI uint32_t eval_ctx_of(const EvalList &l, uint32_t nB, uint64_t q)
+{
+	uint32_t lo = 0, hi = nB + 1;
+	for (int step = 0; step < 33 && lo < hi; ++step) {
+		const uint32_t mid = lo + (hi - lo) / 2;
+		if (l.ptr[mid] <= q) lo = mid + 1; else hi = mid;
+	}
+	return lo - 1;
+}
+
+struct EvalKeyArgs {
+	int mode;
+	FinishArgs f;             // EVAL_MEAN (ctx_all is then [tile of ctx][f][ctx]) and EVAL_UCB: the sides of a pair
+	ChainFinishArgs ch;       // EVAL_CHAIN
+	uint32_t nB;
+	EvalList pos, excl;
+	double *lkey;             // [pos.n + excl.n]: the listed pairs' keys, NaN where the pair is not ok
+};
+
+// One thread per listed pair: its value by the ranking's own expressions, the sums in the pair
+// kernels' order (f ascending from 0, a chain's draws in order).
+__global__ __launch_bounds__(256) void k_eval_keys(const EvalKeyArgs a)
+{
+	const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (p >= a.pos.n + a.excl.n) return;
+	const bool is_pos = p < a.pos.n;
+	const EvalList &l = is_pos ? a.pos : a.excl;
+	const uint64_t e = is_pos ? p : p - a.pos.n;
+	const uint32_t c = eval_ctx_of(l, a.nB, e + l.base), j = l.idx[e];
+	double key;
+	bool ok;
+	if (a.mode == EVAL_MEAN) {
+		const FinishArgs &f = a.f;
+		const double *qc = f.ctx_all + (size_t)(c / f.ctx) * f.k * f.ctx + c % f.ctx;
+		double dot = 0.0;
+		for (int i = 0; i < f.k; ++i) dot = __builtin_fma(qc[(size_t)i * f.ctx], f.qt[(size_t)i * f.Mpad + j], dot);
+		key = rec_raw(f.base_c[c], f.base_j[j], f.w0, dot);
+		ok = __builtin_isfinite(key);
+	} else if (a.mode == EVAL_UCB) {
+		const UcbVal v = ucb_entry(a.f, c, j);
+		key = v.key;
+		ok = v.ok;
+	} else {
+		double unused;
+		const ChainVal v = chain_entry<false>(a.ch, c, j, unused);
+		key = v.key;
+		ok = v.ok;
+	}
+	a.lkey[p] = ok ? key : __builtin_nan("");
+}
+
+struct EvalArgs {
+	EvalList pos;
+	const double *lkey;       // [pos.n] the positives' keys (k_eval_keys)
+	uint32_t *cnt;            // [pos.n] candidates in the order before the positive, excluded ones included
+	uint32_t *nok;            // [nB] candidates whose pair is ok, excluded ones included
+	uint32_t pass0;           // the launch's first pass (grid z counts on from it)
+};
+
+// What a wave of a counting kernel keeps beside the pair kernel's accumulators: the thresholds of its
+// CTX contexts, EVAL_POS each, and their counters, slot i * EVAL_POS + t in lane (slot % 64) of
+// register (slot / 64). A threshold is read with readlane (wave-uniform operands for the compares), a
+// count -- uniform, from a ballot -- is added in the slot's lane: no memory of any kind in the loop.
+template <int CTX> struct EvalTally {
+	static constexpr int H = (CTX * EVAL_POS + 63) / 64;
+	double key[H];
+	uint32_t idx[H], cnt[H];
+	uint64_t tgt[H];          // the slot's positive in the chunk, ~0: none
+	uint32_t npos;            // lane i: thresholds of context i in this pass
+	uint32_t nok;             // lane i: ok pairs of context i
+
+	DEVI void init(const EvalArgs &e, uint32_t c0, int nctx, uint32_t pass, uint32_t lane)
+	{
+		const uint64_t off = (uint64_t)pass * EVAL_POS;
+#pragma unroll
+		for (int h = 0; h < H; ++h) {
+			const uint32_t slot = lane + 64u * h, i = slot / EVAL_POS, t = slot % EVAL_POS;
+			key[h] = __builtin_nan("");
+			idx[h] = 0;
+			cnt[h] = 0;
+			tgt[h] = ~0ull;
+			if (i < (uint32_t)nctx) {
+				const uint64_t b = e.pos.ptr[c0 + i] - e.pos.base + off + t, en = e.pos.ptr[c0 + i + 1] - e.pos.base;
+				if (b < en) {
+					tgt[h] = b;
+					key[h] = e.lkey[b];
+					idx[h] = e.pos.idx[b];
+				}
+			}
+		}
+		npos = 0;
+		nok = 0;
+		if (lane < (uint32_t)nctx) {
+			const uint64_t n = e.pos.ptr[c0 + lane + 1] - e.pos.ptr[c0 + lane];
+			npos = n > off ? (uint32_t)min(n - off, (uint64_t)EVAL_POS) : 0u;
+		}
+	}
+
+	// nothing of this pass in the wave's tile (the same in all lanes)
+	DEVI bool idle() const { return __ballot(npos != 0) == 0; }
+
+	// context i of the tile (a constant after unrolling): the two pairs every lane holds for it, v0 of
+	// candidate ja and v1 of ja + 64 (in / ok: inside the slice, the pair's ok)
+	DEVI void add(int i, uint32_t lane, bool in0, bool ok0, double v0, bool in1, bool ok1, double v1, uint32_t ja)
+	{
+		const bool a0 = in0 && ok0, a1 = in1 && ok1;
+		const uint32_t n = (uint32_t)__popcll(__ballot(a0)) + (uint32_t)__popcll(__ballot(a1));
+		nok += lane == (uint32_t)i ? n : 0u;
+		const int np = __builtin_amdgcn_readlane((int)npos, i);
+		const int h = i * EVAL_POS / 64;
+		for (int t = 0; t < EVAL_POS && t < np; ++t) {
+			const int sl = (i * EVAL_POS + t) & 63;
+			const double kt = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(key[h]), sl),
+			                                   __builtin_amdgcn_readlane(__double2loint(key[h]), sl));
+			const uint32_t it = (uint32_t)__builtin_amdgcn_readlane((int)idx[h], sl);
+			const uint32_t c = (uint32_t)__popcll(__ballot(a0 && rec_better(v0, ja, kt, it))) +
+			                   (uint32_t)__popcll(__ballot(a1 && rec_better(v1, ja + 64, kt, it)));
+			cnt[h] += lane == (uint32_t)sl ? c : 0u;
+		}
+	}
+
+	// the slice is done: one integer atomicAdd per (target, slice); integer sums do not depend on the order
+	DEVI void flush(const EvalArgs &e, uint32_t c0, int nctx, uint32_t pass, uint32_t lane) const
+	{
+#pragma unroll
+		for (int h = 0; h < H; ++h)
+			if (tgt[h] != ~0ull && cnt[h]) atomicAdd(&e.cnt[tgt[h]], cnt[h]);
+		if (pass == 0 && lane < (uint32_t)nctx && nok) atomicAdd(&e.nok[c0 + lane], nok);
+	}
+};
+
+// k_rec_pairs without its lists: the same tile, slices, loads and accumulation, then the tally.
+// Grid (context tiles of REC_TILE_B, candidate slices, passes).
+__global__ __launch_bounds__(64 * REC_WAVES) void k_eval_count_mean(const double *__restrict__ qc_all, const double *__restrict__ qt,
+                                                                    const double *__restrict__ base_c,
+                                                                    const double *__restrict__ base_j, const PairArgs a,
+                                                                    const EvalArgs e)
+{
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+	const uint32_t tile = blockIdx.x * REC_WAVES + wave;
+	const uint32_t c0 = tile * REC_CTX;
+	if (c0 >= a.nB) return;
+	const int nctx = (int)min((uint32_t)REC_CTX, a.nB - c0);
+	const uint32_t pass = e.pass0 + blockIdx.z;
+	EvalTally<REC_CTX> tl;
+	tl.init(e, c0, nctx, pass, lane);
+	if (pass && tl.idle()) return;
+	const int k = a.k;
+	const uint32_t slice = blockIdx.y;
+	const uint32_t jb = (uint32_t)min((uint64_t)a.M, (uint64_t)slice * a.slice_len);
+	const uint32_t je = (uint32_t)min((uint64_t)a.M, (uint64_t)jb + a.slice_len);
+	const double *__restrict__ qc = qc_all + (size_t)tile * k * REC_CTX;
+	const double w0 = a.w0;
+	for (uint32_t j0 = jb; j0 < je; j0 += REC_STEP) {   // at most slice_len / REC_STEP steps
+		double acc[REC_CJ][REC_CTX];
+#pragma unroll
+		for (int u = 0; u < REC_CJ; ++u)
+#pragma unroll
+			for (int i = 0; i < REC_CTX; ++i) acc[u][i] = 0.0;
+		const double *__restrict__ qj = qt + j0 + lane;   // j0 + 127 < Mpad: Mpad % REC_STEP == 0
+#pragma unroll 2
+		for (int f = 0; f < k; ++f) {
+			const double v0 = qj[(size_t)f * a.Mpad], v1 = qj[(size_t)f * a.Mpad + 64];
+			const double *__restrict__ c = qc + (size_t)f * REC_CTX;
+#pragma unroll
+			for (int i = 0; i < REC_CTX; ++i) {
+				const double ci = c[i];
+				acc[0][i] = __builtin_fma(ci, v0, acc[0][i]);
+				acc[1][i] = __builtin_fma(ci, v1, acc[1][i]);
+			}
+		}
+		const double bj0 = base_j[j0 + lane], bj1 = base_j[j0 + 64 + lane];
+		const bool in0 = j0 + lane < je, in1 = j0 + 64 + lane < je;
+#pragma unroll
+		for (int i = 0; i < REC_CTX; ++i) {
+			if (i < nctx) {
+				const double bc = base_c[c0 + i];
+				const double r0 = rec_raw(bc, bj0, w0, acc[0][i]), r1 = rec_raw(bc, bj1, w0, acc[1][i]);
+				tl.add(i, lane, in0, __builtin_isfinite(r0), r0, in1, __builtin_isfinite(r1), r1, j0 + lane);
+			}
+		}
+	}
+	tl.flush(e, c0, nctx, pass, lane);
+}
+
+// k_ucb_pairs without its lists. Grid (context tiles of CTX * UCB_WAVES, candidate slices, passes).
+template <int CTX>
+__global__ __launch_bounds__(64 * UCB_WAVES) void k_eval_count_ucb(const double *__restrict__ ctx_all, const double *__restrict__ qt,
+                                                                   const double *__restrict__ zt, const double *__restrict__ ut,
+                                                                   const double *__restrict__ base_c, const double *__restrict__ base_j,
+                                                                   const double *__restrict__ tb_c, const double *__restrict__ tb_j,
+                                                                   const PairArgs a, const UcbArgs u, const EvalArgs e)
+{
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+	const uint32_t tile = blockIdx.x * UCB_WAVES + wave;
+	const uint32_t c0 = tile * CTX;
+	if (c0 >= a.nB) return;
+	const int nctx = (int)min((uint32_t)CTX, a.nB - c0);
+	const uint32_t pass = e.pass0 + blockIdx.z;
+	EvalTally<CTX> tl;
+	tl.init(e, c0, nctx, pass, lane);
+	if (pass && tl.idle()) return;
+	const int k = a.k;
+	const uint32_t slice = blockIdx.y;
+	const uint32_t jb = (uint32_t)min((uint64_t)a.M, (uint64_t)slice * a.slice_len);
+	const uint32_t je = (uint32_t)min((uint64_t)a.M, (uint64_t)jb + a.slice_len);
+	const double *__restrict__ qc = ctx_all + (size_t)tile * 3 * k * CTX;
+	const double *__restrict__ zc = qc + (size_t)k * CTX;
+	const double *__restrict__ pc = zc + (size_t)k * CTX;
+	const double w0 = a.w0;
+	for (uint32_t j0 = jb; j0 < je; j0 += REC_STEP) {   // at most slice_len / REC_STEP steps
+		double dot[REC_CJ][CTX], t[REC_CJ][CTX];
+#pragma unroll
+		for (int v = 0; v < REC_CJ; ++v)
+#pragma unroll
+			for (int i = 0; i < CTX; ++i) { dot[v][i] = 0.0; t[v][i] = 0.0; }
+		const size_t at = (size_t)j0 + lane;   // j0 + 127 < Mpad: Mpad % REC_STEP == 0
+#pragma unroll 1
+		for (int f = 0; f < k; ++f) {
+			const size_t o = (size_t)f * a.Mpad + at;
+			const double q0 = qt[o], q1 = qt[o + 64], z0 = zt[o], z1 = zt[o + 64], u0 = ut[o], u1 = ut[o + 64];
+			const double *__restrict__ cq = qc + (size_t)f * CTX;
+			const double *__restrict__ cz = zc + (size_t)f * CTX;
+			const double *__restrict__ cp = pc + (size_t)f * CTX;
+#pragma unroll
+			for (int i = 0; i < CTX; ++i) {
+				const double qi = cq[i], zi = cz[i], pi = cp[i];
+				dot[0][i] = __builtin_fma(qi, q0, dot[0][i]);
+				dot[1][i] = __builtin_fma(qi, q1, dot[1][i]);
+				t[0][i] = __builtin_fma(zi, u0, t[0][i]);
+				t[1][i] = __builtin_fma(zi, u1, t[1][i]);
+				t[0][i] = __builtin_fma(pi, z0, t[0][i]);
+				t[1][i] = __builtin_fma(pi, z1, t[1][i]);
+			}
+		}
+		const double bj0 = base_j[at], bj1 = base_j[at + 64], tj0 = tb_j[at], tj1 = tb_j[at + 64];
+		const bool in0 = j0 + lane < je, in1 = j0 + 64 + lane < je;
+#pragma unroll
+		for (int i = 0; i < CTX; ++i) {
+			if (i < nctx) {
+				const double bc = base_c[c0 + i], tc = tb_c[c0 + i];
+				const UcbVal v0 = ucb_pair(bc, bj0, w0, dot[0][i], tc, tj0, t[0][i], u);
+				const UcbVal v1 = ucb_pair(bc, bj1, w0, dot[1][i], tc, tj1, t[1][i], u);
+				tl.add(i, lane, in0, v0.ok, v0.key, in1, v1.ok, v1.key, j0 + lane);
+			}
+		}
+	}
+	tl.flush(e, c0, nctx, pass, lane);
+}
+
+// k_chain_pairs without its lists. Grid (context tiles of CHAIN_TILE_B, candidate slices, passes).
+__global__ __launch_bounds__(64 * CHAIN_WAVES) void k_eval_count_chain(const double *__restrict__ ctx_all, const double *__restrict__ qt,
+                                                                       const double *__restrict__ base_c,
+                                                                       const double *__restrict__ base_j,
+                                                                       const double *__restrict__ w0s, const PairArgs a,
+                                                                       const ChainRank u, const EvalArgs e)
+{
+	constexpr int CTX = CHAIN_CTX;
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+	const uint32_t tile = blockIdx.x * CHAIN_WAVES + wave;
+	const uint32_t c0 = tile * CTX;
+	if (c0 >= a.nB) return;
+	const int nctx = (int)min((uint32_t)CTX, a.nB - c0);
+	const uint32_t pass = e.pass0 + blockIdx.z;
+	EvalTally<CTX> tl;
+	tl.init(e, c0, nctx, pass, lane);
+	if (pass && tl.idle()) return;
+	const int k = a.k;
+	const uint32_t S = u.S;
+	const uint32_t slice = blockIdx.y;
+	const uint32_t jb = (uint32_t)min((uint64_t)a.M, (uint64_t)slice * a.slice_len);
+	const uint32_t je = (uint32_t)min((uint64_t)a.M, (uint64_t)jb + a.slice_len);
+	const double *__restrict__ qc = ctx_all + (size_t)tile * S * k * CTX;
+	for (uint32_t j0 = jb; j0 < je; j0 += REC_STEP) {   // at most slice_len / REC_STEP steps
+		double raw0[REC_CJ][CTX], sa[REC_CJ][CTX], sb[REC_CJ][CTX];
+		const size_t at = (size_t)j0 + lane;   // j0 + 127 < Mpad: Mpad % REC_STEP == 0
+#pragma unroll 1
+		for (uint32_t s = 0; s < S; ++s) {
+			double dot[REC_CJ][CTX];
+#pragma unroll
+			for (int v = 0; v < REC_CJ; ++v)
+#pragma unroll
+				for (int i = 0; i < CTX; ++i) dot[v][i] = 0.0;
+			const double *__restrict__ qj = qt + (size_t)s * k * a.Mpad + at;
+			const double *__restrict__ cs = qc + (size_t)s * k * CTX;
+#pragma unroll 2
+			for (int f = 0; f < k; ++f) {
+				const double v0 = qj[(size_t)f * a.Mpad], v1 = qj[(size_t)f * a.Mpad + 64];
+				const double *__restrict__ c = cs + (size_t)f * CTX;
+#pragma unroll
+				for (int i = 0; i < CTX; ++i) {
+					const double ci = c[i];
+					dot[0][i] = __builtin_fma(ci, v0, dot[0][i]);
+					dot[1][i] = __builtin_fma(ci, v1, dot[1][i]);
+				}
+			}
+			const double bj0 = base_j[(size_t)s * a.Mpad + at], bj1 = base_j[(size_t)s * a.Mpad + at + 64];
+			const double w0 = w0s[s];
+			const double *__restrict__ bcs = base_c + (size_t)s * a.rows_pad + c0;   // c0 + CTX <= rows_pad
+			const bool first = s == 0;
+#pragma unroll
+			for (int i = 0; i < CTX; ++i) {
+				const double bc = bcs[i];
+				chain_add(raw0[0][i], sa[0][i], sb[0][i], rec_raw(bc, bj0, w0, dot[0][i]), first);
+				chain_add(raw0[1][i], sa[1][i], sb[1][i], rec_raw(bc, bj1, w0, dot[1][i]), first);
+			}
+		}
+		const bool in0 = j0 + lane < je, in1 = j0 + 64 + lane < je;
+#pragma unroll
+		for (int i = 0; i < CTX; ++i) {
+			if (i < nctx) {
+				const ChainVal v0 = chain_val(raw0[0][i], sa[0][i], sb[0][i], u);
+				const ChainVal v1 = chain_val(raw0[1][i], sa[1][i], sb[1][i], u);
+				tl.add(i, lane, in0, v0.ok, v0.key, in1, v1.ok, v1.key, j0 + lane);
+			}
+		}
+	}
+	tl.flush(e, c0, nctx, pass, lane);
+}
+
+struct EvalFinishArgs {
+	uint32_t nB;
+	EvalList pos, excl;
+	const double *lkey;           // [pos.n + excl.n]
+	const uint32_t *cnt, *nok;    // the counting kernels' sums
+	double *key;                  // [pos.n]
+	long long *rank;              // [pos.n]
+	uint32_t *ranked, *nok_out;   // [nB] each
+};
+
+// Threads 0 .. pos.n - 1: a positive's rank is its count less the distinct excluded candidates of its
+// context that are ok and before it (rec_better is strict: a positive never counts itself); threads
+// pos.n .. pos.n + nB - 1: a context's rankable candidates. Each walks its context's exclusion list
+// once, bounded by the list; a repeated index (adjacent: the list is sorted) counts once.
+__global__ __launch_bounds__(256) void k_eval_finish(const EvalFinishArgs a)
+{
+	const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+	if (p >= a.pos.n + a.nB) return;
+	const bool is_pos = p < a.pos.n;
+	const uint32_t c = is_pos ? eval_ctx_of(a.pos, a.nB, p + a.pos.base) : (uint32_t)(p - a.pos.n);
+	const double kp = is_pos ? a.lkey[p] : 0.0;
+	const uint32_t ip = is_pos ? a.pos.idx[p] : 0u;
+	uint32_t sub = 0;
+	if (a.excl.ptr && !(is_pos && kp != kp)) {
+		const uint64_t b = a.excl.ptr[c] - a.excl.base, en = a.excl.ptr[c + 1] - a.excl.base;
+		for (uint64_t x = b; x < en; ++x) {
+			const uint32_t jx = a.excl.idx[x];
+			if (x > b && jx == a.excl.idx[x - 1]) continue;
+			const double kx = a.lkey[a.pos.n + x];
+			if (kx != kx) continue;   // not ok: in no count
+			if (!is_pos || rec_better(kx, jx, kp, ip)) sub++;
+		}
+	}
+	if (is_pos) {
+		a.key[p] = kp;
+		a.rank[p] = kp != kp ? -1ll : (long long)a.cnt[p] - (long long)sub;
+	} else {
+		a.ranked[c] = a.nok[c] - sub;
+		a.nok_out[c] = a.nok[c];
+	}
 }
 
 uint32_t round_up(uint64_t v, uint32_t to) { return (uint32_t)((v + to - 1) / to * to); }
@@ -1182,6 +1584,73 @@ void require_topn(const std::string &who, int32_t topn)
 		throw who + ": topn = " + std::to_string(topn) + " is outside 1 .. " + std::to_string(VBFM_REC_MAX_TOPN);
 }
 
+// the two kinds of set a ranking other than the plain one takes
+void require_var_set(const std::string &who, const vbfm_candidates *cs)
+{
+	if (!cs->tb)
+		throw who + ": the candidate set holds no variance sums (it was made by vbfm_candidates_create; use vbfm_candidates_create_var)";
+}
+
+void require_chain_set(const std::string &who, const vbfm_candidates *cs)
+{
+	if (!cs->S)   // such a set is never this model's: vbfm_candidates_create refuses a chain
+		throw who + ": the candidate set holds one set of sums (it was made by vbfm_candidates_create" + (cs->tb ? "_var" : "") +
+		    "; use vbfm_candidates_create_chain)";
+}
+
+void require_beta_noise(const std::string &who, double beta, int32_t noise)
+{
+	if (!std::isfinite(beta)) throw who + ": beta = " + std::to_string(beta) + " is not a finite number";
+	if (noise != 0 && noise != 1) throw who + ": noise is 0 or 1";
+}
+
+void refuse_class_noise(const std::string &who, const vbfm_model *m, int32_t noise)
+{
+	if (noise && m->task == VBFM_TASK_CLASSIFICATION)
+		throw who + ": noise = 1 adds the mean of 1 / alpha to the spread, and a model of task c has no noise precision";
+}
+
+// ucb_pair's constants of a model
+UcbArgs ucb_args(const vbfm_model *m, double beta, int32_t noise)
+{
+	UcbArgs u;
+	u.s0 = m->info.k0 ? m->info.sigma_0_dash : 0.0;
+	u.na = noise ? 1.0 / m->info.alpha : 0.0;
+	u.beta = beta;
+	return u;
+}
+
+// chain_val's constants of a chain model, and what the finish kernel makes of the draws' raw values
+ChainRank chain_rank(const vbfm_model *m, double beta, int32_t noise, int32_t clip)
+{
+	const bool cls = m->task == VBFM_TASK_CLASSIFICATION;
+	const uint32_t S = m->S;
+	ChainRank u = {};
+	u.S = S;
+	u.invS = 1.0 / (double)S;
+	if (noise) {   // the mean over the draws of 1 / alpha_s, in draw order
+		double sum = 0.0;
+		for (uint32_t s = 0; s < S; s++) sum = sum + 1.0 / m->draw_alpha[s];
+		u.na = sum / (double)S;
+	}
+	u.beta = beta;
+	u.link = !clip ? 0 : (cls ? 2 : 1);
+	u.fin = clip != 0;
+	u.mn = m->info.min_target; u.mx = m->info.max_target;
+	u.lo = cls ? 0.0 : (double)m->info.min_target;
+	u.hi = cls ? 1.0 : (double)m->info.max_target;
+	return u;
+}
+
+// what rec_raw subtracts for draw s of a chain model: its w0, or nothing without k0
+void chain_w0s(const vbfm_model *m, DevBuf<double> &w0s)
+{
+	std::vector<double> h_w0(m->S, 0.0);
+	if (m->info.k0) h_w0 = m->draw_w0;
+	w0s.alloc(m->S);
+	HIPCHK(hipMemcpy(w0s, h_w0.data(), (size_t)m->S * 8, hipMemcpyHostToDevice));
+}
+
 // have_results: every result array the call requires is there
 void require_rest(const std::string &who, const vbfm_model *m, int32_t unknown_ids, const vbfm_csr *contexts, bool have_results)
 {
@@ -1308,6 +1777,232 @@ void rank_call(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *context
 	if (st) *st = out;
 }
 
+// the positive lists of vbfm_rank_positives: positions from 0, monotone, every list strictly ascending,
+// inside the candidate set and apart from the context's exclusion list (both sorted: one merge walk)
+void check_positives(const std::string &who, uint32_t B, uint32_t M, const uint64_t *pos_ptr, const uint32_t *pos_idx,
+                     const uint64_t *excl_ptr, const uint32_t *excl_idx)
+{
+	if (pos_ptr[0] != 0) throw who + ": pos_ptr does not start at 0";
+	for (uint32_t r = 0; r < B; r++)   // the positions first: no list is read through a position that is not one
+		if (pos_ptr[r + 1] < pos_ptr[r]) throw who + ": pos_ptr is not monotone at context row " + std::to_string(r);
+	if (pos_ptr[B] && !pos_idx) throw who + ": positives without pos_idx";
+	for (uint32_t r = 0; r < B; r++) {
+		uint64_t x = excl_ptr ? excl_ptr[r] : 0;
+		const uint64_t xe = excl_ptr ? excl_ptr[r + 1] : 0;
+		for (uint64_t p = pos_ptr[r]; p < pos_ptr[r + 1]; p++) {
+			const uint32_t j = pos_idx[p];
+			if (j >= M)
+				throw who + ": the positive list of context row " + std::to_string(r) + " holds candidate index " + std::to_string(j) +
+				    ", but the candidate set has " + std::to_string(M) + " rows";
+			if (p > pos_ptr[r] && j <= pos_idx[p - 1])
+				throw who + ": the positive list of context row " + std::to_string(r) + " is not strictly ascending";
+			while (x < xe && excl_idx[x] < j) x++;
+			if (x < xe && excl_idx[x] == j)
+				throw who + ": candidate index " + std::to_string(j) + " is a positive of context row " + std::to_string(r) +
+				    " and on its exclusion list";
+		}
+	}
+}
+
+// What a ranking adds to eval_call below: its rows' preparation and tile as rank_call takes them (who,
+// planes, bases, tb, row_extra, min_rows, prepare, tile of Ranking; the rest is not read), the
+// constants of its pair expression and its counting kernel.
+struct EvalRanking {
+	Ranking d;
+	int mode = EVAL_MEAN;
+	UcbArgs u = {};
+	ChainRank ch = {};
+	const double *w0s = nullptr;  // (view: the entry point's buffer) a chain's [S]
+};
+
+// passes [e.pass0, e.pass0 + nz) of a chunk
+
+hipError_t launch_eval_count(const EvalRanking &d, uint32_t ctx, const PairPtrs &p, const PairArgs &a, const EvalArgs &e, uint32_t nz,
+                             hipStream_t s)
+{
+	if (a.nB == 0) return hipSuccess;
+	const uint32_t waves = (a.nB + ctx - 1) / ctx;
+	const dim3 grid((waves + 3) / 4, a.slices, nz);   // REC_WAVES, UCB_WAVES and CHAIN_WAVES are 4
+	static_assert(REC_WAVES == 4 && UCB_WAVES == 4 && CHAIN_WAVES == 4, "one grid for the three counting kernels");
+	if (d.mode == EVAL_MEAN)
+		k_eval_count_mean<<<grid, 64 * REC_WAVES, 0, s>>>(p.ctx_all, p.qt, p.base_c, p.base_j, a, e);
+	else if (d.mode == EVAL_UCB && ctx == UCB_CTX)
+		k_eval_count_ucb<UCB_CTX><<<grid, 64 * UCB_WAVES, 0, s>>>(p.ctx_all, p.qt, p.zt, p.ut, p.base_c, p.base_j, p.tb_c, p.tb_j, a, d.u, e);
+	else if (d.mode == EVAL_UCB)
+		k_eval_count_ucb<REC_CTX><<<grid, 64 * UCB_WAVES, 0, s>>>(p.ctx_all, p.qt, p.zt, p.ut, p.base_c, p.base_j, p.tb_c, p.tb_j, a, d.u, e);
+	else
+		k_eval_count_chain<<<grid, 64 * CHAIN_WAVES, 0, s>>>(p.ctx_all, p.qt, p.base_c, p.base_j, d.w0s, a, d.ch, e);
+	return hipGetLastError();
+}
+
+// vbfm_rank_positives (validated by its entry point): rank_call's staging and chunking -- the contexts
+// in chunks of whole rows through the two slots, each chunk [row_ptr slice | entries | excl_ptr slice |
+// excl_idx slice | pad to 8 | pos_ptr slice | pos_idx slice] prepared as the ranking prepares its rows
+// -- then the listed pairs' keys, the counting passes against the whole candidate set and the finish,
+// before the chunk's block [key | rank | ranked | nok] comes back.
+void eval_call(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *contexts, const uint64_t *excl_ptr,
+               const uint32_t *excl_idx, const uint64_t *pos_ptr, const uint32_t *pos_idx, uint64_t chunk_bytes, int32_t unknown_ids,
+               const EvalRanking &er, double *key, int64_t *rank, uint32_t *ranked, vbfm_rank_positives_stats *st)
+{
+	const double t_begin = wall_s();
+	const Ranking &d = er.d;
+	const std::string who = d.who;
+	const uint32_t B = contexts->num_rows, M = cs->M;
+	const int k = cs->k;
+	vbfm_rank_positives_stats out = {};
+	size_t need_in = 0, need_rows = 0;
+	const std::vector<ChunkPlan> plan = plan_chunks(contexts, chunk_bytes ? chunk_bytes : VBFM_SCORE_CHUNK_DEFAULT, who, &need_in,
+	                                                &need_rows, d.row_extra, d.min_rows);
+	const uint32_t ctx = d.tile(need_rows, k, 1);   // no lists: the tile of the smallest capacity
+	const auto rows_bytes = [&](uint32_t r0, uint32_t nr) {
+		return ((size_t)nr + 1) * 8 + (contexts->row_ptr[r0 + nr] - contexts->row_ptr[r0]) * 8;
+	};
+	// where a chunk's exclusion block ends (8-byte aligned: the positives' positions follow)
+	const auto excl_bytes = [&](uint32_t r0, uint32_t nr) {
+		return excl_ptr ? ((size_t)nr + 1) * 8 + ((excl_ptr[r0 + nr] - excl_ptr[r0]) * 4 + 7) / 8 * 8 : (size_t)0;
+	};
+	size_t need_pos = 0, need_listed = 0, need_out = 0;
+	for (const ChunkPlan &p : plan) {
+		const uint32_t nr = p.r1 - p.r0;
+		const size_t np = pos_ptr[p.r1] - pos_ptr[p.r0], nx = excl_ptr ? excl_ptr[p.r1] - excl_ptr[p.r0] : 0;
+		need_in = std::max(need_in, rows_bytes(p.r0, nr) + excl_bytes(p.r0, nr) + ((size_t)nr + 1) * 8 + np * 4);
+		need_pos = std::max(need_pos, np);
+		need_listed = std::max(need_listed, np + nx);
+		need_out = std::max(need_out, 2 * np + nr);
+	}
+	staging_reserve(m, need_in, need_out);
+	const size_t rows_pad = round_up(need_rows, ctx);
+	DevBuf<double> base_c(d.bases * rows_pad), tb_c;
+	if (d.tb) tb_c.alloc(rows_pad);
+	DevBuf<double> qc(d.planes * rows_pad * (size_t)k), lkey(need_listed);
+	DevBuf<uint32_t> cnt(need_pos), nok(need_rows);
+	HIPCHK(hipMemsetAsync(base_c, 0, d.bases * rows_pad * 8, m->s));
+	if (d.tb) HIPCHK(hipMemsetAsync(tb_c, 0, rows_pad * 8, m->s));
+	flags_reset(m);
+	struct { Event ev[2][5]; } pe;
+	for (auto &s : pe.ev)
+		for (Event &e : s) e.create();
+	const PairPtrs ptrs = {qc, cs->qt, cs->zt, cs->ut, base_c, cs->base, tb_c, cs->tb};
+	rotate_chunks(
+	    m, plan.size(),
+	    [&](size_t i, vbfm_model::Slot &sl) {
+		    const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
+		    size_t bytes = stage_rows(sl.h_in, contexts, r0, nr);
+		    if (excl_ptr) {
+			    const uint64_t xe0 = excl_ptr[r0], nx = excl_ptr[r0 + nr] - xe0;
+			    const size_t end = bytes + excl_bytes(r0, nr);
+			    memcpy(sl.h_in + bytes, excl_ptr + r0, ((size_t)nr + 1) * 8);
+			    bytes += ((size_t)nr + 1) * 8;
+			    if (nx) memcpy(sl.h_in + bytes, excl_idx + xe0, nx * 4);
+			    memset(sl.h_in + bytes + nx * 4, 0, end - (bytes + nx * 4));
+			    bytes = end;
+		    }
+		    const uint64_t pe0 = pos_ptr[r0], np = pos_ptr[r0 + nr] - pe0;
+		    memcpy(sl.h_in + bytes, pos_ptr + r0, ((size_t)nr + 1) * 8);
+		    bytes += ((size_t)nr + 1) * 8;
+		    if (np) memcpy(sl.h_in + bytes, pos_idx + pe0, np * 4);
+		    return bytes + np * 4;
+	    },
+	    [&](size_t i, vbfm_model::Slot &sl) {
+		    const uint32_t r0 = plan[i].r0, nr = plan[i].r1 - r0;
+		    const uint64_t np = pos_ptr[r0 + nr] - pos_ptr[r0], nx = excl_ptr ? excl_ptr[r0 + nr] - excl_ptr[r0] : 0;
+		    Event *ev = pe.ev[i & 1];
+		    HIPCHK(hipEventRecord(ev[0], m->s));
+		    if (d.prepare) d.prepare(sl.d_in, nr, contexts->row_ptr[r0], r0, base_c, qc, ctx, (uint32_t)rows_pad);
+		    else launch_prepare(m, sl.d_in, nr, contexts->row_ptr[r0], r0, base_c, tb_c, qc, ctx);
+		    HIPCHK(hipEventRecord(ev[1], m->s));
+		    PairArgs a = {};
+		    a.nB = nr; a.rows_pad = (uint32_t)rows_pad; a.M = M; a.Mpad = cs->Mpad;
+		    a.k = k;
+		    a.w0 = m->info.k0 ? m->info.w0_or_mu0 : 0.0;
+		    a.slices = pick_slices(nr, M, ctx);
+		    a.slice_len = std::max<uint32_t>(REC_STEP, round_up(((uint64_t)M + a.slices - 1) / a.slices, REC_STEP));
+		    const size_t excl_off = rows_bytes(r0, nr), pos_off = excl_off + excl_bytes(r0, nr);
+		    EvalList lp = {}, lx = {};
+		    lp.ptr = (const uint64_t *)(sl.d_in + pos_off);
+		    lp.idx = (const uint32_t *)(sl.d_in + pos_off + ((size_t)nr + 1) * 8);
+		    lp.base = pos_ptr[r0];
+		    lp.n = np;
+		    if (excl_ptr) {
+			    lx.ptr = (const uint64_t *)(sl.d_in + excl_off);
+			    lx.idx = (const uint32_t *)(sl.d_in + excl_off + ((size_t)nr + 1) * 8);
+			    lx.base = excl_ptr[r0];
+			    lx.n = nx;
+		    }
+		    if (np) HIPCHK(hipMemsetAsync(cnt, 0, np * 4, m->s));
+		    HIPCHK(hipMemsetAsync(nok, 0, (size_t)nr * 4, m->s));
+		    if (np + nx) {
+			    EvalKeyArgs ka = {};
+			    ka.mode = er.mode;
+			    ka.f.ctx_all = qc; ka.f.ctx = ctx;
+			    ka.f.qt = cs->qt; ka.f.zt = cs->zt; ka.f.ut = cs->ut;
+			    ka.f.base_c = base_c; ka.f.base_j = cs->base; ka.f.tb_c = tb_c; ka.f.tb_j = cs->tb;
+			    ka.f.nB = nr; ka.f.Mpad = cs->Mpad; ka.f.k = k;
+			    ka.f.w0 = a.w0; ka.f.u = er.u;
+			    ka.ch.ctx_all = qc; ka.ch.qt = cs->qt; ka.ch.base_c = base_c; ka.ch.base_j = cs->base; ka.ch.w0s = er.w0s;
+			    ka.ch.nB = nr; ka.ch.rows_pad = (uint32_t)rows_pad; ka.ch.Mpad = cs->Mpad; ka.ch.k = k;
+			    ka.ch.u = er.ch;
+			    ka.nB = nr;
+			    ka.pos = lp; ka.excl = lx;
+			    ka.lkey = lkey;
+			    k_eval_keys<<<(unsigned)((np + nx + 255) / 256), 256, 0, m->s>>>(ka);
+			    HIPCHK(hipGetLastError());
+		    }
+		    HIPCHK(hipEventRecord(ev[2], m->s));
+		    uint64_t most = 0;
+		    for (uint32_t r = r0; r < r0 + nr; r++) most = std::max<uint64_t>(most, pos_ptr[r + 1] - pos_ptr[r]);
+		    const uint32_t passes = (uint32_t)std::max<uint64_t>(1, (most + EVAL_POS - 1) / EVAL_POS);
+		    EvalArgs e = {};
+		    e.pos = lp;
+		    e.lkey = lkey;
+		    e.cnt = cnt; e.nok = nok;
+		    for (uint32_t z0 = 0; z0 < passes; z0 += 65535u) {   // the grid's z limit
+			    e.pass0 = z0;
+			    HIPCHK(launch_eval_count(er, ctx, ptrs, a, e, std::min<uint32_t>(65535u, passes - z0), m->s));
+		    }
+		    HIPCHK(hipEventRecord(ev[3], m->s));
+		    EvalFinishArgs fa = {};
+		    fa.nB = nr;
+		    fa.pos = lp; fa.excl = lx;
+		    fa.lkey = lkey; fa.cnt = cnt; fa.nok = nok;
+		    fa.key = sl.d_out;
+		    fa.rank = (long long *)(sl.d_out + np);
+		    fa.ranked = (uint32_t *)(sl.d_out + 2 * np);
+		    fa.nok_out = fa.ranked + nr;
+		    k_eval_finish<<<(unsigned)((np + nr + 255) / 256), 256, 0, m->s>>>(fa);
+		    HIPCHK(hipGetLastError());
+		    HIPCHK(hipEventRecord(ev[4], m->s));
+		    HIPCHK(hipMemcpyAsync(sl.h_out, sl.d_out, (2 * np + nr) * 8, hipMemcpyDeviceToHost, m->s));
+		    out.pairs += (uint64_t)nr * M;
+		    out.passes = std::max(out.passes, passes);
+	    },
+	    [&](size_t i, vbfm_model::Slot &sl) {
+		    const size_t r0 = plan[i].r0, nr = plan[i].r1 - plan[i].r0, p0 = pos_ptr[r0], np = pos_ptr[r0 + nr] - p0;
+		    if (np) {
+			    memcpy(key + p0, sl.h_out, np * 8);
+			    memcpy(rank + p0, sl.h_out + np, np * 8);
+		    }
+		    const uint32_t *tail = (const uint32_t *)(sl.h_out + 2 * np);
+		    memcpy(ranked + r0, tail, nr * 4);
+		    uint64_t ok = 0;
+		    for (size_t r = 0; r < nr; r++) ok += tail[nr + r];
+		    out.nonfinite_pairs += (uint64_t)nr * M - ok;
+		    for (size_t p = 0; p < np; p++) out.nonfinite_positives += rank[p0 + p] < 0;
+		    const Event *ev = pe.ev[i & 1];
+		    out.ms_prepare += elapsed(ev[0], ev[1]);
+		    out.ms_keys += elapsed(ev[1], ev[2]);
+		    out.ms_count += elapsed(ev[2], ev[3]);
+		    out.ms_finish += elapsed(ev[3], ev[4]);
+	    });
+	const ScoreFlags f = flags_read(m);
+	if (f.first != ~0ull && !unknown_ids) throw unknown_msg(m, f.first >> 32, (uint32_t)f.first);
+	HIPCHK(hipStreamSynchronize(m->s));
+	out.n_chunks = (uint32_t)plan.size();
+	out.positives = B ? pos_ptr[B] : 0;
+	out.ms_total = (wall_s() - t_begin) * 1e3;
+	if (st) *st = out;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1372,16 +2067,11 @@ int vbfm_recommend_ucb(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr 
 		refuse_chain_set(who, cs);
 		require_variance(m, who.c_str());
 		require_own_set(who, m, cs);
-		if (!cs->tb)
-			throw who + ": the candidate set holds no variance sums (it was made by vbfm_candidates_create; use vbfm_candidates_create_var)";
+		require_var_set(who, cs);
 		require_topn(who, o.topn);
-		if (!std::isfinite(o.beta)) throw who + ": beta = " + std::to_string(o.beta) + " is not a finite number";
-		if (o.noise != 0 && o.noise != 1) throw who + ": noise is 0 or 1";
+		require_beta_noise(who, o.beta, o.noise);
 		require_rest(who, m, o.unknown_ids, contexts, idx && count);
-		UcbArgs u;
-		u.s0 = m->info.k0 ? m->info.sigma_0_dash : 0.0;
-		u.na = o.noise ? 1.0 / m->info.alpha : 0.0;
-		u.beta = o.beta;
+		const UcbArgs u = ucb_args(m, o.beta, o.noise);
 		Ranking d;
 		d.who = who.c_str();
 		d.planes = 3;
@@ -1425,38 +2115,17 @@ int vbfm_recommend_chain(vbfm_model *m, const vbfm_candidates *cs, const vbfm_cs
 	    who, m, cs, contexts, opts,
 	    [&] {
 		    const vbfm_recommend_chain_opts o = *opts;
-		    if (!cs->S)   // such a set is never this model's: vbfm_candidates_create refuses a chain
-			    throw who + ": the candidate set holds one set of sums (it was made by vbfm_candidates_create" +
-			        (cs->tb ? "_var" : "") + "; use vbfm_candidates_create_chain)";
+		    require_chain_set(who, cs);
 		    require_own_set(who, m, cs);
 		    require_topn(who, o.topn);
-		    if (!std::isfinite(o.beta)) throw who + ": beta = " + std::to_string(o.beta) + " is not a finite number";
-		    if (o.noise != 0 && o.noise != 1) throw who + ": noise is 0 or 1";
-		    const bool cls = m->task == VBFM_TASK_CLASSIFICATION;
-		    if (o.noise && cls)
-			    throw who + ": noise = 1 adds the mean of 1 / alpha to the spread, and a model of task c has no noise precision";
+		    require_beta_noise(who, o.beta, o.noise);
+		    refuse_class_noise(who, m, o.noise);
 		    require_rest(who, m, o.unknown_ids, contexts, idx && count);
 		    const uint32_t S = m->S;
 		    const int k = cs->k;
-		    ChainRank u = {};
-		    u.S = S;
-		    u.invS = 1.0 / (double)S;
-		    if (o.noise) {   // the mean over the draws of 1 / alpha_s, in draw order
-			    double sum = 0.0;
-			    for (uint32_t s = 0; s < S; s++) sum = sum + 1.0 / m->draw_alpha[s];
-			    u.na = sum / (double)S;
-		    }
-		    u.beta = o.beta;
-		    u.link = !o.clip ? 0 : (cls ? 2 : 1);
-		    u.fin = o.clip != 0;
-		    u.mn = m->info.min_target; u.mx = m->info.max_target;
-		    u.lo = cls ? 0.0 : (double)m->info.min_target;
-		    u.hi = cls ? 1.0 : (double)m->info.max_target;
-		    // what rec_raw subtracts for draw s: its w0, or nothing without k0
-		    std::vector<double> h_w0(S, 0.0);
-		    if (m->info.k0) h_w0 = m->draw_w0;
-		    DevBuf<double> w0s(S);
-		    HIPCHK(hipMemcpy(w0s, h_w0.data(), (size_t)S * 8, hipMemcpyHostToDevice));
+		    const ChainRank u = chain_rank(m, o.beta, o.noise, o.clip);
+		    DevBuf<double> w0s;
+		    chain_w0s(m, w0s);
 		    const double *d_w0s = w0s;
 		    Ranking d;
 		    d.who = who.c_str();
@@ -1489,6 +2158,80 @@ int vbfm_recommend_chain(vbfm_model *m, const vbfm_candidates *cs, const vbfm_cs
 		              count, st);
 	    },
 	    true);
+}
+
+// The exact rank of listed candidates under the total order of vbfm_recommend (ranking MEAN),
+// vbfm_recommend_ucb (UCB) or vbfm_recommend_chain (CHAIN): that call's refusals through its helpers,
+// its preparation and tile, and eval_call in place of rank_call.
+int vbfm_rank_positives(vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr *contexts, const uint64_t *excl_ptr,
+                        const uint32_t *excl_idx, const uint64_t *pos_ptr, const uint32_t *pos_idx,
+                        const vbfm_rank_positives_opts *opts, double *key, int64_t *rank, uint32_t *ranked,
+                        vbfm_rank_positives_stats *st)
+{
+	const std::string who = "vbfm_rank_positives";
+	if (m && opts && (opts->ranking < VBFM_RANKING_MEAN || opts->ranking > VBFM_RANKING_CHAIN))
+		return mfail(m, who + ": ranking = " + std::to_string(opts->ranking) +
+		                    " is none of VBFM_RANKING_MEAN, VBFM_RANKING_UCB, VBFM_RANKING_CHAIN");
+	const bool chain = opts && opts->ranking == VBFM_RANKING_CHAIN;
+	return ranking_guarded(
+	    who, m, cs, contexts, opts,
+	    [&] {
+		    const vbfm_rank_positives_opts o = *opts;
+		    const uint32_t B = contexts->num_rows;
+		    if (!pos_ptr) throw who + ": null argument (pos_ptr)";
+		    EvalRanking er;
+		    Ranking &d = er.d;
+		    d.who = who.c_str();
+		    require_model(m, who.c_str());   // (first: a model beyond the limit has no set of its own to get further with)
+		    // the refusals of the ranking's own call, in its order
+		    if (o.ranking == VBFM_RANKING_MEAN) {
+			    refuse_chain_set(who, cs);
+			    require_own_set(who, m, cs);
+		    } else if (o.ranking == VBFM_RANKING_UCB) {
+			    refuse_chain_set(who, cs);
+			    require_variance(m, who.c_str());
+			    require_own_set(who, m, cs);
+			    require_var_set(who, cs);
+		    } else {
+			    require_chain_set(who, cs);
+			    require_own_set(who, m, cs);
+		    }
+		    require_beta_noise(who, o.beta, o.noise);
+		    if (o.ranking == VBFM_RANKING_MEAN && (o.beta != 0.0 || o.noise != 0))
+			    throw who + ": beta = " + std::to_string(o.beta) + ", noise = " + std::to_string(o.noise) +
+			        " with VBFM_RANKING_MEAN: the mean is ranked without a spread (beta = 0, noise = 0)";
+		    if (chain) refuse_class_noise(who, m, o.noise);
+		    require_rest(who, m, o.unknown_ids, contexts, ranked && (!pos_ptr[B] || (pos_idx && key && rank)));
+		    check_exclusions(who, B, cs->M, excl_ptr, excl_idx);
+		    check_positives(who, B, cs->M, pos_ptr, pos_idx, excl_ptr, excl_idx);
+		    // (nothing has touched the device so far)
+		    DevBuf<double> w0s;
+		    if (o.ranking == VBFM_RANKING_MEAN) {
+			    er.mode = EVAL_MEAN;
+			    d.tile = [](size_t, int, int) { return (uint32_t)REC_CTX; };
+		    } else if (o.ranking == VBFM_RANKING_UCB) {
+			    er.mode = EVAL_UCB;
+			    er.u = ucb_args(m, o.beta, o.noise);
+			    d.planes = 3;
+			    d.tb = true;
+			    d.tile = ucb_ctx;
+		    } else {
+			    const uint32_t S = m->S;
+			    er.mode = EVAL_CHAIN;
+			    er.ch = chain_rank(m, o.beta, o.noise, 0);
+			    chain_w0s(m, w0s);
+			    er.w0s = w0s;
+			    d.planes = (int)S;
+			    d.bases = (int)S;
+			    d.row_extra = (uint64_t)S * ((uint64_t)cs->k + 1) * 8;
+			    d.min_rows = CHAIN_CTX;
+			    d.tile = [](size_t, int, int) { return (uint32_t)CHAIN_CTX; };
+			    d.prepare = [m](const uint8_t *d_in, uint32_t nr, uint64_t e0, uint32_t r0, double *base, double *q, uint32_t q_tile,
+			                    uint32_t rows_pad) { launch_prepare_chain(m, d_in, nr, e0, r0, base, rows_pad, q, q_tile); };
+		    }
+		    eval_call(m, cs, contexts, excl_ptr, excl_idx, pos_ptr, pos_idx, o.chunk_bytes, o.unknown_ids, er, key, rank, ranked, st);
+	    },
+	    chain);
 }
 
 }  // extern "C"

@@ -21,6 +21,8 @@
 //     -candidates ITEMS -topn N [-exclude X] that mode ranks the rows of ITEMS for every row of T,
 //     with -ucb BETA [-ucb_noise 1] [-out_rank_var V] on mean + BETA * sd (a model with variances);
 //     a chain file is ranked on the mean over its draws, with -ucb plus BETA times their spread;
+//     with -positives FILE [-eval_at 5,10,20] in place of -topn the held-out candidates FILE lists per row
+//     are ranked exactly among all of ITEMS and HR@N, NDCG@N, recall@N, MRR and AUC are printed;
 //   * -method mcmc -save_model FILE -chain B,T keeps the draws of iterations B, B + T, ... and writes
 //     them as one model whose -load_model scores are the chain average (what -out reports), -out_var
 //     the spread across the draws.
@@ -95,6 +97,8 @@
 #pragma weak vbfm_chain_last_error
 #pragma weak vbfm_model_num_draws
 // ... and those of -fold_in
+// ... and that of -positives
+#pragma weak vbfm_rank_positives
 #pragma weak vbfm_fold_in
 #pragma weak vbfm_model_write
 
@@ -1090,6 +1094,8 @@ struct RecommendRun {
 	double beta = 0.0;
 	std::string rank_var_file;
 	FoldSpec fold;
+	std::string positives_file;   // -positives: held-out evaluation in place of the top N
+	std::vector<int> eval_at;
 };
 
 static bool have_recommender()
@@ -1097,38 +1103,148 @@ static bool have_recommender()
 	return have_scorer() && vbfm_candidates_create && vbfm_candidates_count && vbfm_candidates_destroy && vbfm_recommend;
 }
 
+// -exclude and -positives: line r of `file` lists candidate indices for row r of -test, in any order;
+// sorted and without duplicates, as the library takes them (idx is never left empty)
+static void read_index_lists(const std::string &file, const std::string &flag, uint32_t B, std::vector<uint64_t> &ptr,
+                             std::vector<uint32_t> &idx)
+{
+	std::ifstream in(file.c_str());
+	if (!in.is_open()) throw std::string("Unable to open file " + file);
+	ptr.push_back(0);
+	std::string line;
+	for (uint32_t row = 0; row < B; row++) {
+		if (!std::getline(in, line)) throw std::string(flag + ": " + file + " has fewer lines than -test has rows");
+		std::vector<uint32_t> ids;
+		std::istringstream ls(line);
+		long long v;
+		while (ls >> v) {
+			if (v < 0 || v > 0xffffffffll) throw std::string(flag + ": line " + std::to_string(row + 1) + " holds an index out of range");
+			ids.push_back((uint32_t)v);
+		}
+		if (!ls.eof()) throw std::string(flag + ": line " + std::to_string(row + 1) + " is not a list of indices");
+		std::sort(ids.begin(), ids.end());
+		ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+		idx.insert(idx.end(), ids.begin(), ids.end());
+		ptr.push_back(idx.size());
+	}
+	if (idx.empty()) idx.push_back(0);
+}
+
+// The metrics of a held-out evaluation (include/vbfm.h "ranking held-out candidates"; the formulas of
+// vbfm.ranking_metrics, in the same order of operations): contexts without positives are left out, a
+// positive of rank -1 is a miss. at: the cut-offs N.
+struct EvalMetrics {
+	uint64_t contexts = 0, auc_contexts = 0;
+	double ranked_mean = 0.0, mrr = 0.0, auc = 0.0;
+	std::vector<double> hr, recall, ndcg;   // one per cut-off
+};
+
+static EvalMetrics eval_metrics(uint32_t B, const uint64_t *pos_ptr, const int64_t *rank, const uint32_t *ranked,
+                                const std::vector<int> &at)
+{
+	EvalMetrics e;
+	e.hr.assign(at.size(), 0.0);
+	e.recall.assign(at.size(), 0.0);
+	e.ndcg.assign(at.size(), 0.0);
+	double ranked_sum = 0.0;
+	for (uint32_t c = 0; c < B; c++) {
+		const size_t n = (size_t)(pos_ptr[c + 1] - pos_ptr[c]);
+		if (!n) continue;
+		e.contexts++;
+		ranked_sum += (double)ranked[c];
+		std::vector<int64_t> r;
+		for (uint64_t p = pos_ptr[c]; p < pos_ptr[c + 1]; p++)
+			if (rank[p] >= 0) r.push_back(rank[p]);
+		std::sort(r.begin(), r.end());
+		for (size_t a = 0; a < at.size(); a++) {
+			const int64_t N = at[a];
+			size_t hits = 0;
+			double dcg = 0.0, idcg = 0.0;
+			for (int64_t x : r)
+				if (x < N) {
+					hits++;
+					dcg += 1.0 / std::log2((double)x + 2.0);
+				}
+			for (int64_t i = 0; i < std::min<int64_t>((int64_t)n, N); i++) idcg += 1.0 / std::log2((double)i + 2.0);
+			e.hr[a] += hits ? 1.0 : 0.0;
+			e.recall[a] += (double)hits / (double)n;
+			e.ndcg[a] += idcg > 0.0 ? dcg / idcg : 0.0;
+		}
+		if (r.empty()) continue;
+		e.mrr += 1.0 / ((double)r[0] + 1.0);
+		const int64_t nn = (int64_t)ranked[c] - (int64_t)r.size();
+		if (nn > 0) {
+			double above = 0.0;
+			for (size_t i = 0; i < r.size(); i++) above += (double)(r[i] - (int64_t)i);
+			e.auc += 1.0 - above / ((double)r.size() * (double)nn);
+			e.auc_contexts++;
+		}
+	}
+	const double nan = std::nan("");
+	const double nc = (double)e.contexts;
+	for (size_t a = 0; a < at.size(); a++) {
+		e.hr[a] = e.contexts ? e.hr[a] / nc : nan;
+		e.recall[a] = e.contexts ? e.recall[a] / nc : nan;
+		e.ndcg[a] = e.contexts ? e.ndcg[a] / nc : nan;
+	}
+	e.ranked_mean = e.contexts ? ranked_sum / nc : nan;
+	e.mrr = e.contexts ? e.mrr / nc : nan;
+	e.auc = e.auc_contexts ? e.auc / (double)e.auc_contexts : nan;
+	return e;
+}
+
+// -positives: the exact rank of every held-out candidate (vbfm_rank_positives) under the ranking
+// run_recommend would use, the "#Eval" line, and with -out line r as the row's "index:rank:key" triples
+static void run_eval(const RecommendRun &r, vbfm_model *m, const vbfm_candidates *cs, const vbfm_csr &rows, bool chain,
+                     const uint64_t *xp, const uint32_t *xi, const std::vector<uint64_t> &pptr, const std::vector<uint32_t> &pidx)
+{
+	const uint32_t B = rows.num_rows;
+	const size_t P = (size_t)pptr[B];
+	std::vector<double> key(std::max<size_t>(P, 1));
+	std::vector<int64_t> rank(std::max<size_t>(P, 1));
+	std::vector<uint32_t> ranked(std::max<uint32_t>(B, 1));
+	const vbfm_rank_positives_opts o{chain ? VBFM_RANKING_CHAIN : (r.ucb ? VBFM_RANKING_UCB : VBFM_RANKING_MEAN), r.skip_unknown ? 1 : 0,
+	                                 0, r.beta, r.ucb_noise ? 1 : 0};
+	vbfm_rank_positives_stats st;
+	if (vbfm_rank_positives(m, cs, &rows, xp, xi, pptr.data(), pidx.data(), &o, key.data(), rank.data(), ranked.data(), &st) != 0)
+		throw std::string(vbfm_model_last_error(m));
+	std::cout << "ranked " << st.positives << " positives among " << st.pairs << " pairs (" << B << " contexts x "
+	          << vbfm_candidates_count(cs) << " candidates) in " << st.ms_total << " ms: prepare " << st.ms_prepare << ", keys "
+	          << st.ms_keys << ", count " << st.ms_count << " (" << st.passes << " passes), finish " << st.ms_finish
+	          << " ms on the device";
+	if (st.nonfinite_pairs) std::cout << "; " << st.nonfinite_pairs << " pairs were not finite";
+	if (st.nonfinite_positives) std::cout << "; " << st.nonfinite_positives << " positives have no rank";
+	std::cout << std::endl;
+	const EvalMetrics e = eval_metrics(B, pptr.data(), rank.data(), ranked.data(), r.eval_at);
+	char buf[64];
+	const auto g6 = [&](double v) { snprintf(buf, sizeof(buf), "%.6g", v); return std::string(buf); };
+	std::cout << "#Eval contexts=" << e.contexts << " positives=" << P << " ranked_mean=" << g6(e.ranked_mean);
+	for (size_t a = 0; a < r.eval_at.size(); a++)
+		std::cout << " HR@" << r.eval_at[a] << "=" << g6(e.hr[a]) << " NDCG@" << r.eval_at[a] << "=" << g6(e.ndcg[a]) << " recall@"
+		          << r.eval_at[a] << "=" << g6(e.recall[a]);
+	std::cout << " MRR=" << g6(e.mrr) << " AUC=" << g6(e.auc) << std::endl;
+	if (r.out_file.empty()) return;
+	const Owned<FILE> f = open_for_writing(r.out_file);
+	for (uint32_t c = 0; c < B; c++) {
+		for (uint64_t p = pptr[c]; p < pptr[c + 1]; p++)
+			fprintf(f.get(), "%s%u:%lld:%.17g", p > pptr[c] ? " " : "", pidx[p], (long long)rank[p], key[p]);
+		fputc('\n', f.get());
+	}
+}
+
 static void run_recommend(const RecommendRun &r)
 {
-	if (!have_recommender() || (r.ucb && !(vbfm_candidates_create_var && vbfm_recommend_ucb)))
+	if (!have_recommender() || (r.ucb && !(vbfm_candidates_create_var && vbfm_recommend_ucb)) ||
+	    (!r.positives_file.empty() && !vbfm_rank_positives))
 		throw std::string("this build has no scorer");
 	Data ctx, items;
 	load(r.context_file, ctx, "contexts");
 	load(r.item_file, items, "candidates");
 	const uint32_t B = ctx.h.num_rows;
-	std::vector<uint64_t> xptr;
-	std::vector<uint32_t> xidx;
-	if (!r.exclude_file.empty()) {   // sorted and without duplicates, as the library takes them
-		std::ifstream in(r.exclude_file.c_str());
-		if (!in.is_open()) throw std::string("Unable to open file " + r.exclude_file);
-		xptr.push_back(0);
-		std::string line;
-		for (uint32_t row = 0; row < B; row++) {
-			if (!std::getline(in, line)) throw std::string("-exclude: " + r.exclude_file + " has fewer lines than -test has rows");
-			std::vector<uint32_t> ids;
-			std::istringstream ls(line);
-			long long v;
-			while (ls >> v) {
-				if (v < 0 || v > 0xffffffffll) throw std::string("-exclude: line " + std::to_string(row + 1) + " holds an index out of range");
-				ids.push_back((uint32_t)v);
-			}
-			if (!ls.eof()) throw std::string("-exclude: line " + std::to_string(row + 1) + " is not a list of indices");
-			std::sort(ids.begin(), ids.end());
-			ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-			xidx.insert(xidx.end(), ids.begin(), ids.end());
-			xptr.push_back(xidx.size());
-		}
-		if (xidx.empty()) xidx.push_back(0);
-	}
+	std::vector<uint64_t> xptr, pptr;
+	std::vector<uint32_t> xidx, pidx;
+	if (!r.exclude_file.empty()) read_index_lists(r.exclude_file, "-exclude", B, xptr, xidx);
+	if (!r.positives_file.empty()) read_index_lists(r.positives_file, "-positives", B, pptr, pidx);
 	const Owned<vbfm_model> model = load_model(r.model_file, r.device, r.fold);
 	vbfm_model *m = model.get();
 	vbfm_model_info info;
@@ -1144,14 +1260,18 @@ static void run_recommend(const RecommendRun &r)
 	if (create(&cs, m, &item_rows, r.skip_unknown ? 1 : 0) != 0) throw std::string(vbfm_model_last_error(m));
 	const Owned<vbfm_candidates> candidates(cs);   // declared after the model: destroyed before it
 	const vbfm_csr rows{B, ctx.h.nnz, ctx.h.row_ptr, ctx.h.row_ent};
+	const uint64_t *xp = xptr.empty() ? nullptr : xptr.data();
+	const uint32_t *xi = xptr.empty() ? nullptr : xidx.data();
+	if (!r.positives_file.empty()) {
+		run_eval(r, m, cs, rows, chain, xp, xi, pptr, pidx);
+		return;
+	}
 	const vbfm_recommend_opts o{r.topn, 1, r.skip_unknown ? 1 : 0, 0};
 	const size_t n = (size_t)B * (size_t)std::max(r.topn, 0);
 	std::vector<int32_t> idx(n);
 	std::vector<double> score(n), var(r.ucb ? n : 0);
 	std::vector<uint32_t> count(B);
 	vbfm_recommend_stats st;
-	const uint64_t *xp = xptr.empty() ? nullptr : xptr.data();
-	const uint32_t *xi = xptr.empty() ? nullptr : xidx.data();
 	if (chain) {   // without -ucb: beta = 0, the chain mean
 		const vbfm_recommend_chain_opts co{o.topn, o.clip, o.unknown_ids, o.chunk_bytes, r.beta, r.ucb_noise ? 1 : 0};
 		if (vbfm_recommend_chain(m, cs, &rows, xp, xi, &co, idx.data(), nullptr, score.data(), r.ucb ? var.data() : nullptr,
@@ -1394,14 +1514,35 @@ static void run_load_model(const CmdLine &cmd)
 	const FoldSpec fold = parse_fold(cmd);
 	const bool fold_only = !fold.support_file.empty() && !cmd.has("test");   // fold in and write the extended model, nothing scored
 	if (fold_only && cmd.has("out")) throw std::string("-out needs -test");
-	if (!fold_only && (!cmd.has("test") || !cmd.has("out"))) throw std::string("-load_model needs -test and -out");
+	if (!fold_only && (!cmd.has("test") || !(cmd.has("out") || cmd.has("positives"))))   // -positives prints; its -out is optional
+		throw std::string("-load_model needs -test and -out");
 	if (cmd.has("topn") && !cmd.has("candidates")) throw std::string("-topn needs -candidates");
 	if (cmd.has("exclude") && !cmd.has("candidates")) throw std::string("-exclude needs -candidates");
-	if (cmd.has("candidates") && !cmd.has("topn")) throw std::string("-candidates needs -topn");
+	if (cmd.has("positives") && !cmd.has("candidates")) throw std::string("-positives needs -candidates");
+	if (cmd.has("eval_at") && !cmd.has("candidates")) throw std::string("-eval_at needs -candidates");
+	if (cmd.has("positives") && cmd.has("topn"))
+		throw std::string("-positives ranks the held-out candidates among all of -candidates: -topn does not apply");
+	if (cmd.has("candidates") && !cmd.has("topn") && !cmd.has("positives"))
+		throw std::string("-candidates needs -topn (the best N per row) or -positives (held-out evaluation)");
+	if (cmd.has("eval_at") && !cmd.has("positives")) throw std::string("-eval_at needs -positives");
 	if (cmd.has("candidates") && cmd.has("out_var")) throw std::string("-out_var does not apply to -candidates (variances are not ranked)");
 	if (cmd.has("ucb") && !cmd.has("candidates")) throw std::string("-ucb needs -candidates");
 	if (cmd.has("ucb_noise") && !cmd.has("ucb")) throw std::string("-ucb_noise needs -ucb");
 	if (cmd.has("out_rank_var") && !cmd.has("ucb")) throw std::string("-out_rank_var needs -ucb");
+	if (cmd.has("positives") && cmd.has("out_rank_var"))
+		throw std::string("-out_rank_var does not apply to -positives (-out holds index:rank:key triples)");
+	std::vector<int> eval_at = {5, 10, 20};
+	if (cmd.has("eval_at")) {   // each cut-off once, in the order given
+		eval_at.clear();
+		for (const std::string &a : cmd.list("eval_at")) {
+			char *end = nullptr;
+			const long n = strtol(a.c_str(), &end, 10);
+			if (a.empty() || *end || n < 1 || n > 1000000000l)
+				throw std::string("-eval_at needs a list of positive integers (e.g. 5,10,20), not '" + cmd.get("eval_at") + "'");
+			if (std::find(eval_at.begin(), eval_at.end(), (int)n) == eval_at.end()) eval_at.push_back((int)n);
+		}
+		if (eval_at.empty()) throw std::string("-eval_at needs a list of positive integers (e.g. 5,10,20)");
+	}
 	double beta = 0.0;
 	if (cmd.has("ucb")) {
 		const std::string b = cmd.get("ucb");
@@ -1439,6 +1580,8 @@ static void run_load_model(const CmdLine &cmd)
 			run.ucb_noise = cmd.geti("ucb_noise", 0) != 0;
 			run.rank_var_file = cmd.get("out_rank_var");
 		}
+		run.positives_file = cmd.get("positives");
+		run.eval_at = eval_at;
 		run_recommend(run);
 		return;
 	}
@@ -1549,6 +1692,8 @@ int main(int argc, char **argv)
 		const std::string p_ucb = cmd.reg("ucb", "with -candidates: rank on mean + BETA * sd of the pair's row (vb and vb_online models, and chain files: sd is then the spread across the draws; a negative BETA ranks on a lower bound); -out still holds the scores");
 		const std::string p_ucbn = cmd.reg("ucb_noise", "with -ucb: 1 = sd is of y (T + 1/alpha), 0 (default) = of the model's mean (T)");
 		const std::string p_orv = cmd.reg("out_rank_var", "with -ucb: the returned entries' variance terms T as index:T pairs, in the layout of -out");
+		const std::string p_pos = cmd.reg("positives", "with -candidates, in place of -topn: line r lists the candidate indices (0-based rows of -candidates) held out for row r of -test; each is ranked exactly among all candidates (-exclude and -ucb apply as with -topn), the line #Eval reports HR@N, NDCG@N, recall@N, MRR and AUC, and -out (optional) holds index:rank:key triples per row");
+		const std::string p_evat = cmd.reg("eval_at", "with -positives: the cut-offs N of HR@N, NDCG@N and recall@N; default=5,10,20");
 		const std::string p_fold = cmd.reg("fold_in", "with -load_model (vb and vb_online models): extend the model by the feature ids it has never seen, fitted from the rows of this file (each holds exactly one such id) with everything else fixed, before -test is scored or ranked; -save_model writes the extended model");
 		const std::string p_foldp = cmd.reg("fold_passes", "with -fold_in: sweeps over a new id's parameters; default=20");
 		const std::string p_foldt = cmd.reg("fold_tol", "with -fold_in: stop a new id once no mean moved by more than this in a sweep; default=0 (run every sweep)");
@@ -1566,6 +1711,7 @@ int main(int argc, char **argv)
 			throw std::string("-candidates, -topn and -exclude belong to -load_model");
 		if (cmd.has(p_ucb) || cmd.has(p_ucbn) || cmd.has(p_orv))
 			throw std::string("-ucb, -ucb_noise and -out_rank_var belong to -load_model");
+		if (cmd.has(p_pos) || cmd.has(p_evat)) throw std::string("-positives and -eval_at belong to -load_model");
 		if (cmd.has(p_fold) || cmd.has(p_foldp) || cmd.has(p_foldt) || cmd.has(p_foldi) || cmd.has(p_foldw))
 			throw std::string("-fold_in and its -fold_* flags belong to -load_model");
 

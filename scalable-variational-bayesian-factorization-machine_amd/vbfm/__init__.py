@@ -19,6 +19,7 @@ built library (make -C scalable-variational-bayesian-factorization-machine_amd) 
 a HIP device every call raises.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -232,6 +233,26 @@ class RecommendStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+RANKINGS = {"mean": 0, "ucb": 1, "chain": 2}   # VBFM_RANKING_*
+
+
+class RankPositivesOpts(C.Structure):
+    """vbfm_rank_positives_opts"""
+    _fields_ = [("ranking", C.c_int32), ("unknown_ids", C.c_int32), ("chunk_bytes", C.c_uint64), ("beta", C.c_double),
+                ("noise", C.c_int32)]
+
+
+class RankPositivesStats(C.Structure):
+    """vbfm_rank_positives_stats"""
+    _fields_ = [("n_chunks", C.c_uint32), ("pairs", C.c_uint64), ("nonfinite_pairs", C.c_uint64),
+                ("positives", C.c_uint64), ("nonfinite_positives", C.c_uint64), ("passes", C.c_uint32),
+                ("ms_prepare", C.c_double), ("ms_keys", C.c_double), ("ms_count", C.c_double),
+                ("ms_finish", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class FoldOpts(C.Structure):
     """vbfm_fold_opts"""
     _fields_ = [("passes", C.c_int32), ("tol", C.c_double), ("prior_w", C.c_double), ("prior_v", P_f64),
@@ -272,7 +293,7 @@ EXPORTS = ["vbfm_abi_version", "vbfm_last_error", "vbfm_create", "vbfm_destroy",
            "vbfm_model_file_draws", "vbfm_model_write_host_chain", "vbfm_model_read_host_draw", "vbfm_model_num_draws",
            "vbfm_model_draw_scalars", "vbfm_chain_create", "vbfm_chain_add", "vbfm_chain_count", "vbfm_chain_save",
            "vbfm_model_from_chain", "vbfm_chain_destroy", "vbfm_chain_last_error",
-           "vbfm_fold_in", "vbfm_model_write"]
+           "vbfm_fold_in", "vbfm_model_write", "vbfm_rank_positives"]
 
 # vbfm_exchange_fn: int fn(void *user, void *buf, uint64_t count, int32_t dtype, int32_t op)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32)
@@ -404,6 +425,8 @@ def lib():
         L.vbfm_fold_in.argtypes = [C.POINTER(V), V, C.POINTER(Csr), P_f32, C.POINTER(FoldOpts), P_f64, P_f64,
                                    C.POINTER(FoldStats)]
         L.vbfm_model_write.argtypes = [V, C.c_char_p, C.c_uint32]
+        L.vbfm_rank_positives.argtypes = [V, V, C.POINTER(Csr), P_u64, P_u32, P_u64, P_u32, C.POINTER(RankPositivesOpts),
+                                          P_f64, C.POINTER(C.c_int64), P_u32, C.POINTER(RankPositivesStats)]
         _lib = L
     return _lib
 
@@ -1032,6 +1055,7 @@ class Model:
         self._m = handle
         self.last_stats = None
         self.last_recommend_stats = None
+        self.last_rank_stats = None
         inf = ModelInfo()
         _check(lib().vbfm_model_info_get(self._m, C.byref(inf)))
         self.info = inf.as_dict()
@@ -1295,6 +1319,36 @@ class Model:
         idx, (key, score, var), count = self._rank(lib().vbfm_recommend_chain, o, 3, contexts, candidates, topn, exclude)
         return idx, key, score, var, count
 
+    def rank_positives(self, contexts, candidates, positives, exclude=None, ranking="mean", beta=0.0, noise=False,
+                       unknown_ids="refuse", chunk_bytes=0):
+        """The exact position of held-out candidates among ALL candidates (include/vbfm.h "ranking
+        held-out candidates"), under the order of recommend (ranking="mean"), recommend_ucb ("ucb": beta,
+        noise; a candidate set made with variance=True) or recommend_chain ("chain": a chain model and a
+        set from candidates_chain). positives: one strictly ascending integer array of candidate indices
+        per context, or a (ptr, idx) pair; exclude as recommend takes it. Returns (rank int64 [P] -- the
+        rankable candidates before the positive, -1 where its own pair is not finite --, key float64 [P]
+        -- the value ranked on, NaN there --, ranked uint32 [B] -- the context's rankable candidates), P
+        the positives in the order given. ranking_metrics turns them into HR@N, NDCG@N, MRR and AUC."""
+        if ranking not in RANKINGS:
+            raise VbfmError("rank_positives: ranking is one of %s, not %r" % (", ".join(sorted(RANKINGS)), ranking))
+        rows, _keep = self._rows(contexts)
+        B = rows.num_rows
+        xp, xi = self._exclusions(exclude, B)
+        pp, pi = self._exclusions(positives, B)
+        if pp is None:
+            raise VbfmError("rank_positives: positives is a list of index arrays, one per context, or a (ptr, idx) pair")
+        P = int(pp[-1])
+        rank = np.full(max(P, 1), -1, dtype=np.int64)
+        key = np.full(max(P, 1), np.nan)
+        ranked = np.zeros(max(B, 1), dtype=np.uint32)
+        o = RankPositivesOpts(RANKINGS[ranking], UNKNOWN_IDS[unknown_ids], int(chunk_bytes), float(beta), int(bool(noise)))
+        st = RankPositivesStats()
+        self._mcheck(lib().vbfm_rank_positives(self._m, candidates._c, C.byref(rows), _ptr(xp, P_u64), _ptr(xi, P_u32),
+                                               _ptr(pp, P_u64), _ptr(pi, P_u32), C.byref(o), _ptr(key, P_f64),
+                                               rank.ctypes.data_as(C.POINTER(C.c_int64)), _ptr(ranked, P_u32), C.byref(st)))
+        self.last_rank_stats = st.as_dict()
+        return rank[:P], key[:P], ranked[:B]
+
     def fold_in(self, data, passes=20, tol=0.0, prior_w=None, prior_v=None, prior_ids=None, num_attribute=None, lanes=0,
                 chunk_bytes=0, residuals=False):
         """Attributes this VB model has never seen, fitted from support rows (include/vbfm.h "fold-in"):
@@ -1375,3 +1429,70 @@ class Candidates:
             self.close()
         except Exception:
             pass
+
+
+def ranking_metrics(positives, rank, ranked, at=(5, 10, 20)):
+    """Held-out ranking metrics from Model.rank_positives' results (pure numpy). positives: the list of
+    index arrays (or the (ptr, idx) pair) that call was given -- only the lists' lengths are read --,
+    rank [P] and ranked [B] its results. Contexts without positives are left out of every metric; a
+    positive of rank -1 is a miss. For a context with n positives and 0-based ranks r:
+        hr@N      share of contexts with some r < N
+        recall@N  mean of #{r < N} / n
+        ndcg@N    mean of DCG / IDCG, DCG = sum_{r < N} 1 / log2(r + 2), IDCG = sum_{i < min(n, N)} 1 / log2(i + 2)
+        mrr       mean of 1 / (min r + 1), 0 for a context without a valid rank
+        auc       with the valid ranks sorted r_(1) < .. < r_(n') and Nn = ranked - n':
+                  1 - sum_i (r_(i) - (i - 1)) / (n' Nn), the mean over the contexts with n' > 0 and
+                  Nn > 0; auc_contexts counts them
+    Sums run in context order, in float64. Returns a dict (also contexts and positives, the counts the
+    means are over); a metric over no context is NaN."""
+    if isinstance(positives, tuple) and len(positives) == 2:
+        ptr = np.asarray(positives[0], dtype=np.int64)
+    else:
+        ptr = np.zeros(len(positives) + 1, dtype=np.int64)
+        np.cumsum([len(p) for p in positives], out=ptr[1:])
+    rank = np.asarray(rank, dtype=np.int64)
+    ranked = np.asarray(ranked, dtype=np.int64)
+    B = len(ptr) - 1
+    if len(ranked) != B or (B and int(ptr[-1]) != len(rank)):
+        raise VbfmError("ranking_metrics: %d positives and %d contexts do not fit rank [%d] and ranked [%d]" % (
+            int(ptr[-1]) if B else 0, B, len(rank), len(ranked)))
+    at = [int(n) for n in at]
+    hr, rec, ndcg = {n: 0.0 for n in at}, {n: 0.0 for n in at}, {n: 0.0 for n in at}
+    mrr = auc = 0.0
+    contexts = auc_contexts = 0
+    for c in range(B):
+        n = int(ptr[c + 1] - ptr[c])
+        if n == 0:
+            continue
+        contexts += 1
+        r = np.sort(rank[ptr[c]:ptr[c + 1]])
+        r = r[r >= 0]
+        for N in at:
+            hit = r[r < N]
+            hr[N] += 1.0 if len(hit) else 0.0
+            rec[N] += len(hit) / n
+            dcg = idcg = 0.0
+            for x in hit:
+                dcg += 1.0 / math.log2(float(x) + 2.0)
+            for i in range(min(n, N)):
+                idcg += 1.0 / math.log2(i + 2.0)
+            ndcg[N] += dcg / idcg if idcg > 0.0 else 0.0
+        if len(r):
+            mrr += 1.0 / (float(r[0]) + 1.0)
+            nn = int(ranked[c]) - len(r)
+            if nn > 0:
+                above = 0.0
+                for i, x in enumerate(r):
+                    above += float(x - i)
+                auc += 1.0 - above / (float(len(r)) * float(nn))
+                auc_contexts += 1
+    mean = lambda v, d: v / d if d else float("nan")
+    out = {"contexts": contexts, "positives": int(ptr[-1]) if B else 0}
+    for N in at:
+        out["hr@%d" % N] = mean(hr[N], contexts)
+        out["recall@%d" % N] = mean(rec[N], contexts)
+        out["ndcg@%d" % N] = mean(ndcg[N], contexts)
+    out["mrr"] = mean(mrr, contexts)
+    out["auc"] = mean(auc, auc_contexts)
+    out["auc_contexts"] = auc_contexts
+    return out
